@@ -16,7 +16,9 @@ int(sha1(uuid)[:3], 16) % N (simple_reporter.py:116), the graph replicated per G
 GPU matching its ~1M/N traces in device batches of --chunk-traces (strong scaling: the
 total is fixed), then the keyed histogram exchange.
 
-Besides the timed device-resident line the bench reports, for rank 0 at N=1:
+A plain run sets up, warms up, times the steps and prints the headline line (metric,
+value, ms_per_step, ...); --dump-outputs DIR also writes what the last timed step computed.
+With --full the bench reports besides the timed device-resident line, for rank 0 at N=1:
   * roofline: the dominant route-search kernel of the workload (largest device time):
     SURVEY §8(d) algorithmic bytes (K3: 24 B per settled node + 16 B per relaxed edge;
     K4: 8 B per transition entry) ÷ its HIP-event time on the matcher's stream;
@@ -26,7 +28,7 @@ Besides the timed device-resident line the bench reports, for rank 0 at N=1:
   * end_to_end: the SoA input in pinned host memory → H2D → match → reports and the
     histogram back on the host (SURVEY §8(d)'s drop-in definition; PCIe included).
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
   N>1:   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -113,6 +115,61 @@ class _DevBytes:
                                          'version': 2}
 
 
+def graph_cache_dir(gname):
+    """Where the generated graph file lives: build/graphs of this tree when the graph is
+    there or can be written there; else (a checkout this user may only read) a per-user
+    cache outside the tree: $XDG_CACHE_HOME or ~/.cache, else the temporary directory.
+    The bench itself writes nothing else, and nothing into a tree it cannot write."""
+    import tempfile
+    cands = [os.path.join(ROOT, 'build', 'graphs'),
+             os.path.join(os.environ.get('XDG_CACHE_HOME') or os.path.join(os.path.expanduser('~'), '.cache'),
+                          'otr-mi355x', 'graphs'),
+             os.path.join(tempfile.gettempdir(), 'otr-mi355x-%d' % os.getuid(), 'graphs')]
+    for d in cands:
+        if os.path.exists(os.path.join(d, gname + '.otrg')):
+            return d
+    for d in cands:
+        try:
+            os.makedirs(d, exist_ok=True)
+        except OSError:
+            continue
+        if os.access(d, os.W_OK | os.X_OK):
+            return d
+    raise SystemExit('bench: no writable directory for the %s graph (tried %s)' % (gname, ', '.join(cands)))
+
+
+DUMP_ARRAY_BYTES = 20 << 20  # per array: three arrays stay under 64 MB in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy in float64, exactly.  A record array
+    becomes one row per record and one column per field, a 64-bit id field two columns (its
+    low and high 32 bits: a double holds 53); the column names go to <name>.columns.json.
+    An array beyond DUMP_ARRAY_BYTES is cut to a fixed seeded sample of its rows, in order."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        cols = None
+        if a.dtype.names:
+            cols, parts = [], []
+            for f in a.dtype.names:
+                if a.dtype[f] == np.dtype('<u8'):
+                    cols += [f + '_lo32', f + '_hi32']
+                    parts += [(a[f] & 0xFFFFFFFF).astype(np.float64), (a[f] >> 32).astype(np.float64)]
+                else:
+                    cols.append(f)
+                    parts.append(a[f].astype(np.float64))
+            a = np.stack(parts, axis=1) if len(a) else np.zeros((0, len(cols)), np.float64)
+        a = np.ascontiguousarray(a, np.float64)
+        row_bytes = max(1, a[0].nbytes) if len(a) else 1
+        keep = DUMP_ARRAY_BYTES // row_bytes
+        if len(a) > keep:
+            a = a[np.sort(np.random.default_rng(20170101).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        if cols:
+            with open(os.path.join(out_dir, name + '.columns.json'), 'w') as f:
+                json.dump(cols, f)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -160,6 +217,14 @@ def main():
     ap.add_argument('--dist', action='store_true',
                     help='run the N > 1 path (process group, uuid shards, keyed all-to-all exchange to the '
                          '(hour, tile) owner) even at N = 1: RCCL at world size 1 on one GPU')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run everything else the bench measures or checks: the '
+                         'instrumented step (per-kernel work, roofline), the oracle sample (CPU baseline, parity), '
+                         'the host-to-host and the JSON drop-in legs.  Without it the run sets up, warms up, times '
+                         'the steps and prints the headline line only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float64; a fixed seeded '
+                         'sample of an array beyond its share of 64 MB)')
     args = ap.parse_args()
 
     rank = int(os.environ.get('RANK', 0))
@@ -201,8 +266,8 @@ def main():
     if not os.path.exists(_lib.LIB_PATH):
         raise SystemExit('libotr.so missing: run python __graft_entry__.py build first')
 
-    gdir = os.path.join(ROOT, 'build', 'graphs')
     gname = {'c5': 'country', 'c1': 'city'}.get(args.workload, 'metro')
+    gdir = graph_cache_dir(gname)
     if rank == 0:
         tg = time.time()
         gpath = gen.graph_path(gname, gdir)
@@ -426,6 +491,53 @@ def main():
     elapsed = float(el.item())
     total_probes = float(probes.item())
     value = total_probes * args.steps / elapsed
+    rs = results[-1]
+
+    if args.dump_outputs:
+        # what the last timed step left its caller (before any later step reuses the matchers'
+        # buffers): per device batch its counts and, where it is the matcher's latest batch, its
+        # tile rows; the histogram this rank owns
+        arrays = {'batch_counts': np.array([[r.n_traces, r.n_probes, r.n_states, n_rows[j], r.status]
+                                            for j, r in enumerate(rs)], np.float64).reshape(len(rs), 5)}
+        if keyed:
+            arrays['hist_entries'] = owned['buf'][:owned['n'] * EW].cpu().numpy().view(_lib.HIST_ENTRY)
+            if rows_direct:
+                arrays['tile_rows'] = torch.cat(row_views).cpu().numpy().view(_lib.TILE_ROW)
+        else:
+            arrays['hist_dense'] = hist_out.cpu().numpy()
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, 'rank%d' % rank), arrays)
+
+    if not args.full:
+        # the plain run: the headline line alone (everything else the bench measures: --full)
+        if rank == 0:
+            from reporter_amd.build import source_hash
+            print(json.dumps({
+                'metric': 'GPS probes matched/sec (whole node)',
+                'value': round(value, 1),
+                'unit': 'probes/s',
+                'n_gpus': world,
+                'steps': args.steps,
+                'warmup': args.warmup,
+                'ms_per_step': round(1e3 * elapsed / args.steps, 3),
+                'higher_is_better': True,
+                'scaling': 'strong' if args.workload == 'c3' and not args.traces_per_gpu else 'weak',
+                'vs_baseline': None,
+                'dtype': 'f64',
+                'data': 'synthetic',
+                'config': {'workload': args.workload, 'graph': gname, 'nodes': n_nodes, 'directed_edges': n_edges,
+                           'osmlr_segments': n_segments, 'traces_per_gpu': mine.n_traces,
+                           'probes_per_step': int(total_probes),
+                           'histogram': ({'kind': 'keyed (SURVEY 8e)', 'privacy': args.privacy, **hist_stats}
+                                         if keyed else {'kind': 'dense [hour][segment][speed]'}),
+                           'streams': ns, 'device_batches': n_parts, 'step_wall_ms': timed_split,
+                           'output_segments': int(sum(int(r.counters[7]) for r in rs))},
+                'build': '%s:%s' % (source_hash(), os.path.basename(os.environ.get('OTR_LIB') or 'libotr.so')),
+                'full': False,
+            }), flush=True)
+        if dist_on:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- per-kernel device time over the timed steps (every stream, every step); the work
     # each kernel did comes from one more, instrumented step over the same batch (the

@@ -114,7 +114,7 @@ def test_bench_dist_flag_world1(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(_free_port()))
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--dist', '--workload', 'c2',
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--dist', '--workload', 'c2',
                           '--traces-per-gpu', '2000', '--steps', '2', '--warmup', '1', '--cpu-traces', '200',
                           '--e2e-steps', '0'], cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                          text=True, timeout=300)

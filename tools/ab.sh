@@ -21,7 +21,7 @@ for ((r = 0; r < ROUNDS; r++)); do
     tag=$(echo "$v" | tr ':=,+' '____')
     LIB=reporter_amd/libotr.so; [ "$n" != base ] && LIB=reporter_amd/libotr_$n.so
     CPU="--cpu-traces 0"; [ $r = 0 ] && CPU=""
-    env "${EV[@]}" OTR_LIB=$PWD/$LIB timeout -k 10 300 python3 -u bench.py --workload $WL --e2e-steps 0 $CPU "$@" \
+    env "${EV[@]}" OTR_LIB=$PWD/$LIB timeout -k 10 300 python3 -u bench.py --full --workload $WL --e2e-steps 0 $CPU "$@" \
       > $O/${tag}_$r.json 2> $O/${tag}_$r.err || { echo "$v round $r failed"; tail -20 $O/${tag}_$r.err; exit 1; }
     echo "$v $r ok"
   done

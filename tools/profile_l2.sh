@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 O=gpurun_out/l2
 mkdir -p $O
 timeout -k 10 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-trace --output-format csv -d $O/p1 -o run -- \
-  python3 bench.py --steps 2 --warmup 1 --cpu-traces 0 > $O/bench_p1.json 2> $O/bench_p1.err
+  python3 bench.py --full --steps 2 --warmup 1 --cpu-traces 0 > $O/bench_p1.json 2> $O/bench_p1.err
 timeout -k 10 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-trace --output-format csv -d $O/p4 -o run -- \
-  python3 bench.py --workload c4 --steps 1 --warmup 1 --cpu-traces 0 > $O/bench_p4.json 2> $O/bench_p4.err
+  python3 bench.py --full --workload c4 --steps 1 --warmup 1 --cpu-traces 0 > $O/bench_p4.json 2> $O/bench_p4.err
 echo done

@@ -18,11 +18,11 @@ for W in "$@"; do
   mkdir -p $O
   ARGS="--workload $W --cpu-traces 0 --e2e-steps 0 --json-traces 0"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o run -- \
-    python3 bench.py $ARGS --steps 5 --warmup 2 > $O/bench_kt.json 2> $O/bench_kt.err
+    python3 bench.py --full $ARGS --steps 5 --warmup 2 > $O/bench_kt.json 2> $O/bench_kt.err
   for P in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
     N=${P%% *}
     timeout -k 10 300 rocprofv3 --pmc $P --kernel-trace --output-format csv -d $O/$N -o run -- \
-      python3 bench.py $ARGS --steps 2 --warmup 1 > $O/bench_$N.json 2> $O/bench_$N.err
+      python3 bench.py --full $ARGS --steps 2 --warmup 1 > $O/bench_$N.json 2> $O/bench_$N.err
   done
   echo "$W done"
 done

@@ -14,6 +14,6 @@ i=0
 for P in "$P1" "$P2" "$P3"; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc $P --kernel-trace --output-format csv -d $O/p$i -o run -- \
-    python3 bench.py --steps 1 --warmup 1 --cpu-traces 0 --e2e-steps 0 --streams 1 "$@" > $O/bench_p$i.json 2> $O/bench_p$i.err
+    python3 bench.py --full --steps 1 --warmup 1 --cpu-traces 0 --e2e-steps 0 --streams 1 "$@" > $O/bench_p$i.json 2> $O/bench_p$i.err
 done
 echo done

@@ -7,7 +7,7 @@ export PYTHONUNBUFFERED=1
 O=gpurun_out/${1:-r6j}
 mkdir -p $O
 for W in c2 c2dep; do
-  timeout -k 10 400 python3 -u bench.py --workload $W --cpu-traces 0 --e2e-steps 0 > $O/bench_$W.json 2> $O/bench_$W.err || exit 1
+  timeout -k 10 400 python3 -u bench.py --full --workload $W --cpu-traces 0 --e2e-steps 0 > $O/bench_$W.json 2> $O/bench_$W.err || exit 1
   echo "$W ok"
 done
 for V in "1 100" "2 100" "3 100" "2 0" "2 300"; do

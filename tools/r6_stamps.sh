@@ -6,6 +6,6 @@ O=gpurun_out/${1:-r6st}
 mkdir -p $O
 shift
 for W in "$@"; do
-  OTR_LIB=$PWD/reporter_amd/libotr_stamps.so timeout -k 10 400 python3 -u bench.py --workload $W --cpu-traces 0 --e2e-steps 0 --json-traces 0 > $O/$W.json 2> $O/$W.err || exit 1
+  OTR_LIB=$PWD/reporter_amd/libotr_stamps.so timeout -k 10 400 python3 -u bench.py --full --workload $W --cpu-traces 0 --e2e-steps 0 --json-traces 0 > $O/$W.json 2> $O/$W.err || exit 1
   echo "$W ok"
 done

@@ -32,16 +32,16 @@ if [ "$T" != none ]; then
 fi
 for w in "${W[@]}"; do
   case $w in
-    c2) step c2 300 python3 -u bench.py ;;
-    c1) step c1 300 python3 -u bench.py --workload c1 --e2e-steps 0 ;;
-    c2dep) step c2dep 300 python3 -u bench.py --workload c2dep --e2e-steps 0 ;;
-    c2dep_noresume) OTR_E1RESUME=0 step c2dep_noresume 300 python3 -u bench.py --workload c2dep --e2e-steps 0 ;;
-    c4) step c4 300 python3 -u bench.py --workload c4 --e2e-steps 0 ;;
-    c5mix) step c5mix 200 python3 -u bench.py --workload c5mix --e2e-steps 0 ;;
-    c5) step c5 400 python3 -u bench.py --workload c5 --e2e-steps 0 ;;
-    c3w1) step c3_w1_rccl 600 python3 -u bench.py --dist --workload c3 --e2e-steps 0 ;;
+    c2) step c2 300 python3 -u bench.py --full ;;
+    c1) step c1 300 python3 -u bench.py --full --workload c1 --e2e-steps 0 ;;
+    c2dep) step c2dep 300 python3 -u bench.py --full --workload c2dep --e2e-steps 0 ;;
+    c2dep_noresume) OTR_E1RESUME=0 step c2dep_noresume 300 python3 -u bench.py --full --workload c2dep --e2e-steps 0 ;;
+    c4) step c4 300 python3 -u bench.py --full --workload c4 --e2e-steps 0 ;;
+    c5mix) step c5mix 200 python3 -u bench.py --full --workload c5mix --e2e-steps 0 ;;
+    c5) step c5 400 python3 -u bench.py --full --workload c5 --e2e-steps 0 ;;
+    c3w1) step c3_w1_rccl 600 python3 -u bench.py --full --dist --workload c3 --e2e-steps 0 ;;
     c3n2) OTR_BENCH_BACKEND=gloo step c3_n2_gloo 600 python3 -u -m torch.distributed.run --nnodes=1 \
-            --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 2 ;;
+            --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --full --gpus 2 ;;
   esac
 done
 echo done
