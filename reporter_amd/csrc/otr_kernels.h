@@ -19,6 +19,7 @@
 
 #include "otr_device.h"
 #include "otr_mincode.h"  // IN-gap codes of the node tables (mi_of / in_gap, mf8_of / mf8_gap)
+#include "otr_pred.h"     // the round's 32-bit predicates (in_final32, target_final32)
 #include "otr_report.h"
 
 // the first tier's table (slots per search, two searches per wave) and its load limit in
@@ -192,6 +193,12 @@ __device__ inline uint32_t wave_min_u32(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+// The eight-search (tiny) tier runs the rounds as they were before DESIGN.md §6s — pending
+// bit in the keys, 64-bit predicates, loop bounds by lane reads, dword table reset, the step
+// re-read for the rows, unpadded tables: only the country-graph workload runs it, and its
+// five-round A/B of the §6s rounds has not been made.  Compile-time, per instantiation.
+__host__ __device__ constexpr bool old_rounds(int g) { return g == 8; }
+
 // G independent searches per wave, GL = 64 / G lanes each (G = 1, 2, 4 or 8).  Per-group
 // ballots, prefix counts, minima and wave-uniform loop bounds.
 template <int G>
@@ -226,17 +233,16 @@ struct Grp {
     const int ab = a > b ? a : b, cd = c > d ? c : d;
     return ab > cd ? ab : cd;
   }
+  // every group's (group-uniform) v holds: one ballot, no lane reads through the scalar unit
+  // (the eight-search tier keeps its lane reads: it runs the earlier rounds, old_rounds())
   __device__ static bool all(bool v) {
-    if (G == 1) return __builtin_amdgcn_readfirstlane((int)v) != 0;
     if (G == 8) {
       bool r = true;
 #pragma unroll
       for (int q = 0; q < 8; ++q) r = r && __builtin_amdgcn_readlane((int)v, q * GL) != 0;
       return r;
     }
-    const bool ab = __builtin_amdgcn_readlane((int)v, 0) != 0 && __builtin_amdgcn_readlane((int)v, GL) != 0;
-    if (G == 2) return ab;
-    return ab && __builtin_amdgcn_readlane((int)v, 2 * GL) != 0 && __builtin_amdgcn_readlane((int)v, 3 * GL) != 0;
+    return __ballot(!v) == 0ull;
   }
   __device__ static uint32_t min_u32(uint32_t v) {
     if (G == 1) return wave_min_u32(v);
@@ -629,8 +635,11 @@ struct WorkE {
 #ifndef OTR_WCAP4
 #define OTR_WCAP4 16
 #endif
+// table alignment: 16 bytes, search_init fills lab[] and key[] in 16-byte stores; the tiny
+// tier's tables (at most 48 slots, old_rounds) keep their natural alignment and size
+__host__ __device__ constexpr int search_lds_align(int cap, int lm) { return cap <= 48 ? (lm == 0 ? 4 : 8) : 16; }
 template <int CAP, int LM>
-struct SearchLds {
+struct alignas(search_lds_align(CAP, LM)) SearchLds {
   static constexpr bool PRED = LM == 1;
   // one-byte minin codes (mf8) in the retry tables of 384..1024 slots: 11 B per slot
   // instead of 12 (C4: the 1024-slot tier 13 waves per CU instead of 12, 263.9 -> 257.0 ms;
@@ -648,7 +657,7 @@ struct SearchLds {
   }
   using W = typename LabelT<LM>::W;
   typename LabelT<LM>::T lab[CAP];  // label (| pred edge)
-  uint32_t key[CAP];                  // node id | INQ / REL bits, 0xFFFFFFFF empty
+  uint32_t key[CAP];                  // node id | REL bit, 0xFFFFFFFF empty
   MiT mi[CAP];                        // minin(node) code (mi_of, or mf8_of): the IN criterion's gap
   using Idx = typename std::conditional<(CAP <= 256 && !PRED), uint8_t, uint16_t>::type;
   // nodes settled per round (at most); k_paths (PRED) reuses pend + work as CAP u32 words
@@ -666,7 +675,9 @@ struct SearchLds {
 
 constexpr uint32_t kEmpty = 0xFFFFFFFFu;
 
-constexpr uint32_t kInq = 0x80000000u;   // key bit: the node is on the pending list
+// key bit: the node is on the pending list (the edge-state tables' keys; the node tables'
+// only in a dump slot, NDump: there a labelled key that is not settled is pending)
+constexpr uint32_t kInq = 0x80000000u;
 constexpr uint32_t kRel = 0x40000000u;   // key bit: the node is settled (its label is final)
 constexpr uint32_t kNodeMask = 0x0FFFFFFFu;
 constexpr uint32_t kNoLabel = 0xFFFFFFFFu;
@@ -738,11 +749,28 @@ __device__ inline int lds_insert(SearchLds<CAP, LM>& L, uint32_t node, bool* isn
 
 template <int CAP, int LM, int G = 1>
 __device__ inline void search_init(SearchLds<CAP, LM>* Ls) {
+  using S = SearchLds<CAP, LM>;
+  // labels and keys are all-ones and contiguous at the head of the table: one fill in
+  // 16-byte LDS stores (every table size in use is a multiple of 4 slots); the eight-search
+  // tier (old_rounds) writes them a dword at a time as before
+  constexpr size_t kFill = (sizeof(typename LabelT<LM>::T) + sizeof(uint32_t)) * CAP;
+  static_assert(offsetof(S, lab) == 0 && offsetof(S, key) == sizeof(typename LabelT<LM>::T) * CAP,
+                "lab[] and key[] lead the table, back to back");
+  static_assert(LabelT<LM>::kInf == (typename LabelT<LM>::T)~0ull && kEmpty == 0xFFFFFFFFu, "all-ones fill");
+  static_assert(old_rounds(G) || (kFill % 16 == 0 && sizeof(S) % 16 == 0 && alignof(S) % 16 == 0),
+                "the fill region and the tables' stride are whole 16-byte words");
   for (int q = 0; q < G; ++q) {
     SearchLds<CAP, LM>& L = Ls[q];
-    for (int k = threadIdx.x; k < CAP; k += OTR_WAVE) {
-      L.key[k] = kEmpty;
-      L.lab[k] = LabelT<LM>::kInf;
+    if constexpr (old_rounds(G)) {
+      for (int k = threadIdx.x; k < CAP; k += OTR_WAVE) {
+        L.key[k] = kEmpty;
+        L.lab[k] = LabelT<LM>::kInf;
+      }
+    } else {
+      // (the labels are read back in their own type, unsigned long long for LM 1 and 2: the
+      // __syncthreads() below orders these stores before every such read)
+      uint4* p = reinterpret_cast<uint4*>(&L);
+      for (int k = threadIdx.x; k < (int)(kFill / 16); k += OTR_WAVE) p[k] = make_uint4(kEmpty, kEmpty, kEmpty, kEmpty);
     }
     if (threadIdx.x == 0) {
       L.n_pend = 0;
@@ -786,16 +814,22 @@ __host__ __device__ inline bool pack_fits(uint32_t bmm, uint32_t sh) {
 // label and the smallest pending time + its entry time breaks the time bound) settled
 // 3.2 % fewer nodes at C2 and made the first tier 2.5 % slower (the per-round minimum,
 // six more registers).
-template <int CAP, int LM>
+template <int CAP, int LM, bool OLD = false>
 __device__ inline bool target_resolved(const SearchLds<CAP, LM>& L, const Pack& K, int tslot, uint32_t tpart,
                                        uint32_t gapT, uint32_t pd, uint32_t kmin, bool pend_empty) {
   const int ts = tslot < 0 ? 0 : tslot;
   const uint32_t key = L.key[ts];
   const typename LabelT<LM>::W lw = LabelT<LM>::label(L.lab[ts]);
-  const int64_t lab = lw == LabelT<LM>::kNone ? INT64_MAX / 4 : (int64_t)K.d(lw);
-  const int64_t next = (int64_t)kmin + (int64_t)gapT;
-  const bool unreach = (lab < next ? lab : next) + (int64_t)tpart > (int64_t)pd;
-  return (tslot < 0) | pend_empty | ((key & kRel) != 0u) | (lab < next) | unreach;
+  if constexpr (LM != 2 && !OLD) {
+    // 32-bit label words: the whole test in 32-bit arithmetic (otr_pred.h)
+    const bool fin = target_final32(lw == LabelT<LM>::kNone, K.d(lw), kmin, gapT, tpart, pd);
+    return (tslot < 0) | pend_empty | ((key & kRel) != 0u) | fin;
+  } else {
+    const int64_t lab = lw == LabelT<LM>::kNone ? INT64_MAX / 4 : (int64_t)K.d(lw);
+    const int64_t next = (int64_t)kmin + (int64_t)gapT;
+    const bool unreach = (lab < next ? lab : next) + (int64_t)tpart > (int64_t)pd;
+    return (tslot < 0) | pend_empty | ((key & kRel) != 0u) | (lab < next) | unreach;
+  }
 }
 
 // Relax edge (u → dw) with u's FINAL packed label pu: the offer (length nd, time tt) is
@@ -805,7 +839,7 @@ __device__ inline bool target_resolved(const SearchLds<CAP, LM>& L, const Pack& 
 // improvement's length enters the next round's kmin.  mq: minin(head) in 16-mm units
 // (the adjacency record carries it), stored with a new key.  Returns the slot when it
 // became newly pending.
-template <int CAP, int LM, bool COUNT = true>
+template <int CAP, int LM, bool COUNT = true, bool OLD = false>
 __device__ inline int relax_one(SearchLds<CAP, LM>& L, const Pack& K, uint32_t dw, uint32_t len_mm,
                                 uint32_t time_ds, uint32_t minin, typename LabelT<LM>::W pu, uint32_t edge,
                                 uint32_t pd, uint32_t pt, uint32_t mode_bit, uint32_t& relaxed, uint32_t& knext,
@@ -826,20 +860,29 @@ __device__ inline int relax_one(SearchLds<CAP, LM>& L, const Pack& K, uint32_t d
   const typename LabelT<LM>::T old = atomicMin(&L.lab[sl], nb);
   if (LabelT<LM>::label(nb) < LabelT<LM>::label(old)) {
     knext = nd < knext ? nd : knext;
-    const uint32_t ok = atomicOr(&L.key[sl], kInq);
-    if (!(ok & kInq)) return sl;  // newly pending: the caller appends it
+    // newly pending exactly when the node had no label: a labelled node is pending already
+    // or settled, and a settled label never improves (every later offer is at least kmin +
+    // minin, beyond it: edges are >= 1 mm); of two lanes improving one node in a round the
+    // atomic orders them, and only the first finds the empty label.  So the key needs no
+    // pending bit (a dump synthesises it, search_run)
+    if constexpr (OLD) {  // (old_rounds: the key's pending bit tells)
+      const uint32_t ok = atomicOr(&L.key[sl], kInq);
+      if (!(ok & kInq)) return sl;
+    } else {
+      if (old == LabelT<LM>::kInf) return sl;  // the caller appends it
+    }
   }
   return -1;
 }
 
 // relax_one for the plain (non-PRED) tables with its common path branch-free: the
-// group's lanes all issue the insert, label and pending-bit atomics, a lane with nothing
+// group's lanes all issue the insert and label atomics, a lane with nothing
 // to do aiming them at its own word of `sink` (a per-wave scratch row in LDS whose values
 // are never read), so the exec-mask bookkeeping of the nested ifs is gone — the scalar
 // unit, which carries it, was the search's busiest issue port.  Only a
 // probe chain past the home slot takes a branch (wave-uniform, rare).  Same slots, labels
 // and pending list as relax_one.
-template <int CAP>
+template <int CAP, bool OLD = false>
 __device__ inline int relax_sink(SearchLds<CAP, 0>& L, uint32_t* sink, const Pack& K, uint32_t dw, uint32_t len_mm,
                                  uint32_t time_ds, uint32_t minin, uint32_t pu, uint32_t pd, uint32_t pt,
                                  uint32_t mode_bit, uint32_t& relaxed, uint32_t& knext, bool& isnew) {
@@ -881,15 +924,19 @@ __device__ inline int relax_sink(SearchLds<CAP, 0>& L, uint32_t* sink, const Pac
   const uint32_t old = atomicMin(go ? &L.lab[sl] : mine, nw);
   const bool imp = go && nw < old;
   knext = (imp && nd < knext) ? nd : knext;
-  const uint32_t was = atomicOr(imp ? &L.key[sl] : mine, kInq);
-  return (imp && !(was & kInq)) ? sl : -1;  // newly pending: the caller appends it
+  if constexpr (OLD) {  // (old_rounds: the pending-bit atomic, a lane without an improvement on its scratch word)
+    const uint32_t was = atomicOr(imp ? &L.key[sl] : mine, kInq);
+    return (imp && !(was & kInq)) ? sl : -1;
+  } else {
+    return (imp && old == kNoLabel) ? sl : -1;  // newly pending (as relax_one): the caller appends it
+  }
 }
 
 // Resuming an outgrown node search in the next retry table (as otr_edge1.h does for the
 // edge-state tiers): a search that passes its table's load limit stops between two rounds
 // (no relaxation lost) and its table goes to a dump slot in HBM — every key with its label
 // and minin code (settled nodes too, whose final labels keep rejecting later offers; the
-// pending ones carry kInq), and the round's kmin; the next table re-inserts the keys,
+// pending ones carry kInq, set by the dump: labelled and not settled), and the round's kmin; the next table re-inserts the keys,
 // rebuilds the pending list and goes on with the next round: the same rounds as one big
 // table, so the same labels.  32-bit labels only (the retry tiers).  Slot (u64 words):
 // [0] entries n, [1] kmin, [2, 2 + n) label | key << 32, then the n IN gaps (u32 mm: the
@@ -929,6 +976,8 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
                            unsigned long long* rounds, unsigned long long* stamps = nullptr, uint32_t* sink = nullptr,
                            const NDump* nd = nullptr, int* dslot = nullptr) {
   using Gr = Grp<G>;
+  constexpr bool OLD = old_rounds(G);  // the eight-search tier: the rounds as before DESIGN.md §6s
+  static_assert(!(OLD && (RIN || ROUT)), "the dump and resume code assumes keys without the pending bit");
   // load-factor limit (probe chains stay short): 7/8 (the exact searches run to the
   // bounds, so a fuller first-tier table keeps more of them out of the retry tiers: C2
   // 32.5M -> 33.1M probes/s against 3/4, profiles/r03_ab_load7_bench_c2.json)
@@ -963,7 +1012,7 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
           h = h + 1 == (uint32_t)CAP ? 0u : h + 1;
         }
         sl = (int)h;
-        L.key[sl] = key;
+        L.key[sl] = key & ~kInq;  // (the dump's pending mark: the table's keys carry none)
         L.lab[sl] = (typename LabelT<LM>::T)(uint32_t)e;
         L.mi[sl] = SearchLds<CAP, LM>::code(M[k]);
         pend = (key & kInq) != 0u;
@@ -987,7 +1036,7 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
     const int sl = lds_insert(L, start, &isnew);
     L.mi[sl] = 0;
     L.lab[sl] = LabelT<LM>::make(0u, kEmpty);
-    L.key[sl] |= kInq;
+    if (OLD) L.key[sl] |= kInq;
     L.pend[0] = (Idx)sl;
   }
   __syncthreads();
@@ -1010,7 +1059,8 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
     OTR_STAMP(t0);
     const int np = done ? 0 : npend;
     OTR_STAMP(t1);
-    const bool res = done | (gl >= n_tgt) | target_resolved(L, K, tslot, tpart, gapT, pd, kmin, np == 0);
+    const bool res =
+        done | (gl >= n_tgt) | target_resolved<CAP, LM, OLD>(L, K, tslot, tpart, gapT, pd, kmin, np == 0);
     done = done || Gr::mine(__ballot(!res)) == 0ull || np == 0;
     OTR_STAMP(t2);
     cyc[0] += t1 - t0;
@@ -1019,8 +1069,11 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
     if (!done && gl == 0) ++my_rounds;
     uint32_t knext = 0xFFFFFFFFu;
     int kept = 0, nw = 0;
-    const int npx = Gr::umax(np);
-    for (int base = 0; base < npx; base += Gr::GL) {
+    // (the loops run while any lane of the wave has an entry: the ballot of their own `in`
+    // predicate, not a maximum of the groups' counts read through the scalar unit; OLD: the
+    // maximum, as before)
+    const int npx = OLD ? Gr::umax(np) : 0;
+    for (int base = 0; OLD ? base < npx : __ballot(base + gl < np) != 0ull; base += Gr::GL) {
       const int k = base + gl;
       const bool in = k < np;
       // unconditional reads (k < CAP; a lane past its group's list reads slot 0), so no
@@ -1029,19 +1082,30 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
       const W lb = LabelT<LM>::label(L.lab[sl]);
       const uint32_t key = L.key[sl];
       const uint32_t d = K.d(lb);
-      bool take = in && (uint64_t)d < (uint64_t)kmin + SearchLds<CAP, LM>::gap(L.mi[sl]);  // final (IN criterion)
+      // final (IN criterion): d < kmin + gap; the 32-bit tables test d - kmin (otr_pred.h)
       // at most WCAP settles per round; the rest stay pending (still final later)
-      take = take && nw + Gr::prefix(__ballot(take)) < WCAP;
-      const unsigned long long mt = __ballot(take), mk = __ballot(in && !take);
-      __syncthreads();
-      if (take) {
-        // off the pending list and marked settled; the relax phase's atomics on this key
-        // come after the barrier below, so a plain store suffices
-        const uint32_t node = key & kNodeMask;
-        L.work[nw + Gr::prefix(mt)] = WorkE<W>{node, lb};
-        L.key[sl] = node | kRel;
+      bool take, keep;
+      if constexpr (OLD) {
+        take = in && (uint64_t)d < (uint64_t)kmin + SearchLds<CAP, LM>::gap(L.mi[sl]);
+        take = take && nw + Gr::prefix(__ballot(take)) < WCAP;
+        keep = in && !take;
+      } else {
+        const uint32_t gp = SearchLds<CAP, LM>::gap(L.mi[sl]);
+        if constexpr (LM != 2) take = in & in_final32(d, kmin, gp);
+        else take = in & ((uint64_t)d < (uint64_t)kmin + gp);
+        take = take & (nw + Gr::prefix(__ballot(take)) < WCAP);
+        keep = in & !take;
       }
-      const bool keep = in && !take;
+      const unsigned long long mt = __ballot(take), mk = __ballot(keep);
+      __syncthreads();
+      // off the pending list and marked settled; the relax phase's atomics on this key come
+      // after the barrier below, so a plain store suffices
+      // (measured and dropped, DESIGN.md §6s: these stores branch-free through the scratch
+      // row as in relax_sink; the first tier lost 0.2 ms)
+      if (take) {
+        L.work[nw + Gr::prefix(mt)] = WorkE<W>{key & kNodeMask, lb};
+        L.key[sl] = (key & kNodeMask) | kRel;
+      }
       if (keep) L.pend[kept + Gr::prefix(mk)] = (Idx)sl;
       knext = (keep && d < knext) ? d : knext;
       nw += Gr::count(mt);
@@ -1053,9 +1117,9 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
     cyc[2] += t3 - t2;
     // relax: lane = (work node, adjacency slot), so a round's dependent chain is a single
     // relaxation; slot 3 of a node with more than 4 out-edges also walks the CSR tail
-    const int nwx = Gr::umax(4 * nw);
     uint32_t tail = 0u;  // (a lane word, not a lane mask: VALU ors instead of scalar mask updates)
-    for (int base = 0; base < nwx; base += Gr::GL) {
+    const int nwx = OLD ? Gr::umax(4 * nw) : 0;
+    for (int base = 0; OLD ? base < nwx : __ballot(base + gl < 4 * nw) != 0ull; base += Gr::GL) {
       const int k = base + gl;
       int psl = -1;
       bool isnew = false;
@@ -1071,16 +1135,16 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
         const uint32_t tt = timed ? tq : 0u;
         if constexpr (LM == 0) {
 #ifdef OTR_NO_SINK  // (A/B build: the branching relax_one)
-          psl = relax_one<CAP, LM, false>(L, K, r.x & ~kAdjMore, r.y, tt, r.z, wk.lab, 0u, pd, pt, mode_bit,
-                                          my_relaxed, knext, isnew);
+          psl = relax_one<CAP, LM, false, OLD>(L, K, r.x & ~kAdjMore, r.y, tt, r.z, wk.lab, 0u, pd, pt, mode_bit,
+                                               my_relaxed, knext, isnew);
 #else  // (every 32-bit table has its scratch row: no run-time test of `sink`)
-          psl = relax_sink<CAP>(L, sink, K, r.x & ~kAdjMore, r.y, tt, r.z, wk.lab, pd, pt, mode_bit, my_relaxed,
-                                knext, isnew);
+          psl = relax_sink<CAP, OLD>(L, sink, K, r.x & ~kAdjMore, r.y, tt, r.z, wk.lab, pd, pt, mode_bit, my_relaxed,
+                                     knext, isnew);
 #endif
         } else {
           const uint32_t e0 = LM == 1 ? g.node_row[wnode] : 0u;  // edge id = CSR row start + slot
-          psl = relax_one<CAP, LM, false>(L, K, r.x & ~kAdjMore, r.y, tt, r.z, wk.lab, e0 + slot, pd, pt, mode_bit,
-                                          my_relaxed, knext, isnew);
+          psl = relax_one<CAP, LM, false, OLD>(L, K, r.x & ~kAdjMore, r.y, tt, r.z, wk.lab, e0 + slot, pd, pt,
+                                               mode_bit, my_relaxed, knext, isnew);
         }
         tail |= slot == 3 ? (r.x & kAdjMore) : 0u;
       }
@@ -1115,7 +1179,7 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
       // through the shared counter
       if (gl == 0) L.n_pend = npend;
       __syncthreads();
-      for (int base = 0; base < nwx; base += Gr::GL) {
+      for (int base = 0; OLD ? base < nwx : __ballot(base + gl < 4 * nw) != 0ull; base += Gr::GL) {
         const int k = base + gl;
         if (k < 4 * nw && (k & 3) == 3) {
           const WorkE<W> wk = L.work[k >> 2];
@@ -1125,8 +1189,8 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
               const uint4 pk = ld16(g.edge_pack + e);  // {dst, len_mm, attr, minin(dst)}
               const uint32_t tt = timed ? g.et(__builtin_ctz(mode_bit))[e] : 0u;
               bool isnew;
-              const int psl = relax_one(L, K, pk.x | ((pk.z & 7u) << 28), pk.y, tt, pk.w, wk.lab, e, pd, pt, mode_bit,
-                                        my_relaxed, knext, isnew);
+              const int psl = relax_one<CAP, LM, true, OLD>(L, K, pk.x | ((pk.z & 7u) << 28), pk.y, tt, pk.w, wk.lab, e,
+                                                            pd, pt, mode_bit, my_relaxed, knext, isnew);
               if (psl >= 0) {
                 const int p = atomicAdd(&L.n_pend, 1);
                 if (p < SearchLds<CAP, LM>::PCAP) L.pend[p] = (Idx)psl;
@@ -1177,7 +1241,13 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
       const uint32_t key = (dump && k < CAP) ? L.key[k] : kEmpty;
       const bool has = key != kEmpty;
       const unsigned long long m = __ballot(has);
-      if (has) D[2 + n + Gr::prefix(m)] = (unsigned long long)(uint32_t)L.lab[k] | ((unsigned long long)key << 32);
+      if (has) {
+        // the table's keys carry no pending bit (relax_one): a key with a label that is not
+        // settled is pending, and the slot format keeps kInq for it
+        const uint32_t lb = (uint32_t)L.lab[k];
+        const uint32_t kq = (lb != kNoLabel && !(key & kRel)) ? key | kInq : key;
+        D[2 + n + Gr::prefix(m)] = (unsigned long long)lb | ((unsigned long long)kq << 32);
+      }
       n += Gr::count(m);
     }
     uint32_t* M = dump ? (uint32_t*)(D + 2 + n) : nullptr;
@@ -1532,13 +1602,29 @@ __device__ __forceinline__ void route_unit(const DevGraph& gr, const RouteArgs& 
   const bool have = tw < n_tasks;
   const int64_t task = have ? (LIST ? a.task_list[tw] : tw) : 0;
   OTR_STAMP(ts_in);
-  // ---- search inputs (only these stay live through the search)
+  // ---- search inputs (these, and the first tiers' staged step, stay live through the search)
   bool search, fits, forced;
   int start_tier = -1;  // >= 0: the retry tier this (first-tier) task starts in
   uint32_t tnode = kEmpty, tpart = 0, gapT = 1, d0min = 0xFFFFFFFFu, root = 0, bmm = 0, mode_bit = 1;
   uint32_t pd = 0, pt = 0xFFFFFFFFu;  // pruning bounds relative to the root (length, time)
   int Kb;
   Pack K;
+  // the step as the lanes hold it: target lane j its candidate (edge, fraction), lane q the
+  // q-th source of the previous state (index, edge, fraction, exit time).  kKeep: the first
+  // tiers keep them in registers through the search for the transition rows (they have the
+  // registers: 8 waves per SIMD allow 64); the retry tiers re-read them after the search
+  uint32_t ej = 0, e_q = 0, t_q = 0;
+  double pj = 0, p_q = 0;
+  int iq = 0;
+  // (C2 first tier 19.11 -> 18.83 ms)
+  // Invariant the kept values rest on: the setup stages them for every task that can reach
+  // the rows.  It skips the loads only for `pre` tasks (started in a retry tier), and those
+  // never write rows here: pre clears `fits`, so ok is false, and k_tasks sets pre only on
+  // tasks that are not forced (a forced step has no search to size).  A task with pre and
+  // forced both set would read rows from unstaged lanes.
+  // Kept in the timed compilations only: the counting ones (CNT, the route_work launches)
+  // carry the per-lane tallies as well and have no registers to spare.
+  constexpr bool kKeep = !LIST && !CNT && !old_rounds(G);
   {
     const uint4 r0 = have ? a.rec[3 * task] : make_uint4(0u, 0u, 0u, 0u);
     const uint4 r1 = have ? a.rec[3 * task + 1] : make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
@@ -1570,8 +1656,6 @@ __device__ __forceinline__ void route_unit(const DevGraph& gr, const RouteArgs& 
     root = r0.z;
     d0min = r1.x;
     const int32_t bt = (int32_t)r2.y;
-    uint32_t ej = 0;
-    double pj = 0;
     bool needed = false;
     uint4 cq = make_uint4(0u, 0u, 0u, 0u);
     if (have && !pre && lane < Kb) {
@@ -1582,10 +1666,11 @@ __device__ __forceinline__ void route_unit(const DevGraph& gr, const RouteArgs& 
     }
     // the task's sources staged one per lane (lane q: the q-th set bit of mask), read in
     // the loop by group shuffles: one parallel load instead of a dependent one per source
+    // (measured and dropped, DESIGN.md §6s: staging source i in lane i and looping over the
+    // mask's set bits — the shuffle index then lives in a vector register, an LDS-path
+    // permute per value instead of a lane read: every tier lost)
     const int nsrc = have && !pre ? __popcll(mask) : 0;
-    const int iq = lane < nsrc ? nth_set_bit(mask, lane) : 0;
-    uint32_t e_q = 0, t_q = 0;
-    double p_q = 0;
+    iq = lane < nsrc ? nth_set_bit(mask, lane) : 0;
     if (lane < nsrc) {
       e_q = a.cand_edge[sp * OTR_KMAX + iq];
       p_q = a.cand_p[sp * OTR_KMAX + iq];
@@ -1657,7 +1742,8 @@ __device__ __forceinline__ void route_unit(const DevGraph& gr, const RouteArgs& 
     const int sl = lds_find(L, tnode);
     if (sl >= 0 && LabelT<LM>::label(L.lab[sl]) != LabelT<LM>::kNone) lab = (int64_t)LabelT<LM>::label(L.lab[sl]);
   }
-  // ---- transition rows: re-read the step (cached) rather than hold it live through the search
+  // ---- transition rows: the retry tiers re-read the step (cached) rather than hold it live
+  // through the search; the first tiers kept it (kKeep) and load only what the rows alone need
   asm volatile("" ::: "memory");
   uint32_t ntr = 0;  // transition entries this search wrote (K4), for the work counters
   if (have && forced && Kb > Gr::GL) {
@@ -1681,22 +1767,33 @@ __device__ __forceinline__ void route_unit(const DevGraph& gr, const RouteArgs& 
     // sources staged one per lane as in the setup: {index, edge, fraction, exit part mm,
     // exit part time, edge length mm, edge time}, read by group shuffles in the row loop
     const int nsrc = __popcll(mask);
-    const int iq = lane < nsrc ? nth_set_bit(mask, lane) : 0;
-    uint32_t e_q = 0, w_q = 0, t_q = 0;
+    uint32_t w_q = 0;
     uint2 l_q = make_uint2(0u, 0u);
-    double p_q = 0;
+    if (!kKeep) {
+      // re-read below.  The first tiers start from zero in every lane, so the setup's values
+      // are dead across the search (a lane the loads skip would otherwise keep them alive,
+      // and these kernels are at their register limit)
+      if (!LIST) {
+        e_q = t_q = ej = 0u;
+        p_q = pj = 0.0;
+      }
+      iq = lane < nsrc ? nth_set_bit(mask, lane) : 0;
+    }
     if (lane < nsrc) {
-      e_q = a.cand_edge[sp * OTR_KMAX + iq];
-      p_q = a.cand_p[sp * OTR_KMAX + iq];
+      if (!kKeep) {
+        e_q = a.cand_edge[sp * OTR_KMAX + iq];
+        p_q = a.cand_p[sp * OTR_KMAX + iq];
+        if (bt >= 0) t_q = a.cprep_t[sp * OTR_KMAX + iq].y;
+      }
       w_q = a.cprep[sp * OTR_KMAX + iq].w;
-      if (bt >= 0) t_q = a.cprep_t[sp * OTR_KMAX + iq].y;
       l_q = a.clen[sp * OTR_KMAX + iq];
     }
-    uint32_t ej = 0, tpt = 0;
-    double pj = 0;
+    uint32_t tpt = 0;
     if (lane < Kb) {
-      ej = a.cand_edge[s * OTR_KMAX + lane];
-      pj = a.cand_p[s * OTR_KMAX + lane];
+      if (!kKeep) {
+        ej = a.cand_edge[s * OTR_KMAX + lane];
+        pj = a.cand_p[s * OTR_KMAX + lane];
+      }
       tpt = bt >= 0 ? a.cprep_t[s * OTR_KMAX + lane].x : 0u;
     }
     for (int q = 0; q < nsrc; ++q) {  // group-uniform trip count

@@ -943,6 +943,44 @@ typedef struct {
 
 static int g_nr_term = 3; /* A* rounds' unreachability: 1 the length bound (d + rho hq), 2 the time bound */
 void nr_set_term(int t) { g_nr_term = t; }
+
+/* Relax iterations of the two-search tier (lane pooling): the key-order
+ * searches of nr_run paired in order as route_unit pairs a wave's two tasks, round r of one
+ * beside round r of the other.  A round that settles nw nodes has 4 nw (node, slot) lanes:
+ * [0] per group, the wave runs to the longer group's trip count, sum over rounds of
+ * max(ceil(4 nwa / 32), ceil(4 nwb / 32)); [1] pooled over the wave's 64 lanes,
+ * ceil(4 (nwa + nwb) / 64); [2] rounds of the pairs (max of the two); [3] searches.  Not
+ * modelled: the 48-node cap of a round's work list, the sources of one step that share a
+ * root (one task on the GPU), the XCD order of the units. */
+#define NR_POOL_ROUNDS 4096
+static int64_t g_nr_pool[4];
+static int g_nr_prev_n = -1, g_nr_prev[NR_POOL_ROUNDS];
+static void nr_pool_pair(const int* a, int na, const int* b, int nb) {
+  const int n = na > nb ? na : nb;
+  for (int r = 0; r < n; ++r) {
+    const int x = r < na ? a[r] : 0, y = r < nb ? b[r] : 0;
+    const int ia = (4 * x + 31) / 32, ib = (4 * y + 31) / 32;
+    g_nr_pool[0] += ia > ib ? ia : ib;
+    g_nr_pool[1] += (4 * (x + y) + 63) / 64;
+  }
+  g_nr_pool[2] += n;
+}
+static void nr_pool_search(const int* nw, int n) {
+  g_nr_pool[3]++;
+  if (g_nr_prev_n < 0) {
+    g_nr_prev_n = n < NR_POOL_ROUNDS ? n : NR_POOL_ROUNDS;
+    memcpy(g_nr_prev, nw, sizeof(int) * (size_t)g_nr_prev_n);
+  } else {
+    nr_pool_pair(g_nr_prev, g_nr_prev_n, nw, n);
+    g_nr_prev_n = -1;
+  }
+}
+void nr_pool_get(int64_t* out) { /* flushes an unpaired last search (its partner group idles) */
+  if (g_nr_prev_n >= 0) nr_pool_pair(g_nr_prev, g_nr_prev_n, g_nr_prev, 0);
+  g_nr_prev_n = -1;
+  memcpy(out, g_nr_pool, sizeof(g_nr_pool));
+  memset(g_nr_pool, 0, sizeof(g_nr_pool));
+}
 int nr_run(const orc_graph* g, const orc_params* p, int32_t n_traces, const int64_t* trace_off, const double* lat,
            const double* lon, const int64_t* tms, const float* acc, double c, nr_stats* S) {
   memset(S, 0, sizeof(*S));
@@ -1049,6 +1087,8 @@ int nr_run(const orc_graph* g, const orc_params* p, int32_t n_traces, const int6
           }
           pend[np++] = root;
           int64_t settled = 0, rounds = 0, stalls = 0;
+          static int nwr[NR_POOL_ROUNDS];
+          int nwn = 0;
           for (;;) {
             if (np == 0) break;
             double fmin = 1e300, dlb = 1e300, tlb = 1e300;
@@ -1101,6 +1141,7 @@ int nr_run(const orc_graph* g, const orc_params* p, int32_t n_traces, const int6
               if (nf == 0 && pass == 0) ++stalls;
             }
             np = kept;
+            if (mode == 0 && nwn < NR_POOL_ROUNDS) nwr[nwn++] = (int)nf;
             for (uint32_t f = 0; f < nf; ++f) {
               const uint32_t u = nxt[f];
               flag[u] = 2;
@@ -1132,6 +1173,7 @@ int nr_run(const orc_graph* g, const orc_params* p, int32_t n_traces, const int6
           if (mode == 0) {
             S->settled_base += settled;
             S->rounds_base += rounds;
+            nr_pool_search(nwr, nwn);
           } else {
             S->settled_a += settled;
             S->rounds_a += rounds;
