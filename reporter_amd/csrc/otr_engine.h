@@ -10,6 +10,7 @@
 
 #include "../../include/otr.h"
 #include "otr_device.h"
+#include "otr_tiers.h"
 
 namespace otr {
 
@@ -95,7 +96,7 @@ struct Matcher {
   std::vector<unsigned long long> h_seg_id, h_rep_id, h_rep_next;
   std::vector<uint8_t> h_seg_internal;
   std::vector<otr_tile_row> h_tile_rows;
-  hipEvent_t ev[56];  // 0..19 batch stages, 20..23 ingest, 24..49 route tiers
+  hipEvent_t ev[kEvents];  // 0..19 batch stages, 20..23 ingest, then a pair per route tier slot (otr_tiers.h)
   bool ev_init = false;
 
   template <class T>

@@ -729,12 +729,6 @@ __global__ __launch_bounds__(kCShards) void k_ctr_fold(const unsigned long long*
 
 static inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
-// Retry tiers of the route search after the first (160-slot, 2 per wave) tier, as
-// capacity * 10 + searches per wave.  512x2 (two 512-slot searches per wave) takes the
-// long-bound overflows: C4 route 117 -> 112 ms against a 1024-slot G = 1 tier; a 2048-slot
-// tier before the 4096 one (2.5x its occupancy): C4 4.57M -> 4.79M probes/s.  The last tier is always the 4096-slot one (its
-// overflows are per-trace errors).  OTR_TIERS overrides the list for A/B runs, e.g.
-// "256,512x2,1024,4096".
 // the small-search tier's default size limit (keys of k_ntask's estimate; OTR_SMALL_KEYS)
 constexpr double kSmallKeys = 24.0;
 // the tiny-search tier's (eight searches per wave, at most 8 targets; OTR_TINY_KEYS)
@@ -742,25 +736,9 @@ constexpr double kTinyKeys = 12.0;
 // the small-search path tier's (keys of k_step_lists' estimate; OTR_SMALL_PATH_KEYS)
 constexpr double kSmallPathKeys = 16.0;
 
-static std::vector<int> route_tiers() {
-  std::vector<int> t;
-  const char* env = getenv("OTR_TIERS");
-  std::string spec = env ? env : "256,448x2,1024,2048";
-  size_t i = 0;
-  while (i < spec.size()) {
-    size_t j = spec.find(',', i);
-    if (j == std::string::npos) j = spec.size();
-    const std::string item = spec.substr(i, j - i);
-    const int cap = atoi(item.c_str());
-    const int gw = item.find('x') != std::string::npos ? atoi(item.c_str() + item.find('x') + 1) : 1;
-    const int code = cap * 10 + gw;
-    if (code == 2561 || code == 5121 || code == 7681 || code == 10241 || code == 20481 || code == 3842 || code == 4482 ||
-        code == 5122)
-      t.push_back(code);
-    i = j + 1;
-  }
-  if (t.size() > 4) t.resize(4);  // at most 5 retry tiers (otr_batch_result route_tier_*)
-  t.push_back(40961);
+// the node retry tiers of this process (otr_tiers.h; OTR_TIERS: A/B knob)
+static const std::vector<int>& route_tiers() {
+  static const std::vector<int> t = parse_route_tiers(getenv("OTR_TIERS"));
   return t;
 }
 
@@ -783,6 +761,112 @@ static unsigned pgrid(unsigned full, int64_t units) {
   return (unsigned)std::min<int64_t>((int64_t)full, u);
 }
 
+constexpr unsigned kCollectGrid = 512;  // blocks of a collect over the flagged tasks (a grid stride)
+
+// One batch on its way through the pipeline: what the stages share, and the stages in the
+// order run_impl calls them.  A stage returns OTR_OK or the code the batch ends with.
+struct Batch {
+  Matcher& mat;
+  const otr_trace_batch* in;
+  const ModeParams& mp;
+  otr_batch_result* out;
+  std::string* err;
+  const DevGraph& g;
+  hipStream_t stream;
+  bool timing;
+  bool used[10] = {false};
+  // traces, probes, states, tasks (NT: every task; [0, NT8) the tiny tier's, [NT8, NT8 + NT4)
+  // the small tier's), transition entries, the capacity layout's entries
+  int32_t T = 0;
+  int64_t N = 0, S = 0, NT = 0, NT4 = 0, NT8 = 0, NTR = 0, C = 0;
+  BatchDev b{};
+  CandBuf cb{};
+  StepBuf sb{};
+  PrepArgs pr{};
+  RouteArgs ra{};
+  GenArgs ga{};
+  ViterbiArgs va{};
+  SegArgs sa{};
+  HistArgs ha{};
+  size_t hist_len = 0, scan_bytes = 0;
+  int64_t *trace_state_off = nullptr, *state_probe = nullptr, *trans_off = nullptr, *path_off = nullptr,
+          *cap_off = nullptr;
+  int32_t *state_trace = nullptr, *path_len = nullptr;
+  uint32_t turn_modes = 0;  // modes whose searches carry turn costs (edge-based, k_general)
+  bool k32 = true;          // no mode keeps more than 32 candidates (K <= 32 lanes)
+  // the first tiers' size estimate (link())
+  int route_g = 2, n_est_tiers = 0;
+  float est_k = 0.f, est_v[OTR_MODES] = {};
+  uint32_t est_tier_keys[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  double tiny_keys = 0.0;
+  // work counters (kBanks banks of OTR_COUNTERS kinds x kCShards, folded at the end into
+  // n_ctr values behind them) and list counters (otr_tiers.h CntWord)
+  static constexpr size_t bank = (size_t)OTR_COUNTERS * kCShards;
+  static constexpr size_t n_ctr = kBanks * (size_t)OTR_COUNTERS;
+  unsigned long long *d_counters = nullptr, *cnt = nullptr;
+  int64_t *list = nullptr, *fail_tasks = nullptr, *flagged = nullptr;
+  int32_t *task_ovf = nullptr, *d_turn = nullptr;
+  uint32_t *trans = nullptr, *trans_tc = nullptr;
+  uint4* task_rec = nullptr;
+  // the route stages
+  unsigned long long *rwork = nullptr, *queues = nullptr;
+  int32_t* task_dump = nullptr;
+  bool node_tasks = true, turns = false, nresume = true, eresume = true;
+  // the path stage's step lists: the list's length (the back list's with two lists: small_paths), the
+  // front list's, the retry collects' index range; the (front, back) lengths on the host
+  int64_t* steps = nullptr;
+  unsigned long long *nsteps_d = nullptr, *nsteps4_d = nullptr, h_nsteps[2] = {0ull, 0ull};
+  const unsigned long long* nscan_d = nullptr;
+  int32_t* step_ovf = nullptr;
+  bool small_paths = false;
+  // what drain() brought back
+  std::vector<unsigned long long> hc;
+  unsigned long long h_fail[2] = {0ull, 0ull};  // route tasks / paths beyond every search tier
+  std::vector<int64_t> route_n, seg_n, way_n, rep_n;
+
+  // the stages, in order
+  int upload(), states(), candidates(), link(), route_first(), route_retry(), route_edge(), route_global(), viterbi();
+  int paths(), paths_attempt(int64_t capacity), segments(), drain(), debug_fail(), name_failed();
+  void fold_counters();
+  int copy_out();
+
+  template <class X> X* need(int slot, size_t n) { return mat.need<X>(slot, n); }
+  template <class X> X* want(int slot, size_t n) { return mat.want<X>(slot, n); }
+  // stage k's event pair (OTR_BATCH_TIMING)
+  void tb(int k) {
+    if (timing) (void)hipEventRecord(mat.ev[2 * k], stream);
+  }
+  void te(int k) {
+    if (timing) (void)hipEventRecord(mat.ev[2 * k + 1], stream), used[k] = true;
+  }
+  // a route tier's event pair, counter bank (when counting was asked for), list counter and queue
+  void tier_begin(int slot) {
+    if (timing) (void)hipEventRecord(mat.ev[route_event(slot)], stream);
+  }
+  void tier_end(int slot) {
+    if (timing) (void)hipEventRecord(mat.ev[route_event(slot) + 1], stream);
+  }
+  unsigned long long* tier_bank(int slot) const { return d_counters + kRouteTiers[slot].bank * bank; }
+  unsigned long long* tier_work(int slot) const { return rwork ? tier_bank(slot) : nullptr; }
+  unsigned long long* tier_list(int slot) const { return cnt + kRouteTiers[slot].list; }
+  unsigned long long* tier_queue(int slot) const { return queues + kRouteTiers[slot].queue * kQueueWords; }
+  unsigned long long ctr(int bank_, int k) const { return hc[(size_t)bank_ * OTR_COUNTERS + (size_t)k]; }
+
+  int scan(const int64_t* src, int64_t* dst_np1, int64_t n);
+  int read_i64(const int64_t* p, int64_t* v);
+  int slabs(int tier, GSlabs* out);
+  template <class V>
+  int dl(V& vec, const void* src, size_t n) {
+    vec.resize(n ? n : 1);
+    if (n) HIPCHK(hipMemcpyAsync(vec.data(), src, n * sizeof(vec[0]), hipMemcpyDeviceToHost, stream));
+    return OTR_OK;
+  }
+  template <int CAP, int G, bool LIST>
+  void launch_route(unsigned grid, const RouteArgs& args, unsigned long long* ctr_bank);
+  void first_tier(int slot, int cap, int g_, int64_t n_tasks, int64_t task_base, int64_t units);
+  int retry_tier(int code, const RouteArgs& rb, unsigned long long* ctr_bank);
+};
+
 int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch_result* out, std::string* err) {
   GraphState& gs = graph_state();
   std::shared_lock<std::shared_mutex> graph_lock(gs.mu);  // a reconfigure waits for this batch
@@ -796,25 +880,23 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
     for (auto& e : ev) HIPCHK(hipEventCreate(&e));
     ev_init = true;
   }
-  const bool timing = (in->flags & OTR_BATCH_TIMING) != 0;
-  bool used[10] = {false};
-  auto tb = [&](int k) {
-    if (timing) (void)hipEventRecord(ev[2 * k], stream);
-  };
-  auto te = [&](int k) {
-    if (timing) {
-      (void)hipEventRecord(ev[2 * k + 1], stream);
-      used[k] = true;
-    }
-  };
   memset(out, 0, sizeof(*out));
-  const int32_t T = in->n_traces;
-  out->n_traces = T;
-  if (T <= 0) return OTR_OK;
-  const DevGraph& g = gs.dg;
-  BatchDev b{};
+  out->n_traces = in->n_traces;
+  if (in->n_traces <= 0) return OTR_OK;
+  Batch c{*this, in, mp, out, err, gs.dg, stream, (in->flags & OTR_BATCH_TIMING) != 0};
+  c.T = in->n_traces;
+  int rc;
+  if ((rc = c.upload()) || (rc = c.states()) || (rc = c.candidates()) || (rc = c.link()) || (rc = c.route_first()) ||
+      (rc = c.route_retry()) || (rc = c.route_edge()) || (rc = c.route_global()) || (rc = c.viterbi()) ||
+      (rc = c.paths()) || (rc = c.segments()) || (rc = c.drain()) || (rc = c.debug_fail()) || (rc = c.name_failed()))
+    return rc;
+  c.fold_counters();
+  return c.copy_out();
+}
+
+// input upload (host batches), the batch-size check, the work counters
+int Batch::upload() {
   b.n_traces = T;
-  int64_t N = 0;
   if (in->memory == OTR_MEM_HOST) {
     N = in->trace_offsets[T];
     int64_t* d_off = need<int64_t>(S_TRACE_OFF, T + 1);
@@ -823,10 +905,6 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
     int64_t* d_time = need<int64_t>(S_TIME, N);
     uint8_t* d_mode = need<uint8_t>(S_MODE, T);
     float* d_acc = in->accuracy ? need<float>(S_ACC, N) : nullptr;
-    if (!d_off || !d_lat || !d_lon || !d_time || !d_mode || (in->accuracy && !d_acc)) {
-      if (err) *err = "device allocation failed";
-      return OTR_DEVICE_ERROR;
-    }
     HIPCHK(hipMemcpyAsync(d_off, in->trace_offsets, 8 * (T + 1), hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpyAsync(d_lat, in->lat, 8 * N, hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpyAsync(d_lon, in->lon, 8 * N, hipMemcpyHostToDevice, stream));
@@ -860,60 +938,55 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
              " per otr_match_batch call";
     return OTR_BAD_REQUEST;
   }
-  h_trace_status.assign(T, OTR_OK);
-  // counter banks of OTR_COUNTERS kinds x kCShards: 0 the batch (and the first route
-  // tier), 1 the 512-state edge tier, 2..6 the LDS retry tiers, 7 the 64-bit tier, 8..9 the
-  // global-memory tiers, 10 the first edge tier, 11 the 1024-state edge tier, 12 the
-  // small-search first tier, 13 the tiny-search one; folded at
-  // the end into n_ctr values behind them
-  constexpr int kBanks = 14;
-  const size_t bank = (size_t)OTR_COUNTERS * kCShards;
-  const size_t n_ctr = kBanks * (size_t)OTR_COUNTERS;
-  unsigned long long* d_counters = need<unsigned long long>(S_COUNTERS, kBanks * bank + n_ctr);
+  mat.h_trace_status.assign(T, OTR_OK);
+  d_counters = need<unsigned long long>(S_COUNTERS, kBanks * bank + n_ctr);
   HIPCHK(hipMemsetAsync(d_counters, 0, kBanks * bank * 8, stream));
-  size_t scan_bytes = 0;
-  auto scan = [&](const int64_t* src, int64_t* dst_np1, int64_t n) -> int {
-    // dst[0] = 0, dst[1..n] = inclusive prefix sums
-    HIPCHK(hipMemsetAsync(dst_np1, 0, 8, stream));
-    if (n == 0) return OTR_OK;
-    size_t tb = 0;
-    HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, src, dst_np1 + 1, (int)n, stream));
-    void* tmp = need<char>(S_SCAN_TMP, tb > scan_bytes ? tb : scan_bytes);
-    scan_bytes = scan_bytes > tb ? scan_bytes : tb;
-    HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, src, dst_np1 + 1, (int)n, stream));
-    return OTR_OK;
-  };
-  auto read_i64 = [&](const int64_t* p, int64_t* v) -> int {
-    HIPCHK(hipMemcpyAsync(v, p, 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    return OTR_OK;
-  };
+  return OTR_OK;
+}
+
+// dst[0] = 0, dst[1..n] = inclusive prefix sums
+int Batch::scan(const int64_t* src, int64_t* dst_np1, int64_t n) {
+  HIPCHK(hipMemsetAsync(dst_np1, 0, 8, stream));
+  if (n == 0) return OTR_OK;
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, src, dst_np1 + 1, (int)n, stream));
+  void* tmp = need<char>(S_SCAN_TMP, tb > scan_bytes ? tb : scan_bytes);
+  scan_bytes = scan_bytes > tb ? scan_bytes : tb;
+  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, src, dst_np1 + 1, (int)n, stream));
+  return OTR_OK;
+}
+
+int Batch::read_i64(const int64_t* p, int64_t* v) {
+  HIPCHK(hipMemcpyAsync(v, p, 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  return OTR_OK;
+}
+
+// ---- K0: states
+int Batch::states() {
   int rc;
-  // ---- K0: states
   int64_t* state_cnt = need<int64_t>(S_STATE_CNT, T);
-  int64_t* trace_state_off = need<int64_t>(S_TRACE_STATE_OFF, T + 1);
+  trace_state_off = need<int64_t>(S_TRACE_STATE_OFF, T + 1);
   tb(OTR_STAGE_STATES);
   k_select_states<<<grid_for(T, 256), 256, 0, stream>>>(b, mp, state_cnt, nullptr, nullptr, nullptr);
   te(OTR_STAGE_STATES);
   if ((rc = scan(state_cnt, trace_state_off, T))) return rc;
-  int64_t S = 0;
   if ((rc = read_i64(trace_state_off + T, &S))) return rc;
   out->n_states = S;
-  int64_t* state_probe = need<int64_t>(S_STATE_PROBE, S);
-  int32_t* state_trace = need<int32_t>(S_STATE_TRACE, S);
+  state_probe = need<int64_t>(S_STATE_PROBE, S);
+  state_trace = need<int32_t>(S_STATE_TRACE, S);
   k_select_states<<<grid_for(T, 256), 256, 0, stream>>>(b, mp, state_cnt, trace_state_off, state_probe,
                                                         state_trace);
-  // ---- K1: candidates
-  CandBuf cb;
+  return OTR_OK;
+}
+
+// ---- K1: candidates
+int Batch::candidates() {
   cb.edge = need<uint32_t>(S_CAND_EDGE, (size_t)S * OTR_KMAX);
   cb.p = need<double>(S_CAND_P, (size_t)S * OTR_KMAX);
   cb.sqd = need<double>(S_CAND_SQD, (size_t)S * OTR_KMAX);
   cb.count = need<int32_t>(S_CAND_COUNT, S);
   cb.radius = need<double>(S_CAND_RADIUS, S);
-  if (!cb.edge || !cb.p || !cb.sqd || !cb.count) {
-    if (err) *err = "device allocation failed (candidates)";
-    return OTR_DEVICE_ERROR;
-  }
   if (S > 0) {
     tb(OTR_STAGE_CANDIDATES);
     // two states per wave when no mode keeps more than 32 candidates (lane groups of 32) and
@@ -937,11 +1010,15 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
                                                                         d_counters);
     te(OTR_STAGE_CANDIDATES);
   }
-  // ---- K_link + task map
-  uint32_t turn_modes = 0;  // modes whose searches carry turn costs (edge-based, k_general)
+  return OTR_OK;
+}
+
+// ---- K_link + task map: link, per-state search inputs, the first tiers' size estimate, task
+// counts and records (K_link, K2b, K2, K2c)
+int Batch::link() {
+  int rc;
   for (int m = 0; m < OTR_MODES; ++m)
     if (mp.m[m].turn_penalty_factor > 0.0) turn_modes |= 1u << m;
-  StepBuf sb;
   sb.prev = need<int64_t>(S_PREV, S);
   sb.g = need<double>(S_G, S);
   sb.bound = need<double>(S_BOUND, S);
@@ -950,11 +1027,10 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
   sb.ntask = need<int64_t>(S_NTASK, S);
   sb.ntrans = need<int64_t>(S_NTRANS, S);
   int64_t* task_off = need<int64_t>(S_TASK_OFF, S + 1);
-  int64_t* trans_off = need<int64_t>(S_TRANS_OFF, S + 1);
+  trans_off = need<int64_t>(S_TRANS_OFF, S + 1);
   tb(OTR_STAGE_LINK);  // (K_link, the search inputs and the task records: through k_tasks)
   k_link<<<(unsigned)grid_link(T).blocks, 256, 0, stream>>>(b, mp, trace_state_off, state_probe, cb.count, sb);
   // K2b: per-state search inputs
-  PrepArgs pr{};
   pr.n_states = S;
   pr.prev = sb.prev;
   pr.bound = sb.bound;
@@ -968,12 +1044,7 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
   pr.clen = need<uint2>(S_CLEN, (size_t)S * OTR_KMAX);
   pr.nroot = need<int32_t>(S_CAND_NROOT, S);
   pr.turn_modes = turn_modes;
-  if (!pr.cprep || !pr.cprep_t || !pr.clen || !pr.nroot) {
-    if (err) *err = "device allocation failed (prep)";
-    return OTR_DEVICE_ERROR;
-  }
   // two states per wave when no mode keeps more than 32 candidates (K <= 32 lanes)
-  bool k32 = true;
   for (int m = 0; m < OTR_MODES; ++m) k32 = k32 && mp.m[m].kmax <= 32;
   if (S > 0) {
     if (k32) k_prep<2><<<(unsigned)grid_per_state_waves(S, 2).blocks, 256, 0, stream>>>(g, pr);
@@ -990,10 +1061,8 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
   // profiles/r03_est_*).  OTR_EST_K scales c (A/B knob; 0 = every search starts in the
   // first tier).  A step whose estimate is at most OTR_SMALL_KEYS keys (and has at most
   // 16 targets) goes to the small-search tier, four searches per wave (k_ntask).
-  static const int route_g = getenv("OTR_ROUTE_G") ? atoi(getenv("OTR_ROUTE_G")) : 2;  // A/B knob
-  float est_k = 0.f, est_v[OTR_MODES];
-  uint32_t est_tier_keys[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-  int n_est_tiers = 0;
+  static const int route_g_env = getenv("OTR_ROUTE_G") ? atoi(getenv("OTR_ROUTE_G")) : 2;  // A/B knob
+  route_g = route_g_env;
   {
     static const double est_scale = getenv("OTR_EST_K") ? atof(getenv("OTR_EST_K")) : 1.0;
     const double mlat = g.grid_min_lat + 0.5 * g.grid_rows * g.grid_cell_deg;
@@ -1004,60 +1073,51 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
       const double kph = mp.m[m].speed_kph > 0.0 && mp.m[m].speed_kph < 50.0 ? mp.m[m].speed_kph : 50.0;
       est_v[m] = (float)(kph / 3.6);
     }
-    static const std::vector<int> tl = route_tiers();
+    const std::vector<int>& tl = route_tiers();
     n_est_tiers = (int)std::min<size_t>(tl.size(), 8);
     for (int t = 0; t < n_est_tiers; ++t) est_tier_keys[t] = (uint32_t)((tl[t] / 10) * 7 / 8);
   }
   static const double small_keys = getenv("OTR_SMALL_KEYS") ? atof(getenv("OTR_SMALL_KEYS")) : kSmallKeys;  // A/B knob
-  static const double tiny_keys = getenv("OTR_TINY_KEYS") ? atof(getenv("OTR_TINY_KEYS")) : kTinyKeys;  // A/B knob
+  static const double tiny_keys_env = getenv("OTR_TINY_KEYS") ? atof(getenv("OTR_TINY_KEYS")) : kTinyKeys;  // A/B knob
+  tiny_keys = tiny_keys_env;
   const bool small_tier = route_g == 2 && k32 && small_keys > 0.0 && est_k > 0.f;
   const bool tiny_tier = small_tier && tiny_keys > 0.0;
   int64_t* ntask4 = small_tier ? need<int64_t>(S_NTASK4, S) : nullptr;
   int64_t* task4_off = small_tier ? need<int64_t>(S_TASK4_OFF, S + 1) : nullptr;
   int64_t* ntask8 = tiny_tier ? need<int64_t>(S_NTASK8, S) : nullptr;
   int64_t* task8_off = tiny_tier ? need<int64_t>(S_TASK8_OFF, S + 1) : nullptr;
-  if ((small_tier && (!ntask4 || !task4_off)) || (tiny_tier && (!ntask8 || !task8_off))) {
-    if (err) *err = "device allocation failed (task map)";
-    return OTR_DEVICE_ERROR;
-  }
   // the step's task count: the distinct roots (k_prep) of the previous state's candidates
   if (S > 0) {
-    SmallArgs sa{};
-    sa.ntask4 = ntask4;
-    sa.ntask8 = ntask8;
-    sa.tiny_keys = (float)tiny_keys;
-    sa.bound = sb.bound;
-    sa.bt = sb.bt;
-    sa.forced = sb.forced;
-    sa.cand_count = cb.count;
-    sa.state_trace = state_trace;
-    sa.mode = b.mode;
-    sa.turn_modes = turn_modes;
-    sa.est_k = est_k;
-    for (int m = 0; m < OTR_MODES; ++m) sa.est_v[m] = est_v[m];
-    sa.small_keys = (float)small_keys;
-    k_ntask<<<grid_for(S, 256), 256, 0, stream>>>(S, sb.prev, pr.nroot, sb.ntask, sa);
+    SmallArgs sm{};
+    sm.ntask4 = ntask4;
+    sm.ntask8 = ntask8;
+    sm.tiny_keys = (float)tiny_keys;
+    sm.bound = sb.bound;
+    sm.bt = sb.bt;
+    sm.forced = sb.forced;
+    sm.cand_count = cb.count;
+    sm.state_trace = state_trace;
+    sm.mode = b.mode;
+    sm.turn_modes = turn_modes;
+    sm.est_k = est_k;
+    for (int m = 0; m < OTR_MODES; ++m) sm.est_v[m] = est_v[m];
+    sm.small_keys = (float)small_keys;
+    k_ntask<<<grid_for(S, 256), 256, 0, stream>>>(S, sb.prev, pr.nroot, sb.ntask, sm);
   }
   if ((rc = scan(sb.ntask, task_off, S))) return rc;
   if (small_tier && (rc = scan(ntask4, task4_off, S))) return rc;
   if (tiny_tier && (rc = scan(ntask8, task8_off, S))) return rc;
   if ((rc = scan(sb.ntrans, trans_off, S))) return rc;
-  // NT: every task; [0, NT8) the tiny tier's, [NT8, NT8 + NT4) the small tier's
-  int64_t NT = 0, NTR = 0, NT4 = 0, NT8 = 0;
   HIPCHK(hipMemcpyAsync(&NT, task_off + S, 8, hipMemcpyDeviceToHost, stream));
   if (small_tier) HIPCHK(hipMemcpyAsync(&NT4, task4_off + S, 8, hipMemcpyDeviceToHost, stream));
   if (tiny_tier) HIPCHK(hipMemcpyAsync(&NT8, task8_off + S, 8, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipMemcpyAsync(&NTR, trans_off + S, 8, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
   NT += NT4 + NT8;
-  int32_t* task_ovf = need<int32_t>(S_TASK_OVF, NT);
-  uint32_t* trans = need<uint32_t>(S_TRANS, NTR);
-  uint32_t* trans_tc = need<uint32_t>(S_TRANS_TC, turn_modes ? NTR : 1);  // read for turn modes only
-  uint4* task_rec = need<uint4>(S_TASK_REC, 3 * (size_t)std::max<int64_t>(NT, 1));
-  if (!task_ovf || !trans || !trans_tc || !task_rec) {
-    if (err) *err = "device allocation failed (transitions)";
-    return OTR_DEVICE_ERROR;
-  }
+  task_ovf = need<int32_t>(S_TASK_OVF, NT);
+  trans = need<uint32_t>(S_TRANS, NTR);
+  trans_tc = need<uint32_t>(S_TRANS_TC, turn_modes ? NTR : 1);  // read for turn modes only
+  task_rec = need<uint4>(S_TASK_REC, 3 * (size_t)std::max<int64_t>(NT, 1));
   if (S > 0) {  // tasks and their records (K2 + K2c)
     TaskArgs ta{};
     ta.n_states = S;
@@ -1094,13 +1154,126 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
     else k_tasks<1><<<(unsigned)grid_per_state_waves(S, 1).blocks, 256, 0, stream>>>(ta);
   }
   te(OTR_STAGE_LINK);
+  return OTR_OK;
+}
+
+// general (global-memory) search slabs: allocated on first use, cleared once
+int Batch::slabs(int tier, GSlabs* out) {
+  GSlab& sl = mat.gslab[tier];
+  const uint32_t cap = (uint32_t)kRouteTiers[SLOT_GLOBAL + tier].cap;
+  const uint32_t n = tier == 0 ? 1024u : 8u;
+  if (!sl.key) {
+    // all five arrays or none: a partial set is freed and the batch fails with
+    // OTR_DEVICE_ERROR (a later batch never sees a half-allocated slab)
+    const size_t c = (size_t)cap * n;
+    void* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t bytes[5] = {4 * c, 8 * c, 4 * c, 8 * c, 4 * c};
+    bool good = true;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      good = true;
+      for (int q = 0; q < 5 && good; ++q) good = hipMalloc(&p[q], bytes[q]) == hipSuccess;
+      if (good) break;
+      (void)hipGetLastError();
+      for (void*& q : p)
+        if (q) (void)hipFree(q), q = nullptr;
+      if (attempt > 0 || !mat.release_optional()) break;  // (the optional workspace gone: once more)
+    }
+    if (good)
+      good = hipMemsetAsync(p[0], 0xFF, 4 * c, stream) == hipSuccess &&
+             hipMemsetAsync(p[1], 0xFF, 8 * c, stream) == hipSuccess &&
+             hipMemsetAsync(p[2], 0, 4 * c, stream) == hipSuccess;
+    if (!good) {
+      (void)hipGetLastError();
+      for (void* q : p)
+        if (q) (void)hipFree(q);
+      throw DeviceOom{S_NUM + tier, 28 * c};  // (the global-search slabs of this tier)
+    }
+    sl.key = (uint32_t*)p[0];
+    sl.lab = (unsigned long long*)p[1];
+    sl.qmark = (uint32_t*)p[2];
+    sl.fr = (uint32_t*)p[3];
+    sl.touched = (uint32_t*)p[4];
+  }
+  out->key = sl.key;
+  out->lab = sl.lab;
+  out->qmark = sl.qmark;
+  out->fr = sl.fr;
+  out->touched = sl.touched;
+  out->cap = cap;
+  out->n = n;
+  return OTR_OK;
+}
+
+// the LDS route kernels: with the work counters (CNT) only when counting was asked for
+template <int CAP, int G, bool LIST>
+void Batch::launch_route(unsigned grid, const RouteArgs& args, unsigned long long* ctr_bank) {
+  if (ctr_bank) k_route<CAP, G, LIST, false, true><<<grid, 64, 0, stream>>>(g, args, ctr_bank);
+  else k_route<CAP, G, LIST, false, false><<<grid, 64, 0, stream>>>(g, args, nullptr);
+}
+
+// One of the first tiers (tiny, small, two-search): tasks [task_base, n_tasks) in `units` of
+// g searches, one unit per block, in launches of at most 2^25 blocks: a dispatch's grid size
+// counts work-items in 32 bits (178M tasks at 12.5M probes would wrap).
+// (a block per unit: a persistent grid over per-XCD queues was slower, C5 26.5 -> 35.6 ms,
+// DESIGN.md §6)
+void Batch::first_tier(int slot, int cap, int g_, int64_t n_tasks, int64_t task_base, int64_t units) {
+  constexpr int64_t kMaxUnits = 1ll << 25;
+  unsigned long long* ctr_bank = tier_work(slot);
+  // (the two-search tier's time is the route stage's less the other two tiers')
+  if (slot != SLOT_FIRST) tier_begin(slot);
+  for (int64_t base = 0; base < units; base += kMaxUnits) {
+    RouteArgs rf = ra;
+    rf.n_tasks = n_tasks;
+    rf.task_base = task_base;
+    rf.unit_base = base;
+    const int64_t u = std::min<int64_t>(kMaxUnits, units - base);
+    const unsigned grid = (unsigned)(8 * ((u + 7) / 8));
+    if (slot == SLOT_TINY) launch_route<OTR_CAP8, 8, false>(grid, rf, ctr_bank);
+    else if (slot == SLOT_SMALL) launch_route<OTR_CAP4, 4, false>(grid, rf, ctr_bank);
+    else if (g_ == 2) launch_route<OTR_CAP1, 2, false>(grid, rf, ctr_bank);
+    else launch_route<256, 1, false>(grid, rf, ctr_bank);
+  }
+  if (slot != SLOT_FIRST) tier_end(slot);
+  out->route_tier_code[slot] = route_tier_code(slot, cap, g_);
+}
+
+// a node retry tier's kernel by its code (otr_tiers.h kRetryShapes: every code OTR_TIERS
+// accepts has its kernel here)
+template <int I = 0, class F>
+static bool with_retry_shape(int code, F&& f) {
+  if constexpr (I < kRetryShapeN) {
+    if (code == kRetryShapes[I].code()) {
+      f(std::integral_constant<int, I>{});
+      return true;
+    }
+    return with_retry_shape<I + 1>(code, f);
+  } else {
+    return false;
+  }
+}
+
+int Batch::retry_tier(int code, const RouteArgs& rb, unsigned long long* ctr_bank) {
+  const bool known = with_retry_shape(code, [&](auto i) {
+    constexpr int cap = kRetryShapes[decltype(i)::value].cap, gw = kRetryShapes[decltype(i)::value].g;
+    // persistent grids over per-XCD queues: about twice a tier's resident waves (256 CUs x
+    // 4 SIMDs x 8 waves for the small tables, fewer for the big ones, whose LDS admits
+    // fewer); a block that finds its queue drained exits at once
+    launch_route<cap, gw, true>(pgrid(cap <= 512 ? 16384u : 16384u * 512u / cap, (NT + gw - 1) / gw), rb, ctr_bank);
+  });
+  if (!known) {
+    if (err) *err = "no route kernel for retry tier " + std::to_string(code);
+    return OTR_DEVICE_ERROR;
+  }
+  return OTR_OK;
+}
+
+// ---- K3/K4: routing + transition costs, the first tiers
+int Batch::route_first() {
   // turn cost tables of this batch's parameters (oracle orc_turn_table)
-  int32_t* d_turn = need<int32_t>(S_TURN, 181 * OTR_MODES);
-  h_turn.resize(181 * OTR_MODES);
-  for (int m = 0; m < OTR_MODES; ++m) turn_table(mp.m[m].turn_penalty_factor, h_turn.data() + 181 * m);
-  HIPCHK(hipMemcpyAsync(d_turn, h_turn.data(), 4 * 181 * OTR_MODES, hipMemcpyHostToDevice, stream));
-  // ---- K3/K4: routing + transition costs
-  RouteArgs ra{};
+  d_turn = need<int32_t>(S_TURN, 181 * OTR_MODES);
+  mat.h_turn.resize(181 * OTR_MODES);
+  for (int m = 0; m < OTR_MODES; ++m) turn_table(mp.m[m].turn_penalty_factor, mat.h_turn.data() + 181 * m);
+  HIPCHK(hipMemcpyAsync(d_turn, mat.h_turn.data(), 4 * 181 * OTR_MODES, hipMemcpyHostToDevice, stream));
   ra.task_list = nullptr;
   ra.n_tasks = NT;
   ra.prev = sb.prev;
@@ -1128,70 +1301,12 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
   for (int m = 0; m < OTR_MODES; ++m) ra.est_v[m] = est_v[m];
   ra.n_tiers = n_est_tiers;
   for (int t = 0; t < n_est_tiers; ++t) ra.tier_keys[t] = est_tier_keys[t];
-  // device-side counters of the retry lists: [0..7] route tiers, [8] general tier 1,
-  // [9] general tier 2, [10] route tasks left unrouted, [11] steps, [12..15] path tiers,
-  // [16] path general 1, [17] path general 2, [18] paths left, [19] general overflow
-  // count, [20] cap flag, [21] exact node path tier, [23] first edge-state tier, [24] tasks
-  // the first route tier
-  // flagged, [25..26] edge-state route tiers, [27..28] edge-state path tiers, [29] exact
-  // edge route tier, [30] exact node route tier, [31] exact edge path tier, [32..96) path
-  // bump cursors
-  unsigned long long* cnt = need<unsigned long long>(S_MISC, 32 + kShards);
-  HIPCHK(hipMemsetAsync(cnt, 0, 8 * (32 + kShards), stream));
-  int64_t* list = need<int64_t>(S_LIST, std::max<int64_t>(NT, S));
-  int64_t* fail_tasks = need<int64_t>(S_GFLAG, std::max<int64_t>(NT, 1));
-  int64_t* flagged = need<int64_t>(S_FLAGGED, std::max<int64_t>(NT, 1));
-  if (!list || !fail_tasks || !flagged) {
-    if (err) *err = "device allocation failed (retry lists)";
-    return OTR_DEVICE_ERROR;
-  }
-  // general (global-memory) search slabs: allocated on first use, cleared once
-  auto slabs = [&](int tier, GSlabs* out) -> int {
-    GSlab& sl = gslab[tier];
-    const uint32_t cap = tier == 0 ? (1u << 15) : (1u << 20);
-    const uint32_t n = tier == 0 ? 1024u : 8u;
-    if (!sl.key) {
-      // all five arrays or none: a partial set is freed and the batch fails with
-      // OTR_DEVICE_ERROR (a later batch never sees a half-allocated slab)
-      const size_t c = (size_t)cap * n;
-      void* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-      const size_t bytes[5] = {4 * c, 8 * c, 4 * c, 8 * c, 4 * c};
-      bool good = true;
-      for (int attempt = 0; attempt < 2; ++attempt) {
-        good = true;
-        for (int q = 0; q < 5 && good; ++q) good = hipMalloc(&p[q], bytes[q]) == hipSuccess;
-        if (good) break;
-        (void)hipGetLastError();
-        for (void*& q : p)
-          if (q) (void)hipFree(q), q = nullptr;
-        if (attempt > 0 || !release_optional()) break;  // (the optional workspace gone: once more)
-      }
-      if (good)
-        good = hipMemsetAsync(p[0], 0xFF, 4 * c, stream) == hipSuccess &&
-               hipMemsetAsync(p[1], 0xFF, 8 * c, stream) == hipSuccess &&
-               hipMemsetAsync(p[2], 0, 4 * c, stream) == hipSuccess;
-      if (!good) {
-        (void)hipGetLastError();
-        for (void* q : p)
-          if (q) (void)hipFree(q);
-        throw DeviceOom{S_NUM + tier, 28 * c};  // (the global-search slabs of this tier)
-      }
-      sl.key = (uint32_t*)p[0];
-      sl.lab = (unsigned long long*)p[1];
-      sl.qmark = (uint32_t*)p[2];
-      sl.fr = (uint32_t*)p[3];
-      sl.touched = (uint32_t*)p[4];
-    }
-    out->key = sl.key;
-    out->lab = sl.lab;
-    out->qmark = sl.qmark;
-    out->fr = sl.fr;
-    out->touched = sl.touched;
-    out->cap = cap;
-    out->n = n;
-    return OTR_OK;
-  };
-  GenArgs ga{};
+  // device-side counters of the retry lists (otr_tiers.h CntWord), then the path bump cursors
+  cnt = need<unsigned long long>(S_MISC, C_CURSORS + kShards);
+  HIPCHK(hipMemsetAsync(cnt, 0, 8 * (C_CURSORS + kShards), stream));
+  list = need<int64_t>(S_LIST, std::max<int64_t>(NT, S));
+  fail_tasks = need<int64_t>(S_GFLAG, std::max<int64_t>(NT, 1));
+  flagged = need<int64_t>(S_FLAGGED, std::max<int64_t>(NT, 1));
   ga.prev = sb.prev;
   ga.g = sb.g;
   ga.bt = sb.bt;
@@ -1210,285 +1325,248 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
   ga.trans = trans;
   ga.trans_tc = trans_tc;
   ga.counters = d_counters;
-  ga.n_overflow = cnt + 19;
-  if (NT > 0) {
-    // two searches per wave (CAP 160 tables); wider steps and overflows retry below
-    // the LDS tiers count their work only when asked (OTR_BATCH_ROUTE_WORK): the end-of-
-    // wave counter atomics cost ~7% of the first tier (tools/ab_libs.sh)
-    unsigned long long* rwork = (in->flags & OTR_BATCH_ROUTE_WORK) ? d_counters : nullptr;
-    // the LDS route kernels: with the work counters (CNT) only when counting was asked for
-#define OTR_ROUTE_LAUNCH(C, G_, LIST_, GRID, ARGS, CTR)                                       \
-  do {                                                                                      \
-    if (CTR) k_route<C, G_, LIST_, false, true><<<GRID, 64, 0, stream>>>(g, ARGS, CTR);      \
-    else k_route<C, G_, LIST_, false, false><<<GRID, 64, 0, stream>>>(g, ARGS, nullptr);     \
-  } while (0)
-    // turn-mode (edge-state) tasks belong to the edge-state tiers below: the node
-    // tiers pass them on unflagged, and when every mode has turn costs (the deployed
-    // configuration) no node task exists and the first node tier is not launched at all
-    const bool turns = turn_modes != 0u;
+  ga.n_overflow = cnt + C_GEN_OVERFLOW;
+  if (NT == 0) return OTR_OK;
+  // the LDS tiers count their work only when asked (OTR_BATCH_ROUTE_WORK): the end-of-
+  // wave counter atomics cost ~7% of the first tier (tools/ab_libs.sh)
+  rwork = (in->flags & OTR_BATCH_ROUTE_WORK) ? d_counters : nullptr;
+  // turn-mode (edge-state) tasks belong to the edge-state tiers below: the node
+  // tiers pass them on unflagged, and when every mode has turn costs (the deployed
+  // configuration) no node task exists and the first node tier is not launched at all
+  turns = turn_modes != 0u;
 #ifdef OTR_FORCE_GENERAL
-    const bool node_tasks = true;  // (test build: the first tier flags every task for k_general)
+  node_tasks = true;  // (test build: the first tier flags every task for k_general)
 #else
-    const bool node_tasks = turn_modes != (1u << OTR_MODES) - 1u;
+  node_tasks = turn_modes != (1u << OTR_MODES) - 1u;
 #endif
 #ifdef OTR_FORCE_RETRY
-    {  // test build: OTR_FORCE_EDGE bits force the edge-state tiers to fail (tests/test_gpu_tiers.py)
-      const char* fe = getenv("OTR_FORCE_EDGE");
-      ra.force_edge = fe ? atoi(fe) : 0;
-    }
-#endif
-    // the list tiers' work queues (XcdQueue): 8 counters per launch, 128 B apart
-    constexpr int kQueueWords = 16 * 8;
-    unsigned long long* queues = need<unsigned long long>(S_QUEUE, 16 * kQueueWords);
-    HIPCHK(hipMemsetAsync(queues, 0, 8 * 16 * kQueueWords, stream));
-    // retry-tier dumps (search_run NDump, otr_edge1.h): per task, the dump slot its search
-    // left for the next tier; every tier that fails a task writes it (-1: restart), so the
-    // first node tier, which flags every task a retry tier will see, initialises it
-    static const bool nresume = !getenv("OTR_NRESUME") || atoi(getenv("OTR_NRESUME")) != 0;  // A/B knob
-    static const bool eresume = !getenv("OTR_E1RESUME") || atoi(getenv("OTR_E1RESUME")) != 0;  // A/B knob
-    int32_t* task_dump = nullptr;  // (optional: without it outgrown searches restart, same results)
-    if ((nresume && node_tasks) || (eresume && turns)) task_dump = want<int32_t>(S_TASK_DUMP, NT);
-    opt_busy = true;  // the optional workspace stays until the route stage's kernels are queued
-    ra.task_dump = task_dump;
-    tb(OTR_STAGE_ROUTE);
-    if (node_tasks) {
-      // one unit (G searches) per block, in launches of at most 2^25 blocks: a dispatch's
-      // grid size counts work-items in 32 bits (178M tasks at 12.5M probes would wrap).
-      // The small tier (four searches per wave, tasks [0, NT4)) first, then the two-search
-      // tier over the rest
-      constexpr int64_t kMaxUnits = 1ll << 25;
-      // the tiny tier (eight searches per wave, tasks [0, NT8)) only in batches that are
-      // mostly tiny steps (C5); elsewhere its few tasks join the small tier's range (they are
-      // adjacent), which saves a launch (C1: 18k tiny tasks cost 2 %)
-      const bool tiny_run = NT8 > 0 && (2 * NT8 >= NT || tiny_keys >= 1e8);  // (1e8: tests force it)
-      const int64_t small_lo = tiny_run ? NT8 : 0;
-      if (tiny_run) {
-        unsigned long long* rc8 = rwork ? d_counters + 13 * bank : nullptr;
-        if (timing) (void)hipEventRecord(ev[24 + 2 * 13], stream);
-        const int64_t units = (NT8 + 7) / 8;
-        for (int64_t base = 0; base < units; base += kMaxUnits) {
-          RouteArgs rf = ra;
-          rf.n_tasks = NT8;
-          rf.unit_base = base;
-          const int64_t u = std::min<int64_t>(kMaxUnits, units - base);
-          OTR_ROUTE_LAUNCH(OTR_CAP8, 8, false, (unsigned)(8 * ((u + 7) / 8)), rf, rc8);
-        }
-        if (timing) (void)hipEventRecord(ev[24 + 2 * 13 + 1], stream);
-        out->route_tier_code[13] = OTR_CAP8 * 10 + 8;
-      }
-      if (NT8 + NT4 - small_lo > 0) {
-        unsigned long long* rc4 = rwork ? d_counters + 12 * bank : nullptr;
-        if (timing) (void)hipEventRecord(ev[24 + 2 * 12], stream);
-        const int64_t units = (NT8 + NT4 - small_lo + 3) / 4;
-        // (a block per unit: a persistent grid over per-XCD queues was slower, C5 26.5 ->
-        // 35.6 ms)
-        for (int64_t base = 0; base < units; base += kMaxUnits) {
-          RouteArgs rf = ra;
-          rf.n_tasks = NT8 + NT4;
-          rf.task_base = small_lo;
-          rf.unit_base = base;
-          const int64_t u = std::min<int64_t>(kMaxUnits, units - base);
-          OTR_ROUTE_LAUNCH(OTR_CAP4, 4, false, (unsigned)(8 * ((u + 7) / 8)), rf, rc4);
-        }
-        if (timing) (void)hipEventRecord(ev[24 + 2 * 12 + 1], stream);
-        out->route_tier_code[12] = OTR_CAP4 * 10 + 4;
-      }
-      const int64_t units = route_g == 2 ? (NT - NT8 - NT4 + 1) / 2 : NT;
-      for (int64_t base = 0; base < units; base += kMaxUnits) {
-        RouteArgs rf = ra;
-        rf.unit_base = base;
-        rf.task_base = NT8 + NT4;
-        const int64_t u = std::min<int64_t>(kMaxUnits, units - base);
-        const unsigned grid = (unsigned)(8 * ((u + 7) / 8));
-        if (route_g == 2) OTR_ROUTE_LAUNCH(OTR_CAP1, 2, false, grid, rf, rwork);
-        else OTR_ROUTE_LAUNCH(256, 1, false, grid, rf, rwork);
-      }
-      out->route_tier_code[0] = route_g == 2 ? OTR_CAP1 * 10 + 2 : 2561;
-    }
-    te(OTR_STAGE_ROUTE);
-    // overflow retries with larger LDS tables (same results, fewer resident waves): each
-    // tier takes its list on the device and runs a fixed grid over it — no host round
-    // trip between tiers.  Tier t takes the previous tier's overflows (flag 1) and the
-    // first-tier tasks whose size estimate starts them in a tier <= t (flags 16 + u, u <= t);
-    // OTR_TIERS (A/B knob) lists the retry kernels.
-    tb(OTR_STAGE_ROUTE_BIG);
-    static const std::vector<int> tiers = route_tiers();
-    const int ntier = (int)tiers.size();
-    // persistent grids over per-XCD queues: about twice a tier's resident waves (256 CUs x
-    // 4 SIMDs x 8 waves for the small tables, fewer for the big ones, whose LDS admits
-    // fewer); a block that finds its queue drained exits at once
-    // the first tier's flagged tasks, once; every later collect scans only them
-    k_collect_flagged<<<grid_for(NT, 1024), 1024, 0, stream>>>(NT, task_ovf, flagged, cnt + 24);
-    constexpr unsigned kCollectGrid = 512;
-    // node dump slots: tier t writes buffer t % 2 and tier t + 1 resumes from it; slots for a
-    // quarter of the tasks, at most OTR_NDUMP_GB (4) GB per buffer (C4: 4 % of the 1024-slot
-    // searches outgrow it, 10 KB each); beyond them, or without the memory, searches restart
-    unsigned long long* ndump[2] = {nullptr, nullptr};
-    uint32_t nslots[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    // (tables compiled with the resume / dump code, otr_kernels.h OTR_ND_IN_MIN / OTR_ND_OUT_MIN)
-    auto nd_in = [&](int t) { return t > 0 && t < ntier && tiers[t] / 10 >= OTR_ND_IN_MIN; };
-    auto nd_out = [&](int t) { return t + 1 < ntier && tiers[t] / 10 >= OTR_ND_OUT_MIN && nd_in(t + 1); };
-    if (nresume && node_tasks && task_dump && ntier > 1) {
-      static const double gb = getenv("OTR_NDUMP_GB") ? atof(getenv("OTR_NDUMP_GB")) : 4.0;
-      const int64_t cap_bytes = (int64_t)(gb * (double)(1ll << 30));
-      size_t words[2] = {0, 0};
-      for (int t = 0; t + 1 < ntier && t < 8; ++t) {
-        if (!nd_out(t)) continue;
-        const uint32_t w = nd_words(tiers[t] / 10);
-        nslots[t] = (uint32_t)std::min<int64_t>(std::max<int64_t>(NT / 4, 1024), cap_bytes / (8 * (int64_t)w));
-        words[t & 1] = std::max<size_t>(words[t & 1], (size_t)nslots[t] * w);
-      }
-      for (int q = 0; q < 2; ++q)
-        if (words[q]) ndump[q] = want<unsigned long long>(q == 0 ? S_NDUMP0 : S_NDUMP1, words[q]);
-      if ((words[0] && !ndump[0]) || (words[1] && !ndump[1])) ndump[0] = ndump[1] = nullptr;
-    }
-    for (int tier = 0; tier < (node_tasks ? ntier : 0); ++tier) {  // (no node task: no node tier)
-      unsigned long long* c = cnt + tier;
-      k_collect_tier_from<<<kCollectGrid, 1024, 0, stream>>>(flagged, cnt + 24, task_ovf,
-                                                            0x2u | (((2u << tier) - 1u) << 16), list + 0, c);
-      RouteArgs rb = ra;
-      rb.task_list = list;
-      rb.list_count = c;
-      rb.queue = queues + tier * kQueueWords;
-      const bool din = nd_in(tier) && nd_out(tier - 1) && ndump[(tier + 1) & 1] != nullptr;
-      const bool dout = nd_out(tier) && ndump[tier & 1] != nullptr;
-      rb.dump_in = din ? ndump[(tier + 1) & 1] : nullptr;
-      rb.dump_in_words = din ? nd_words(tiers[tier - 1] / 10) : 0u;
-      rb.dump_out = dout ? ndump[tier & 1] : nullptr;
-      rb.dump_ctr = queues + 15 * kQueueWords + 16 * tier;  // (queue 15: zeroed above; one line per tier)
-      rb.dump_out_words = dout ? nd_words(tiers[tier] / 10) : 0u;
-      rb.dump_out_slots = dout ? nslots[tier] : 0u;
-      unsigned long long* rcn = rwork ? d_counters + (2 + tier) * bank : nullptr;
-      out->route_tier_code[1 + tier] = tiers[tier];
-      if (timing) (void)hipEventRecord(ev[24 + 2 * (1 + tier)], stream);
-#define OTR_TIER(C, G_) \
-  OTR_ROUTE_LAUNCH(C, G_, true, pgrid((C) <= 512 ? 16384u : 16384u * 512u / (C), (NT + (G_) - 1) / (G_)), rb, rcn)
-      switch (tiers[tier]) {
-        case 2561: OTR_TIER(256, 1); break;
-        case 5121: OTR_TIER(512, 1); break;
-        case 7681: OTR_TIER(768, 1); break;
-        case 10241: OTR_TIER(1024, 1); break;
-        case 20481: OTR_TIER(2048, 1); break;
-        case 3842: OTR_TIER(384, 2); break;
-        case 4482: OTR_TIER(448, 2); break;
-        case 5122: OTR_TIER(512, 2); break;
-        default: OTR_TIER(4096, 1); break;
-      }
-#undef OTR_TIER
-      if (timing) (void)hipEventRecord(ev[24 + 2 * (1 + tier) + 1], stream);
-    }
-#ifndef OTR_FORCE_GENERAL  // (test build: every search in k_general)
-    // the node-mode tasks whose (length << sh | time) words need more than 32 bits
-    // (flag 3: long gaps between states) run in an LDS table of 64-bit words (same labels,
-    // DESIGN.md §3.5); what outgrows it is flagged 3 again
-    {
-      unsigned long long* c = cnt + 7;
-      k_collect_tier_from<<<kCollectGrid, 1024, 0, stream>>>(flagged, cnt + 24, task_ovf, 0x8u, list, c);
-      RouteArgs rb = ra;
-      rb.task_list = list;
-      rb.list_count = c;
-      rb.queue = queues + 8 * kQueueWords;
-      out->route_tier_code[8] = 900000 + 2048;
-      if (timing) (void)hipEventRecord(ev[24 + 2 * 8], stream);
-      if (rwork) k_route<2048, 1, true, true, true><<<pgrid(4096, NT), 64, 0, stream>>>(g, rb, d_counters + 7 * bank);
-      else k_route<2048, 1, true, true, false><<<pgrid(4096, NT), 64, 0, stream>>>(g, rb, nullptr);
-      if (timing) (void)hipEventRecord(ev[24 + 2 * 8 + 1], stream);
-    }
-#endif
-    // edge-state tiers (turn-cost modes, otr_edge1.h): OTR_E1CAP (360) states (flag 5, slot
-    // 10), 512 (flag 6, slot 9), 1024 (flag 7, slot 11); what outgrows those (flag 3) goes on below
-    if (turns) {
-      // dump slots of the first two edge tiers: a search they outgrow between two rounds
-      // resumes in the next table (otr_edge1.h e1_dump / e1_restore) instead of starting
-      // over; slots for 1/16 of the tasks (C2, deployed: 4.4 % outgrow the first table),
-      // at most 4 GB / 1 GB — searches beyond them, or when the memory is not there,
-      // restart in the next table (same results)
-      unsigned long long* dump[2] = {nullptr, nullptr};
-      uint32_t dslots[2] = {0u, 0u};
-      const uint32_t dwords[2] = {e1_dump_words(OTR_E1CAP), e1_dump_words(512)};
-      if (eresume && task_dump) {
-        const int64_t cap_bytes[2] = {4ll << 30, 1ll << 30};
-        const int64_t wanted[2] = {std::max<int64_t>(NT / 16, 4096), std::max<int64_t>(NT / 64, 1024)};
-        for (int q = 0; q < 2; ++q) {  // (no dumps beyond what was allocated: those searches restart)
-          const int64_t n = std::min<int64_t>(wanted[q], cap_bytes[q] / (8 * (int64_t)dwords[q]));
-          dump[q] = want<unsigned long long>(q == 0 ? S_E1DUMP0 : S_E1DUMP1, (size_t)n * dwords[q]);
-          dslots[q] = dump[q] ? (uint32_t)n : 0u;
-        }
-        if (!dump[0]) dump[1] = nullptr, dslots[1] = 0u;
-      }
-      for (int et = 0; et < 3; ++et) {
-        const int slot = et == 0 ? 10 : (et == 1 ? 9 : 11);
-        out->route_tier_code[slot] = 6000000 + (et == 0 ? OTR_E1CAP : (et == 1 ? 512 : 1024)) * 100 + 32;
-        unsigned long long* c = cnt + (et == 0 ? 23 : 24 + et);
-        k_collect_tier_from<<<kCollectGrid, 1024, 0, stream>>>(flagged, cnt + 24, task_ovf, 0x20u << et, list, c);
-        RouteArgs rb = ra;
-        rb.task_list = list;
-        // the first edge tier's list in spatial order (k_sort_*: one band of the map per XCD)
-        static const bool esort = !getenv("OTR_SORT") || atoi(getenv("OTR_SORT")) != 0;  // A/B knob
-        int64_t* list2 = nullptr;
-        uint32_t* hist = nullptr;
-        if (et == 0 && esort && NT >= 65536) {
-          list2 = want<int64_t>(S_SORT_LIST, NT);  // (no memory for the copy: the list stays in task order)
-          hist = list2 ? want<uint32_t>(S_SORT_HIST, kSortBuckets) : nullptr;
-        }
-        if (list2 && hist) {
-          int bits = 0;
-          while (bits < 32 && (g.n_edges >> bits) > 0u) ++bits;
-          const int shift = bits > 12 ? bits - 12 : 0;
-          HIPCHK(hipMemsetAsync(hist, 0, 4 * kSortBuckets, stream));
-          k_sort_hist<<<grid_for(NT, 1024), 1024, 0, stream>>>(list, c, task_rec, shift, hist);
-          k_sort_scan<<<1, 1024, 0, stream>>>(hist);
-          k_sort_place<<<grid_for(NT, 1024), 1024, 0, stream>>>(list, c, task_rec, shift, hist, list2);
-          rb.task_list = list2;
-        }
-        rb.list_count = c;
-        rb.queue = queues + (9 + et) * kQueueWords;
-        rb.dump_in = et > 0 ? dump[et - 1] : nullptr;
-        rb.dump_in_words = et > 0 ? dwords[et - 1] : 0u;
-        rb.dump_in_cap = et == 1 ? OTR_E1CAP : 512;
-        rb.dump_out = et < 2 ? dump[et] : nullptr;
-        rb.dump_ctr = queues + (13 + et) * kQueueWords;  // (queues 13, 14: zeroed above)
-        rb.dump_out_words = et < 2 ? dwords[et] : 0u;
-        rb.dump_out_slots = et < 2 ? dslots[et] : 0u;
-        rb.task_dump = task_dump;
-        unsigned long long* rcn = rwork ? d_counters + (et == 0 ? 10 : (et == 1 ? 1 : 11)) * bank : nullptr;
-        if (timing) (void)hipEventRecord(ev[24 + 2 * slot], stream);
-        // persistent grids of at least every resident wave (16 per CU at 384 states, 13 at
-        // 512, 6 at 1024) claiming tasks from per-XCD queues; steps with more than 32
-        // targets (modes keeping > 32 candidates) pass the lean tiers (their TG = 32) on to
-        // k_general
-        if (et == 0) k_route_e1<OTR_E1CAP><<<pgrid(8192, NT), 64, 0, stream>>>(g, rb, rcn);
-        else if (et == 1) k_route_e1<512><<<pgrid(4096, NT), 64, 0, stream>>>(g, rb, rcn);
-        else k_route_e1<1024><<<pgrid(2048, NT), 64, 0, stream>>>(g, rb, rcn);
-        if (timing) (void)hipEventRecord(ev[24 + 2 * slot + 1], stream);
-      }
-    }
-    opt_busy = false;  // (every user of the optional workspace is queued)
-    // everything left — tasks whose labels need 64 bits, overflows of the largest LDS
-    // tables (node and edge-state) — runs in the global-memory search: first on 32K-slot
-    // slabs, then what outgrew those on 1M-slot slabs
-    for (int gt = 0; gt < 2; ++gt) {
-      unsigned long long* c = cnt + 8 + gt;
-      k_collect_tier_from<<<kCollectGrid, 1024, 0, stream>>>(flagged, cnt + 24, task_ovf, gt == 0 ? 0x1Eu : 0x2u, list,
-                                                            c);
-      GSlabs gs2;
-      if ((rc = slabs(gt, &gs2))) return rc;
-      ga.mode = 0;
-      ga.list = list;
-      ga.list_count = c;
-      ga.flag = task_ovf;
-      ga.counters = d_counters + (8 + gt) * bank;
-      out->route_tier_code[6 + gt] = -1 - gt;
-      if (timing) (void)hipEventRecord(ev[24 + 2 * (6 + gt)], stream);
-      k_general<<<pgrid(gs2.n, NT), kGenThreads, 0, stream>>>(g, ga, gs2);
-      if (timing) (void)hipEventRecord(ev[24 + 2 * (6 + gt) + 1], stream);
-    }
-    // tasks still flagged (beyond a 1M-state slab): their traces get OTR_MATCH_ERROR
-    k_collect_tier_from<<<kCollectGrid, 1024, 0, stream>>>(flagged, cnt + 24, task_ovf, 0x1Eu, fail_tasks, cnt + 10);
-    te(OTR_STAGE_ROUTE_BIG);
+  {  // test build: OTR_FORCE_EDGE bits force the edge-state tiers to fail (tests/test_gpu_tiers.py)
+    const char* fe = getenv("OTR_FORCE_EDGE");
+    ra.force_edge = fe ? atoi(fe) : 0;
   }
-  // ---- K5: Viterbi
-  ViterbiArgs va{};
+#endif
+  // the list tiers' work queues (XcdQueue): 8 counters per launch, 128 B apart
+  queues = need<unsigned long long>(S_QUEUE, kQueues * kQueueWords);
+  HIPCHK(hipMemsetAsync(queues, 0, 8 * kQueues * kQueueWords, stream));
+  // retry-tier dumps (search_run NDump, otr_edge1.h): per task, the dump slot its search
+  // left for the next tier; every tier that fails a task writes it (-1: restart), so the
+  // first node tier, which flags every task a retry tier will see, initialises it
+  static const bool nresume_env = !getenv("OTR_NRESUME") || atoi(getenv("OTR_NRESUME")) != 0;  // A/B knob
+  static const bool eresume_env = !getenv("OTR_E1RESUME") || atoi(getenv("OTR_E1RESUME")) != 0;  // A/B knob
+  nresume = nresume_env;
+  eresume = eresume_env;
+  // (optional: without it outgrown searches restart, same results)
+  if ((nresume && node_tasks) || (eresume && turns)) task_dump = want<int32_t>(S_TASK_DUMP, NT);
+  mat.opt_busy = true;  // the optional workspace stays until the route stage's kernels are queued
+  ra.task_dump = task_dump;
+  tb(OTR_STAGE_ROUTE);
+  if (node_tasks) {
+    // The tiny tier (eight searches per wave, tasks [0, NT8)) first, only in batches that
+    // are mostly tiny steps (C5); elsewhere its few tasks join the small tier's range (they
+    // are adjacent), which saves a launch (C1: 18k tiny tasks cost 2 %).  Then the small
+    // tier (four searches per wave), then the two-search tier (CAP 160 tables) over the
+    // rest; wider steps and overflows retry in route_retry()
+    const bool tiny_run = NT8 > 0 && (2 * NT8 >= NT || tiny_keys >= 1e8);  // (1e8: tests force it)
+    const int64_t small_lo = tiny_run ? NT8 : 0;
+    if (tiny_run) first_tier(SLOT_TINY, OTR_CAP8, 8, NT8, 0, (NT8 + 7) / 8);
+    if (NT8 + NT4 - small_lo > 0)
+      first_tier(SLOT_SMALL, OTR_CAP4, 4, NT8 + NT4, small_lo, (NT8 + NT4 - small_lo + 3) / 4);
+    if (route_g == 2) first_tier(SLOT_FIRST, OTR_CAP1, 2, NT, NT8 + NT4, (NT - NT8 - NT4 + 1) / 2);
+    else first_tier(SLOT_FIRST, 256, 1, NT, NT8 + NT4, NT);
+  }
+  te(OTR_STAGE_ROUTE);
+  return OTR_OK;
+}
+
+// ---- the route retry tiers on LDS tables: the node retry tiers, then the 64-bit tier
+int Batch::route_retry() {
+  if (NT == 0) return OTR_OK;
+  int rc;
+  // overflow retries with larger LDS tables (same results, fewer resident waves): each
+  // tier takes its list on the device and runs a fixed grid over it — no host round
+  // trip between tiers.  Tier t takes the previous tier's overflows (flag 1) and the
+  // first-tier tasks whose size estimate starts them in a tier <= t (flags 16 + u, u <= t);
+  // OTR_TIERS (A/B knob) lists the retry kernels.
+  tb(OTR_STAGE_ROUTE_BIG);
+  const std::vector<int>& tiers = route_tiers();
+  const int ntier = (int)tiers.size();
+  // the first tier's flagged tasks, once; every later collect scans only them
+  k_collect_flagged<<<grid_for(NT, 1024), 1024, 0, stream>>>(NT, task_ovf, flagged, cnt + C_FLAGGED);
+  // node dump slots: tier t writes buffer t % 2 and tier t + 1 resumes from it; slots for a
+  // quarter of the tasks, at most OTR_NDUMP_GB (4) GB per buffer (C4: 4 % of the 1024-slot
+  // searches outgrow it, 10 KB each); beyond them, or without the memory, searches restart
+  unsigned long long* ndump[2] = {nullptr, nullptr};
+  uint32_t nslots[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  // (tables compiled with the resume / dump code, otr_kernels.h OTR_ND_IN_MIN / OTR_ND_OUT_MIN)
+  auto nd_in = [&](int t) { return t > 0 && t < ntier && tiers[t] / 10 >= OTR_ND_IN_MIN; };
+  auto nd_out = [&](int t) { return t + 1 < ntier && tiers[t] / 10 >= OTR_ND_OUT_MIN && nd_in(t + 1); };
+  if (nresume && node_tasks && task_dump && ntier > 1) {
+    static const double gb = getenv("OTR_NDUMP_GB") ? atof(getenv("OTR_NDUMP_GB")) : 4.0;
+    const int64_t cap_bytes = (int64_t)(gb * (double)(1ll << 30));
+    size_t words[2] = {0, 0};
+    for (int t = 0; t + 1 < ntier && t < 8; ++t) {
+      if (!nd_out(t)) continue;
+      const uint32_t w = nd_words(tiers[t] / 10);
+      nslots[t] = (uint32_t)std::min<int64_t>(std::max<int64_t>(NT / 4, 1024), cap_bytes / (8 * (int64_t)w));
+      words[t & 1] = std::max<size_t>(words[t & 1], (size_t)nslots[t] * w);
+    }
+    for (int q = 0; q < 2; ++q)
+      if (words[q]) ndump[q] = want<unsigned long long>(q == 0 ? S_NDUMP0 : S_NDUMP1, words[q]);
+    if ((words[0] && !ndump[0]) || (words[1] && !ndump[1])) ndump[0] = ndump[1] = nullptr;
+  }
+  for (int tier = 0; tier < (node_tasks ? ntier : 0); ++tier) {  // (no node task: no node tier)
+    const int slot = SLOT_NODE + tier;
+    unsigned long long* c = tier_list(slot);
+    k_collect_tier_from<<<kCollectGrid, 1024, 0, stream>>>(flagged, cnt + C_FLAGGED, task_ovf,
+                                                          0x2u | (((2u << tier) - 1u) << 16), list + 0, c);
+    RouteArgs rb = ra;
+    rb.task_list = list;
+    rb.list_count = c;
+    rb.queue = tier_queue(slot);
+    const bool din = nd_in(tier) && nd_out(tier - 1) && ndump[(tier + 1) & 1] != nullptr;
+    const bool dout = nd_out(tier) && ndump[tier & 1] != nullptr;
+    rb.dump_in = din ? ndump[(tier + 1) & 1] : nullptr;
+    rb.dump_in_words = din ? nd_words(tiers[tier - 1] / 10) : 0u;
+    rb.dump_out = dout ? ndump[tier & 1] : nullptr;
+    rb.dump_ctr = queues + dump_ctr_word(slot);  // (its queue was zeroed with the others; one line per tier)
+    rb.dump_out_words = dout ? nd_words(tiers[tier] / 10) : 0u;
+    rb.dump_out_slots = dout ? nslots[tier] : 0u;
+    out->route_tier_code[slot] = tiers[tier];
+    tier_begin(slot);
+    if ((rc = retry_tier(tiers[tier], rb, tier_work(slot)))) return rc;
+    tier_end(slot);
+  }
+#ifndef OTR_FORCE_GENERAL  // (test build: every search in k_general)
+  // the node-mode tasks whose (length << sh | time) words need more than 32 bits
+  // (flag 3: long gaps between states) run in an LDS table of 64-bit words (same labels,
+  // DESIGN.md §3.5); what outgrows it is flagged 3 again
+  {
+    constexpr int cap = kRouteTiers[SLOT_WIDE64].cap;
+    unsigned long long* c = tier_list(SLOT_WIDE64);
+    k_collect_tier_from<<<kCollectGrid, 1024, 0, stream>>>(flagged, cnt + C_FLAGGED, task_ovf, 0x8u, list, c);
+    RouteArgs rb = ra;
+    rb.task_list = list;
+    rb.list_count = c;
+    rb.queue = tier_queue(SLOT_WIDE64);
+    out->route_tier_code[SLOT_WIDE64] = route_tier_code(SLOT_WIDE64, cap, 1);
+    tier_begin(SLOT_WIDE64);
+    if (rwork) k_route<cap, 1, true, true, true><<<pgrid(4096, NT), 64, 0, stream>>>(g, rb, tier_bank(SLOT_WIDE64));
+    else k_route<cap, 1, true, true, false><<<pgrid(4096, NT), 64, 0, stream>>>(g, rb, nullptr);
+    tier_end(SLOT_WIDE64);
+  }
+#endif
+  return OTR_OK;
+}
+
+// edge-state tiers (turn-cost modes, otr_edge1.h), in the order of kEdgeSlots: OTR_E1CAP (360)
+// states (flag 5), 512 (flag 6), 1024 (flag 7); what outgrows those (flag 3) goes on to the
+// global-memory tiers
+int Batch::route_edge() {
+  if (NT == 0) return OTR_OK;
+  if (turns) {
+    // dump slots of the first two edge tiers: a search they outgrow between two rounds
+    // resumes in the next table (otr_edge1.h e1_dump / e1_restore) instead of starting
+    // over; slots for 1/16 of the tasks (C2, deployed: 4.4 % outgrow the first table),
+    // at most 4 GB / 1 GB — searches beyond them, or when the memory is not there,
+    // restart in the next table (same results)
+    unsigned long long* dump[2] = {nullptr, nullptr};
+    uint32_t dslots[2] = {0u, 0u};
+    constexpr int cap512 = kRouteTiers[SLOT_EDGE_512].cap, cap1024 = kRouteTiers[SLOT_EDGE_1024].cap;
+    const int caps[3] = {OTR_E1CAP, cap512, cap1024};
+    const uint32_t dwords[2] = {e1_dump_words(OTR_E1CAP), e1_dump_words(cap512)};
+    if (eresume && task_dump) {
+      const int64_t cap_bytes[2] = {4ll << 30, 1ll << 30};
+      const int64_t wanted[2] = {std::max<int64_t>(NT / 16, 4096), std::max<int64_t>(NT / 64, 1024)};
+      for (int q = 0; q < 2; ++q) {  // (no dumps beyond what was allocated: those searches restart)
+        const int64_t n = std::min<int64_t>(wanted[q], cap_bytes[q] / (8 * (int64_t)dwords[q]));
+        dump[q] = want<unsigned long long>(q == 0 ? S_E1DUMP0 : S_E1DUMP1, (size_t)n * dwords[q]);
+        dslots[q] = dump[q] ? (uint32_t)n : 0u;
+      }
+      if (!dump[0]) dump[1] = nullptr, dslots[1] = 0u;
+    }
+    for (int et = 0; et < 3; ++et) {
+      const int slot = kEdgeSlots[et];
+      out->route_tier_code[slot] = route_tier_code(slot, caps[et], 1);
+      unsigned long long* c = tier_list(slot);
+      k_collect_tier_from<<<kCollectGrid, 1024, 0, stream>>>(flagged, cnt + C_FLAGGED, task_ovf, 0x20u << et, list, c);
+      RouteArgs rb = ra;
+      rb.task_list = list;
+      // the first edge tier's list in spatial order (k_sort_*: one band of the map per XCD)
+      static const bool esort = !getenv("OTR_SORT") || atoi(getenv("OTR_SORT")) != 0;  // A/B knob
+      int64_t* list2 = nullptr;
+      uint32_t* hist = nullptr;
+      if (et == 0 && esort && NT >= 65536) {
+        list2 = want<int64_t>(S_SORT_LIST, NT);  // (no memory for the copy: the list stays in task order)
+        hist = list2 ? want<uint32_t>(S_SORT_HIST, kSortBuckets) : nullptr;
+      }
+      if (list2 && hist) {
+        int bits = 0;
+        while (bits < 32 && (g.n_edges >> bits) > 0u) ++bits;
+        const int shift = bits > 12 ? bits - 12 : 0;
+        HIPCHK(hipMemsetAsync(hist, 0, 4 * kSortBuckets, stream));
+        k_sort_hist<<<grid_for(NT, 1024), 1024, 0, stream>>>(list, c, task_rec, shift, hist);
+        k_sort_scan<<<1, 1024, 0, stream>>>(hist);
+        k_sort_place<<<grid_for(NT, 1024), 1024, 0, stream>>>(list, c, task_rec, shift, hist, list2);
+        rb.task_list = list2;
+      }
+      rb.list_count = c;
+      rb.queue = tier_queue(slot);
+      rb.dump_in = et > 0 ? dump[et - 1] : nullptr;
+      rb.dump_in_words = et > 0 ? dwords[et - 1] : 0u;
+      rb.dump_in_cap = et == 1 ? OTR_E1CAP : cap512;
+      rb.dump_out = et < 2 ? dump[et] : nullptr;  // (the last tier never dumps: otr_tiers.h)
+      rb.dump_ctr = queues + dump_ctr_word(slot);
+      rb.dump_out_words = et < 2 ? dwords[et] : 0u;
+      rb.dump_out_slots = et < 2 ? dslots[et] : 0u;
+      rb.task_dump = task_dump;
+      unsigned long long* rcn = tier_work(slot);
+      tier_begin(slot);
+      // persistent grids of at least every resident wave (16 per CU at 384 states, 13 at
+      // 512, 6 at 1024) claiming tasks from per-XCD queues; steps with more than 32
+      // targets (modes keeping > 32 candidates) pass the lean tiers (their TG = 32) on to
+      // k_general
+      if (et == 0) k_route_e1<OTR_E1CAP><<<pgrid(8192, NT), 64, 0, stream>>>(g, rb, rcn);
+      else if (et == 1) k_route_e1<cap512><<<pgrid(4096, NT), 64, 0, stream>>>(g, rb, rcn);
+      else k_route_e1<cap1024><<<pgrid(2048, NT), 64, 0, stream>>>(g, rb, rcn);
+      tier_end(slot);
+    }
+  }
+  mat.opt_busy = false;  // (every user of the optional workspace is queued)
+  return OTR_OK;
+}
+
+// everything left — tasks whose labels need 64 bits, overflows of the largest LDS tables
+// (node and edge-state) — runs in the global-memory search: first on 32K-slot slabs, then
+// what outgrew those on 1M-slot slabs
+int Batch::route_global() {
+  if (NT == 0) return OTR_OK;
+  int rc;
+  for (int gt = 0; gt < 2; ++gt) {
+    const int slot = SLOT_GLOBAL + gt;
+    unsigned long long* c = tier_list(slot);
+    k_collect_tier_from<<<kCollectGrid, 1024, 0, stream>>>(flagged, cnt + C_FLAGGED, task_ovf,
+                                                          gt == 0 ? 0x1Eu : 0x2u, list, c);
+    GSlabs gs2;
+    if ((rc = slabs(gt, &gs2))) return rc;
+    ga.mode = 0;
+    ga.list = list;
+    ga.list_count = c;
+    ga.flag = task_ovf;
+    ga.counters = tier_bank(slot);
+    out->route_tier_code[slot] = route_tier_code(slot, (int)gs2.cap, 0);
+    tier_begin(slot);
+    k_general<<<pgrid(gs2.n, NT), kGenThreads, 0, stream>>>(g, ga, gs2);
+    tier_end(slot);
+  }
+  // tasks still flagged (beyond a 1M-state slab): their traces get OTR_MATCH_ERROR
+  k_collect_tier_from<<<kCollectGrid, 1024, 0, stream>>>(flagged, cnt + C_FLAGGED, task_ovf, 0x1Eu, fail_tasks,
+                                                        cnt + C_TASKS_LEFT);
+  te(OTR_STAGE_ROUTE_BIG);
+  return OTR_OK;
+}
+
+// ---- K5: Viterbi
+int Batch::viterbi() {
   va.n_traces = T;
   va.trace_state_off = trace_state_off;
   va.cand_count = cb.count;
@@ -1523,13 +1601,19 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
     }
   }
   te(OTR_STAGE_VITERBI);
-  // ---- K6: winner paths (step list, tiers and general fallback counted on the device)
-  int64_t* path_off = need<int64_t>(S_PATH_OFF, S);
-  int32_t* path_len = need<int32_t>(S_PATH_LEN, S);
+  return OTR_OK;
+}
+
+// ---- K6: winner paths (step list, tiers and general fallback counted on the device); a
+// path buffer that proves too small grows and the stage runs again
+int Batch::paths() {
+  int rc;
+  path_off = need<int64_t>(S_PATH_OFF, S);
+  path_len = need<int32_t>(S_PATH_LEN, S);
   if (S > 0) k_fill_i32<<<grid_for(S, 256), 256, 0, stream>>>(path_len, S, 0);
   {
-    int64_t* steps = need<int64_t>(S_LIST2, std::max<int64_t>(S, 1));
-    unsigned long long* nsteps_d = cnt + 11;
+    steps = need<int64_t>(S_LIST2, std::max<int64_t>(S, 1));
+    nsteps_d = cnt + C_STEPS;
     // the small-search path tier (four searches per wave): steps whose winning route
     // bounds a search of at most OTR_SMALL_PATH_KEYS keys (estimate: 4 x the node density
     // x r^2, the diamond of road distance r around the root and its frontier); the
@@ -1540,10 +1624,10 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
     // tier (C5, C1): at C2 (3 % small) the synchronisation cost more than the tier saved.
     static const double small_path_keys =
         getenv("OTR_SMALL_PATH_KEYS") ? atof(getenv("OTR_SMALL_PATH_KEYS")) : kSmallPathKeys;  // A/B knob
-    const bool small_paths = small_path_keys > 0.0 && est_k > 0.f && (small_path_keys >= 1e8 || 2 * (NT4 + NT8) >= NT);
-    unsigned long long* nsteps4_d = cnt + 21;  // (the front list's count)
-    unsigned long long* nall_d = cnt + 22;     // (S: the collects' index range)
-    unsigned long long h_nsteps[2] = {0ull, 0ull};  // (front, back)
+    small_paths = small_path_keys > 0.0 && est_k > 0.f && (small_path_keys >= 1e8 || 2 * (NT4 + NT8) >= NT);
+    nsteps4_d = cnt + C_STEPS_FRONT;                          // (the front list's count)
+    unsigned long long* nall_d = cnt + C_STEPS_ALL;           // (S: the collects' index range)
+    static_assert(C_STEPS_ALL == C_STEPS_FRONT + 1, "cleared together below");
     if (S > 0 && small_paths) {
       PathClass pc{};
       pc.winner = va.winner;
@@ -1565,125 +1649,16 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
       k_step_list<<<grid_for(S, 1024), 1024, 0, stream>>>(S, sb.prev, va.brk, cb.count, steps, nsteps_d);
     }
     // the retry collects' index range: every step index (front and back lists), or the list
-    const unsigned long long* nscan_d = small_paths ? nall_d : nsteps_d;
-    int32_t* step_ovf = need<int32_t>(S_STEP_OVF, S + 1);
+    nscan_d = small_paths ? nall_d : nsteps_d;
+    step_ovf = need<int32_t>(S_STEP_OVF, S + 1);
     int64_t capacity = kShards * ((int64_t)S * 24 / kShards + 1024);
     bool paths_fit = S == 0;
     for (int attempt = 0; attempt < 8 && S > 0; ++attempt) {
-      uint32_t* path = need<uint32_t>(S_PATH, capacity);
-      if (!path || !step_ovf) {
-        if (err) *err = "device allocation failed (paths)";
-        return OTR_DEVICE_ERROR;
-      }
-      HIPCHK(hipMemsetAsync(step_ovf, 0, 4 * (S + 1), stream));
-      HIPCHK(hipMemsetAsync(cnt + 12, 0, 8 * 9, stream));  // path tier counts, cap flag
-      HIPCHK(hipMemsetAsync(cnt + 27, 0, 8 * 2, stream));  // edge-state path tier counts
-      HIPCHK(hipMemsetAsync(cnt + 32, 0, 8 * kShards, stream));
-      PathArgs pa{};
-      pa.steps = steps;
-      pa.n_steps = S;
-      pa.n_steps_dev = nsteps_d;
-      pa.prev = sb.prev;
-      pa.bound = sb.bound;
-      pa.brk = va.brk;
-      pa.winner = va.winner;
-      pa.cand_edge = cb.edge;
-      pa.cand_p = cb.p;
-      pa.state_trace = state_trace;
-      pa.mode = b.mode;
-      pa.cprep = ra.cprep;
-      pa.cprep_t = ra.cprep_t;
-      pa.bt = sb.bt;
-      pa.turn_modes = turn_modes;
-      pa.path_off = path_off;
-      pa.path_len = path_len;
-      pa.path = path;
-      pa.cursor = cnt + 32;
-      pa.capacity = capacity;
-      pa.overflow_flag = step_ovf;
-      pa.cap_flag = (int32_t*)(cnt + 20);
-      pa.cand_count = cb.count;
-      pa.trans_off = trans_off;
-      pa.trans = trans;
-      pa.force_edge = ra.force_edge;
-      // the path retry tiers' work queues (XcdQueue)
-      constexpr int kPQWords = 16 * 8;
-      unsigned long long* pq = need<unsigned long long>(S_PQUEUE, 8 * kPQWords);
-      HIPCHK(hipMemsetAsync(pq, 0, 8 * 8 * kPQWords, stream));
-      tb(OTR_STAGE_PATHS);
-      if (small_paths) {
-        // the front list four searches per wave, the back list two, each grid sized by its
-        // list's length (blocks past a list's end exit at once, but cost a dispatch each)
-        if (h_nsteps[0] > 0) {
-          PathArgs p4 = pa;
-          p4.n_steps_dev = nsteps4_d;
-          k_paths<OTR_CAP4, 4><<<(unsigned)grid_paths((int64_t)(h_nsteps[0] + 1) / 2).blocks, 64, 0, stream>>>(
-              g, p4, nullptr, nullptr);
-        }
-        if (h_nsteps[1] > 0) {
-          PathArgs p2 = pa;
-          p2.from_back = true;
-          k_paths<OTR_CAP1, 2><<<(unsigned)grid_paths((int64_t)h_nsteps[1]).blocks, 64, 0, stream>>>(g, p2, nullptr,
-                                                                                                     nullptr);
-        }
-      } else {
-        // (steps <= states: two searches per wave)
-        k_paths<OTR_CAP1, 2><<<(unsigned)grid_paths(S).blocks, 64, 0, stream>>>(g, pa, nullptr, nullptr);
-      }
-      te(OTR_STAGE_PATHS);
-      tb(OTR_STAGE_PATHS_BIG);
-      // large-table retries for table overflows (flag 1), on device-side lists; each
-      // launch's waves claim steps from its own per-XCD queue (XcdQueue)
-      for (int tier = 0; tier < 3; ++tier) {
-        unsigned long long* c = cnt + 12 + tier;
-        k_collect_tier_list<<<grid_for(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, 0x2u, list, c);
-        PathArgs pb = pa;
-        pb.queue = pq + tier * kPQWords;
-        if (tier == 0) k_paths<512, 1><<<pgrid(16384, S), 64, 0, stream>>>(g, pb, list, c);
-        else if (tier == 1) k_paths<1024, 1><<<pgrid(8192, S), 64, 0, stream>>>(g, pb, list, c);
-        else k_paths<4096, 1><<<pgrid(4096, S), 64, 0, stream>>>(g, pb, list, c);
-      }
-      // turn-cost winners (flag 5): the edge-state LDS search, 384 then 2048 states
-      if (turn_modes != 0u) {
-        for (int et = 0; et < 2; ++et) {
-          unsigned long long* c = cnt + 27 + et;
-          k_collect_tier_list<<<grid_for(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, et == 0 ? 0x20u : 0x40u,
-                                                                       list, c);
-          PathArgs pb = pa;
-          pb.queue = pq + (3 + et) * kPQWords;
-          if (et == 0) k_paths_edge<384><<<pgrid(4096, S), 64, 0, stream>>>(g, pb, d_turn, list, c, 6);
-          else k_paths_edge<2048><<<pgrid(512, S), 64, 0, stream>>>(g, pb, d_turn, list, c, 3);
-        }
-      }
-      // 64-bit labels, the largest-table overflows and what the edge tiers left: k_general
-      ga.steps = steps;
-      ga.winner = va.winner;
-      ga.path_off = path_off;
-      ga.path_len = path_len;
-      ga.path = path;
-      ga.cursor = cnt + 32;
-      ga.capacity = capacity;
-      ga.cap_flag = (int32_t*)(cnt + 20);
-      for (int gt = 0; gt < 2; ++gt) {
-        unsigned long long* c = cnt + 16 + gt;
-        k_collect_tier_list<<<grid_for(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, gt == 0 ? 0xAu : 0x2u, list,
-                                                                     c);
-        GSlabs gs2;
-        if ((rc = slabs(gt, &gs2))) return rc;
-        ga.mode = 1;
-        ga.list = list;
-        ga.list_count = c;
-        ga.flag = step_ovf;
-        ga.counters = nullptr;
-        k_general<<<pgrid(gs2.n, S), kGenThreads, 0, stream>>>(g, ga, gs2);
-      }
-      // steps still flagged (beyond a 1M-state slab): named after the final sync
-      k_collect_tier_list<<<grid_for(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, 0xAu, list, cnt + 18);
-      te(OTR_STAGE_PATHS_BIG);
+      if ((rc = paths_attempt(capacity))) return rc;
       unsigned long long capflag = 0;
       std::vector<unsigned long long> cur(kShards);
-      HIPCHK(hipMemcpyAsync(&capflag, cnt + 20, 8, hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipMemcpyAsync(cur.data(), cnt + 32, 8 * kShards, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipMemcpyAsync(&capflag, cnt + C_CAP_FLAG, 8, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipMemcpyAsync(cur.data(), cnt + C_CURSORS, 8 * kShards, hipMemcpyDeviceToHost, stream));
       HIPCHK(hipStreamSynchronize(stream));
       if ((capflag & 0xFFFFFFFFu) == 0) {  // every path fitted its region
         paths_fit = true;
@@ -1698,14 +1673,131 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
       return OTR_DEVICE_ERROR;
     }
   }
-  // ---- K7: stitching, segments, report()
+  return OTR_OK;
+}
+
+// one run of the path kernels into a buffer of `capacity` entries: the first tiers over the
+// step lists, the retry tiers, the edge-state tiers and the global-memory search
+int Batch::paths_attempt(int64_t capacity) {
+  int rc;
+  uint32_t* path = need<uint32_t>(S_PATH, capacity);
+  HIPCHK(hipMemsetAsync(step_ovf, 0, 4 * (S + 1), stream));
+  // path tier counts .. cap flag (the words between are the path stage's too)
+  HIPCHK(hipMemsetAsync(cnt + C_PATH_TIER, 0, 8 * (C_CAP_FLAG + 1 - C_PATH_TIER), stream));
+  HIPCHK(hipMemsetAsync(cnt + C_EDGE_PATH, 0, 8 * 2, stream));  // edge-state path tier counts
+  HIPCHK(hipMemsetAsync(cnt + C_CURSORS, 0, 8 * kShards, stream));
+  PathArgs pa{};
+  pa.steps = steps;
+  pa.n_steps = S;
+  pa.n_steps_dev = nsteps_d;
+  pa.prev = sb.prev;
+  pa.bound = sb.bound;
+  pa.brk = va.brk;
+  pa.winner = va.winner;
+  pa.cand_edge = cb.edge;
+  pa.cand_p = cb.p;
+  pa.state_trace = state_trace;
+  pa.mode = b.mode;
+  pa.cprep = ra.cprep;
+  pa.cprep_t = ra.cprep_t;
+  pa.bt = sb.bt;
+  pa.turn_modes = turn_modes;
+  pa.path_off = path_off;
+  pa.path_len = path_len;
+  pa.path = path;
+  pa.cursor = cnt + C_CURSORS;
+  pa.capacity = capacity;
+  pa.overflow_flag = step_ovf;
+  pa.cap_flag = (int32_t*)(cnt + C_CAP_FLAG);
+  pa.cand_count = cb.count;
+  pa.trans_off = trans_off;
+  pa.trans = trans;
+  pa.force_edge = ra.force_edge;
+  // the path retry tiers' work queues (XcdQueue)
+  constexpr int kPQWords = 16 * 8;
+  unsigned long long* pq = need<unsigned long long>(S_PQUEUE, 8 * kPQWords);
+  HIPCHK(hipMemsetAsync(pq, 0, 8 * 8 * kPQWords, stream));
+  tb(OTR_STAGE_PATHS);
+  if (small_paths) {
+    // the front list four searches per wave, the back list two, each grid sized by its
+    // list's length (blocks past a list's end exit at once, but cost a dispatch each)
+    if (h_nsteps[0] > 0) {
+      PathArgs p4 = pa;
+      p4.n_steps_dev = nsteps4_d;
+      k_paths<OTR_CAP4, 4><<<(unsigned)grid_paths((int64_t)(h_nsteps[0] + 1) / 2).blocks, 64, 0, stream>>>(
+          g, p4, nullptr, nullptr);
+    }
+    if (h_nsteps[1] > 0) {
+      PathArgs p2 = pa;
+      p2.from_back = true;
+      k_paths<OTR_CAP1, 2><<<(unsigned)grid_paths((int64_t)h_nsteps[1]).blocks, 64, 0, stream>>>(g, p2, nullptr,
+                                                                                                 nullptr);
+    }
+  } else {
+    // (steps <= states: two searches per wave)
+    k_paths<OTR_CAP1, 2><<<(unsigned)grid_paths(S).blocks, 64, 0, stream>>>(g, pa, nullptr, nullptr);
+  }
+  te(OTR_STAGE_PATHS);
+  tb(OTR_STAGE_PATHS_BIG);
+  // large-table retries for table overflows (flag 1), on device-side lists; each
+  // launch's waves claim steps from its own per-XCD queue (XcdQueue)
+  for (int tier = 0; tier < 3; ++tier) {
+    unsigned long long* c = cnt + C_PATH_TIER + tier;
+    k_collect_tier_list<<<grid_for(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, 0x2u, list, c);
+    PathArgs pb = pa;
+    pb.queue = pq + tier * kPQWords;
+    if (tier == 0) k_paths<512, 1><<<pgrid(16384, S), 64, 0, stream>>>(g, pb, list, c);
+    else if (tier == 1) k_paths<1024, 1><<<pgrid(8192, S), 64, 0, stream>>>(g, pb, list, c);
+    else k_paths<4096, 1><<<pgrid(4096, S), 64, 0, stream>>>(g, pb, list, c);
+  }
+  // turn-cost winners (flag 5): the edge-state LDS search, 384 then 2048 states
+  if (turn_modes != 0u) {
+    for (int et = 0; et < 2; ++et) {
+      unsigned long long* c = cnt + C_EDGE_PATH + et;
+      k_collect_tier_list<<<grid_for(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, et == 0 ? 0x20u : 0x40u,
+                                                                   list, c);
+      PathArgs pb = pa;
+      pb.queue = pq + (3 + et) * kPQWords;
+      if (et == 0) k_paths_edge<384><<<pgrid(4096, S), 64, 0, stream>>>(g, pb, d_turn, list, c, 6);
+      else k_paths_edge<2048><<<pgrid(512, S), 64, 0, stream>>>(g, pb, d_turn, list, c, 3);
+    }
+  }
+  // 64-bit labels, the largest-table overflows and what the edge tiers left: k_general
+  ga.steps = steps;
+  ga.winner = va.winner;
+  ga.path_off = path_off;
+  ga.path_len = path_len;
+  ga.path = path;
+  ga.cursor = cnt + C_CURSORS;
+  ga.capacity = capacity;
+  ga.cap_flag = (int32_t*)(cnt + C_CAP_FLAG);
+  for (int gt = 0; gt < 2; ++gt) {
+    unsigned long long* c = cnt + C_PATH_GLOBAL + gt;
+    k_collect_tier_list<<<grid_for(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, gt == 0 ? 0xAu : 0x2u, list,
+                                                                 c);
+    GSlabs gs2;
+    if ((rc = slabs(gt, &gs2))) return rc;
+    ga.mode = 1;
+    ga.list = list;
+    ga.list_count = c;
+    ga.flag = step_ovf;
+    ga.counters = nullptr;
+    k_general<<<pgrid(gs2.n, S), kGenThreads, 0, stream>>>(g, ga, gs2);
+  }
+  // steps still flagged (beyond a 1M-state slab): named after the final sync
+  k_collect_tier_list<<<grid_for(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, 0xAu, list, cnt + C_PATHS_LEFT);
+  te(OTR_STAGE_PATHS_BIG);
+  return OTR_OK;
+}
+
+// ---- K7..K9: stitching, segments, report(); hour buckets -> histogram; tile rows
+int Batch::segments() {
+  int rc;
   int64_t* cap = need<int64_t>(S_CAP, T);
-  int64_t* cap_off = need<int64_t>(S_CAP_OFF, T + 1);
+  cap_off = need<int64_t>(S_CAP_OFF, T + 1);
   k_capacity<<<grid_for(T, 256), 256, 0, stream>>>(T, trace_state_off, cb.count, path_len, cap);
   if ((rc = scan(cap, cap_off, T))) return rc;
-  int64_t C = 0;
   if ((rc = read_i64(cap_off + T, &C))) return rc;
-  SegArgs sa{};
   sa.b = b;
   sa.trace_state_off = trace_state_off;
   sa.state_probe = state_probe;
@@ -1763,7 +1855,6 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
   k_segments<<<(unsigned)grid_segments(T).blocks, 64, 0, stream>>>(g, sa, d_counters);
   te(OTR_STAGE_SEGMENTS);
   // ---- K8: hour buckets → histogram
-  HistArgs ha{};
   ha.b = b;
   ha.cap_off = cap_off;
   ha.rep_n = sa.rep_n;
@@ -1778,7 +1869,7 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
   ha.hours = in->hist_hours;
   ha.n_segments = g.n_segments;
   ha.n_rows = d_counters + 8 * kCShards;
-  size_t hist_len = (size_t)(in->hist_hours > 0 ? in->hist_hours : 0) * g.n_segments * OTR_HIST_BINS;
+  hist_len = (size_t)(in->hist_hours > 0 ? in->hist_hours : 0) * g.n_segments * OTR_HIST_BINS;
   ha.hist = hist_len ? (in->hist_device ? in->hist_device : need<uint32_t>(S_HIST, hist_len)) : nullptr;
   if (hist_len) HIPCHK(hipMemsetAsync(ha.hist, 0, hist_len * 4, stream));
   tb(OTR_STAGE_HISTOGRAM);
@@ -1813,24 +1904,33 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
     out->n_rows = R;
   }
   HIPCHK(hipGetLastError());
-  std::vector<unsigned long long> hc(n_ctr);
-  unsigned long long h_fail[2] = {0ull, 0ull};  // route tasks / paths beyond every search tier
+  return OTR_OK;
+}
+
+// the work counters folded, the counts of what no tier could search and the per-trace
+// output counts: one host wait per batch for all of them
+int Batch::drain() {
+  hc.resize(n_ctr);
   k_ctr_fold<<<(unsigned)n_ctr, kCShards, 0, stream>>>(d_counters, d_counters + kBanks * bank);
   HIPCHK(hipMemcpyAsync(hc.data(), d_counters + kBanks * bank, n_ctr * 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(&h_fail[0], cnt + 10, 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(&h_fail[1], cnt + 18, 8, hipMemcpyDeviceToHost, stream));
-  // per-trace output counts in the same drain (one host wait per batch for all of them)
-  std::vector<int64_t> route_n(T), seg_n(T), way_n(T), rep_n(T);
+  HIPCHK(hipMemcpyAsync(&h_fail[0], cnt + C_TASKS_LEFT, 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(&h_fail[1], cnt + C_PATHS_LEFT, 8, hipMemcpyDeviceToHost, stream));
+  route_n.resize(T), seg_n.resize(T), way_n.resize(T), rep_n.resize(T);
   HIPCHK(hipMemcpyAsync(route_n.data(), sa.route_n, 8 * T, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipMemcpyAsync(seg_n.data(), sa.seg_n, 8 * T, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipMemcpyAsync(rep_n.data(), sa.rep_n, 8 * T, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipMemcpyAsync(way_n.data(), sa.way_n, 8 * T, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
-  if (h_fail[0] + h_fail[1] > 0 && getenv("OTR_DEBUG_FAIL")) {  // diagnostic: which stage, which tiers
-    unsigned long long hc2[32];
-    HIPCHK(hipMemcpy(hc2, cnt, 8 * 32, hipMemcpyDeviceToHost));
+  return OTR_OK;
+}
+
+// OTR_DEBUG_FAIL diagnostic: which stage left searches beyond every tier, which tiers saw them
+int Batch::debug_fail() {
+  if (h_fail[0] + h_fail[1] > 0 && getenv("OTR_DEBUG_FAIL")) {
+    unsigned long long hc2[C_CURSORS];
+    HIPCHK(hipMemcpy(hc2, cnt, 8 * C_CURSORS, hipMemcpyDeviceToHost));
     fprintf(stderr, "otr: %llu route tasks, %llu paths beyond every tier; tier lists:", h_fail[0], h_fail[1]);
-    for (int k = 0; k < 32; ++k) fprintf(stderr, " %llu", hc2[k]);
+    for (int k = 0; k < C_CURSORS; ++k) fprintf(stderr, " %llu", hc2[k]);
     fprintf(stderr, "\n");
     if (h_fail[1]) {  // the first failing winner paths: state, its step's bound and winning route
       const int64_t* steps_d = need<int64_t>(S_LIST2, 1);
@@ -1854,8 +1954,12 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
       }
     }
   }
+  return OTR_OK;
+}
+
+// tasks / steps beyond a 1M-state slab (never seen): name the traces (task/step -> state -> trace)
+int Batch::name_failed() {
   if (h_fail[0] + h_fail[1] > 0) {
-    // beyond a 1M-state slab (never seen): name the traces (task/step -> state -> trace)
     for (int which = 0; which < 2; ++which) {
       const unsigned long long nf = h_fail[which];
       if (!nf) continue;
@@ -1873,59 +1977,67 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
           HIPCHK(hipMemcpy(&sidx, src + idx[k], 8, hipMemcpyDeviceToHost));
         }
         HIPCHK(hipMemcpy(&t, state_trace + sidx, 4, hipMemcpyDeviceToHost));
-        if (t >= 0 && t < T && h_trace_status[t] == OTR_OK) {
-          h_trace_status[t] = OTR_MATCH_ERROR;
+        if (t >= 0 && t < T && mat.h_trace_status[t] == OTR_OK) {
+          mat.h_trace_status[t] = OTR_MATCH_ERROR;
           ++out->n_overflow_traces;
         }
       }
     }
   }
-  auto ctr = [&](int b, int k) {
-    return hc[(size_t)b * OTR_COUNTERS + (size_t)k];
-  };
-  for (int k = 0; k < OTR_COUNTERS; ++k) out->counters[k] = ctr(0, k);
-  for (int k : {3, 4, 13, 14}) out->counters[k] += ctr(12, k) + ctr(13, k);  // (the first tier: every launch)
-  // per route kernel: searches, settled, relaxed, transition entries (banks 0, 2..6, 8..9;
-  // slot 8, the 64-bit LDS tier: bank 7; the edge-state tiers: slot 10 the first (bank 10),
-  // slot 9 the 512-state one (bank 1), slot 11 the 1024-state one (bank 11))
-  for (int t = 0; t < 14; ++t) {
-    const int b = t == 0 ? 0 : (t < 6 ? 1 + t : (t < 8 ? 2 + t : (t == 8 ? 7 : (t == 9 ? 1 : t))));
-    out->route_tier_work[t][0] = ctr(b, 6);
-    out->route_tier_work[t][1] = ctr(b, 3);
-    out->route_tier_work[t][2] = ctr(b, 4);
-    out->route_tier_work[t][3] = ctr(b, 5);
-    if ((t >= 1 && t < 6) || t == 8) {  // the LDS retry tiers together (counters 9 / 10)
-      out->counters[9] += ctr(b, 3);
-      out->counters[10] += ctr(b, 4);
+  return OTR_OK;
+}
+
+// the folded work counters into otr_batch_result's counters and route_tier_work (each tier
+// from its bank, otr_tiers.h), and the stage and tier times
+void Batch::fold_counters() {
+  const int bank_first = kRouteTiers[SLOT_FIRST].bank;  // (also the batch's own counters)
+  for (int k = 0; k < OTR_COUNTERS; ++k) out->counters[k] = ctr(bank_first, k);
+  for (int k : {3, 4, 13, 14})  // (the first tier: every launch)
+    out->counters[k] += ctr(kRouteTiers[SLOT_SMALL].bank, k) + ctr(kRouteTiers[SLOT_TINY].bank, k);
+  out->counters[11] = out->counters[12] = 0;
+  // per route kernel: searches, settled, relaxed, transition entries
+  for (int t = 0; t < kRouteSlots; ++t) {
+    const int tb_ = kRouteTiers[t].bank;
+    const TierKind kind = kRouteTiers[t].kind;
+    out->route_tier_work[t][0] = ctr(tb_, 6);
+    out->route_tier_work[t][1] = ctr(tb_, 3);
+    out->route_tier_work[t][2] = ctr(tb_, 4);
+    out->route_tier_work[t][3] = ctr(tb_, 5);
+    if (kind == TierKind::NodeRetry || kind == TierKind::Wide64) {  // the LDS retry tiers together (counters 9 / 10)
+      out->counters[9] += ctr(tb_, 3);
+      out->counters[10] += ctr(tb_, 4);
+    }
+    if (kind == TierKind::NodeRetry) {  // node searches resumed from / dumped to a retry tier's dump
+      out->counters[11] += ctr(tb_, 11);
+      out->counters[12] += ctr(tb_, 12);
     }
   }
   out->counters[5] = (uint64_t)NT;
   out->counters[6] = (uint64_t)NTR;
   // edge-state searches resumed from a dump (the 512- and 1024-state tiers) and dumped
   // (the first two edge tiers), with OTR_BATCH_ROUTE_WORK
-  out->counters[22] = ctr(1, 22) + ctr(11, 22);
-  out->counters[23] = ctr(10, 23) + ctr(1, 23);
-  // node searches resumed from / dumped to a retry tier's dump (the node retry tiers, banks 2..6)
-  out->counters[11] = out->counters[12] = 0;
-  for (int b = 2; b < 7; ++b) {
-    out->counters[11] += ctr(b, 11);
-    out->counters[12] += ctr(b, 12);
-  }
+  out->counters[22] = ctr(kRouteTiers[kEdgeSlots[1]].bank, 22) + ctr(kRouteTiers[kEdgeSlots[2]].bank, 22);
+  out->counters[23] = ctr(kRouteTiers[kEdgeSlots[0]].bank, 23) + ctr(kRouteTiers[kEdgeSlots[1]].bank, 23);
   if (!(in->flags & OTR_BATCH_TILE_ROWS)) out->n_rows = (int64_t)out->counters[8];
   else out->counters[8] = (uint64_t)out->n_rows;  // K9 counted them (K8 may not have run)
   out->d_hist = ha.hist;
   out->hist_len = (int64_t)hist_len;
   if (timing) {
     for (int k = 0; k < 10; ++k)
-      if (used[k]) (void)hipEventElapsedTime(&out->kernel_ms[k], ev[2 * k], ev[2 * k + 1]);
-    for (int t = 1; t < 14; ++t)
-      if (out->route_tier_code[t] != 0)
-        (void)hipEventElapsedTime(&out->route_tier_ms[t], ev[24 + 2 * t], ev[24 + 2 * t + 1]);
+      if (used[k]) (void)hipEventElapsedTime(&out->kernel_ms[k], mat.ev[2 * k], mat.ev[2 * k + 1]);
+    for (int t = 0; t < kRouteSlots; ++t)
+      if (t != SLOT_FIRST && out->route_tier_code[t] != 0)
+        (void)hipEventElapsedTime(&out->route_tier_ms[t], mat.ev[route_event(t)], mat.ev[route_event(t) + 1]);
     // (the route stage holds the tiny and small tiers' launches, then the two-search tier's)
-    out->route_tier_ms[0] = out->kernel_ms[OTR_STAGE_ROUTE] - out->route_tier_ms[12] - out->route_tier_ms[13];
+    out->route_tier_ms[SLOT_FIRST] =
+        out->kernel_ms[OTR_STAGE_ROUTE] - out->route_tier_ms[SLOT_SMALL] - out->route_tier_ms[SLOT_TINY];
     (void)hipGetLastError();  // an unrecorded pair must not leave a sticky error for the next call
   }
-  // ---- copy-out (tests / JSON path), compacting the capacity layout
+}
+
+// ---- copy-out (tests / JSON path), compacting the capacity layout
+int Batch::copy_out() {
+  int rc;
   int64_t nroute = 0, nseg = 0, nrep = 0;
   for (int t = 0; t < T; ++t) {
     nroute += route_n[t];
@@ -1938,25 +2050,20 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
   out->status = out->n_overflow_traces ? OTR_MATCH_ERROR : OTR_OK;
   const bool full = (in->flags & OTR_BATCH_COPY_OUT) != 0;
   if (!full && !(in->flags & OTR_BATCH_COPY_REPORTS)) return OTR_OK;
-  out->trace_status = h_trace_status.data();
-  auto dl = [&](auto& vec, const void* src, size_t n) -> int {
-    vec.resize(n ? n : 1);
-    if (n) HIPCHK(hipMemcpyAsync(vec.data(), src, n * sizeof(vec[0]), hipMemcpyDeviceToHost, stream));
-    return OTR_OK;
-  };
+  out->trace_status = mat.h_trace_status.data();
   if (full) {
-    if ((rc = dl(h_trace_state_off, trace_state_off, T + 1))) return rc;
-    if ((rc = dl(h_state_probe, state_probe, S))) return rc;
-    if ((rc = dl(h_cand_count, cb.count, S))) return rc;
-    if ((rc = dl(h_cand_edge, cb.edge, (size_t)S * OTR_KMAX))) return rc;
-    if ((rc = dl(h_cand_p, cb.p, (size_t)S * OTR_KMAX))) return rc;
-    if ((rc = dl(h_cand_sqd, cb.sqd, (size_t)S * OTR_KMAX))) return rc;
-    if ((rc = dl(h_winner, va.winner, S))) return rc;
-    if ((rc = dl(h_subpath, va.subpath, S))) return rc;
+    if ((rc = dl(mat.h_trace_state_off, trace_state_off, T + 1))) return rc;
+    if ((rc = dl(mat.h_state_probe, state_probe, S))) return rc;
+    if ((rc = dl(mat.h_cand_count, cb.count, S))) return rc;
+    if ((rc = dl(mat.h_cand_edge, cb.edge, (size_t)S * OTR_KMAX))) return rc;
+    if ((rc = dl(mat.h_cand_p, cb.p, (size_t)S * OTR_KMAX))) return rc;
+    if ((rc = dl(mat.h_cand_sqd, cb.sqd, (size_t)S * OTR_KMAX))) return rc;
+    if ((rc = dl(mat.h_winner, va.winner, S))) return rc;
+    if ((rc = dl(mat.h_subpath, va.subpath, S))) return rc;
   }
-  if ((rc = dl(h_shape_used, sa.shape_used, T))) return rc;
-  if ((rc = dl(h_stats, sa.stats, 7 * (size_t)T))) return rc;
-  if ((rc = dl(h_stats_len, sa.stats_len, 2 * (size_t)T))) return rc;
+  if ((rc = dl(mat.h_shape_used, sa.shape_used, T))) return rc;
+  if ((rc = dl(mat.h_stats, sa.stats, 7 * (size_t)T))) return rc;
+  if ((rc = dl(mat.h_stats_len, sa.stats_len, 2 * (size_t)T))) return rc;
   // dense layout on device (k_compact), then only the used entries cross PCIe
   int64_t nway = 0;
   for (int t = 0; t < T; ++t) nway += way_n[t];
@@ -1999,60 +2106,60 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
   int64_t* seg_way_off = need<int64_t>(S_C_SEG_WAY_OFF, (size_t)nseg + 1);
   if ((rc = scan(ca.seg_way_n, seg_way_off, nseg))) return rc;
   HIPCHK(hipGetLastError());
-  if (full && (rc = dl(h_route_edge, ca.route, nroute))) return rc;
-  if (!full) h_route_edge.clear();
-  if ((rc = dl(h_seg_id, ca.seg_id, nseg)) || (rc = dl(h_seg_start, ca.seg_start, nseg)) ||
-      (rc = dl(h_seg_end, ca.seg_end, nseg)) || (rc = dl(h_seg_length, ca.seg_length, nseg)) ||
-      (rc = dl(h_seg_queue, ca.seg_queue, nseg)) || (rc = dl(h_seg_internal, ca.seg_internal, nseg)) ||
-      (rc = dl(h_seg_bshape, ca.seg_bshape, nseg)) || (rc = dl(h_seg_eshape, ca.seg_eshape, nseg)) ||
-      (rc = dl(h_seg_way_off, seg_way_off, (size_t)nseg + 1)) || (rc = dl(h_seg_way, ca.seg_way, nway)) ||
-      (rc = dl(h_rep_id, ca.rep_id, nrep)) || (rc = dl(h_rep_next, ca.rep_next, nrep)) ||
-      (rc = dl(h_rep_t0, ca.rep_t0, nrep)) || (rc = dl(h_rep_t1, ca.rep_t1, nrep)) ||
-      (rc = dl(h_rep_length, ca.rep_length, nrep)) || (rc = dl(h_rep_queue, ca.rep_queue, nrep)))
+  if (full && (rc = dl(mat.h_route_edge, ca.route, nroute))) return rc;
+  if (!full) mat.h_route_edge.clear();
+  if ((rc = dl(mat.h_seg_id, ca.seg_id, nseg)) || (rc = dl(mat.h_seg_start, ca.seg_start, nseg)) ||
+      (rc = dl(mat.h_seg_end, ca.seg_end, nseg)) || (rc = dl(mat.h_seg_length, ca.seg_length, nseg)) ||
+      (rc = dl(mat.h_seg_queue, ca.seg_queue, nseg)) || (rc = dl(mat.h_seg_internal, ca.seg_internal, nseg)) ||
+      (rc = dl(mat.h_seg_bshape, ca.seg_bshape, nseg)) || (rc = dl(mat.h_seg_eshape, ca.seg_eshape, nseg)) ||
+      (rc = dl(mat.h_seg_way_off, seg_way_off, (size_t)nseg + 1)) || (rc = dl(mat.h_seg_way, ca.seg_way, nway)) ||
+      (rc = dl(mat.h_rep_id, ca.rep_id, nrep)) || (rc = dl(mat.h_rep_next, ca.rep_next, nrep)) ||
+      (rc = dl(mat.h_rep_t0, ca.rep_t0, nrep)) || (rc = dl(mat.h_rep_t1, ca.rep_t1, nrep)) ||
+      (rc = dl(mat.h_rep_length, ca.rep_length, nrep)) || (rc = dl(mat.h_rep_queue, ca.rep_queue, nrep)))
     return rc;
   HIPCHK(hipStreamSynchronize(stream));
-  h_trace_route_off.assign(T + 1, 0);
-  h_trace_seg_off.assign(T + 1, 0);
-  h_trace_rep_off.assign(T + 1, 0);
+  mat.h_trace_route_off.assign(T + 1, 0);
+  mat.h_trace_seg_off.assign(T + 1, 0);
+  mat.h_trace_rep_off.assign(T + 1, 0);
   for (int t = 0; t < T; ++t) {
-    h_trace_route_off[t + 1] = h_trace_route_off[t] + route_n[t];
-    h_trace_seg_off[t + 1] = h_trace_seg_off[t] + seg_n[t];
-    h_trace_rep_off[t + 1] = h_trace_rep_off[t] + rep_n[t];
+    mat.h_trace_route_off[t + 1] = mat.h_trace_route_off[t] + route_n[t];
+    mat.h_trace_seg_off[t + 1] = mat.h_trace_seg_off[t] + seg_n[t];
+    mat.h_trace_rep_off[t + 1] = mat.h_trace_rep_off[t] + rep_n[t];
   }
   auto P = [](auto& v) { return v.empty() ? nullptr : v.data(); };
   if (full) {
-    out->trace_state_off = P(h_trace_state_off);
-    out->state_probe = P(h_state_probe);
-    out->cand_count = P(h_cand_count);
-    out->cand_edge = P(h_cand_edge);
-    out->cand_p = P(h_cand_p);
-    out->cand_sqd = P(h_cand_sqd);
-    out->winner = P(h_winner);
-    out->subpath = P(h_subpath);
-    out->trace_route_off = P(h_trace_route_off);
-    out->route_edge = P(h_route_edge);
+    out->trace_state_off = P(mat.h_trace_state_off);
+    out->state_probe = P(mat.h_state_probe);
+    out->cand_count = P(mat.h_cand_count);
+    out->cand_edge = P(mat.h_cand_edge);
+    out->cand_p = P(mat.h_cand_p);
+    out->cand_sqd = P(mat.h_cand_sqd);
+    out->winner = P(mat.h_winner);
+    out->subpath = P(mat.h_subpath);
+    out->trace_route_off = P(mat.h_trace_route_off);
+    out->route_edge = P(mat.h_route_edge);
   }
-  out->trace_seg_off = P(h_trace_seg_off);
-  out->seg_id = (uint64_t*)P(h_seg_id);
-  out->seg_start = P(h_seg_start);
-  out->seg_end = P(h_seg_end);
-  out->seg_length = P(h_seg_length);
-  out->seg_queue = P(h_seg_queue);
-  out->seg_internal = P(h_seg_internal);
-  out->seg_begin_shape = P(h_seg_bshape);
-  out->seg_end_shape = P(h_seg_eshape);
-  out->seg_way_off = P(h_seg_way_off);
-  out->seg_way = P(h_seg_way);
-  out->trace_rep_off = P(h_trace_rep_off);
-  out->rep_id = (uint64_t*)P(h_rep_id);
-  out->rep_next = (uint64_t*)P(h_rep_next);
-  out->rep_t0 = P(h_rep_t0);
-  out->rep_t1 = P(h_rep_t1);
-  out->rep_length = P(h_rep_length);
-  out->rep_queue = P(h_rep_queue);
-  out->shape_used = P(h_shape_used);
-  out->stats = P(h_stats);
-  out->stats_len = P(h_stats_len);
+  out->trace_seg_off = P(mat.h_trace_seg_off);
+  out->seg_id = (uint64_t*)P(mat.h_seg_id);
+  out->seg_start = P(mat.h_seg_start);
+  out->seg_end = P(mat.h_seg_end);
+  out->seg_length = P(mat.h_seg_length);
+  out->seg_queue = P(mat.h_seg_queue);
+  out->seg_internal = P(mat.h_seg_internal);
+  out->seg_begin_shape = P(mat.h_seg_bshape);
+  out->seg_end_shape = P(mat.h_seg_eshape);
+  out->seg_way_off = P(mat.h_seg_way_off);
+  out->seg_way = P(mat.h_seg_way);
+  out->trace_rep_off = P(mat.h_trace_rep_off);
+  out->rep_id = (uint64_t*)P(mat.h_rep_id);
+  out->rep_next = (uint64_t*)P(mat.h_rep_next);
+  out->rep_t0 = P(mat.h_rep_t0);
+  out->rep_t1 = P(mat.h_rep_t1);
+  out->rep_length = P(mat.h_rep_length);
+  out->rep_queue = P(mat.h_rep_queue);
+  out->shape_used = P(mat.h_shape_used);
+  out->stats = P(mat.h_stats);
+  out->stats_len = P(mat.h_stats_len);
   return OTR_OK;
 }
 

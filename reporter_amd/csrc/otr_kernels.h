@@ -310,6 +310,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(G == 2 ? OTR
   const int mode = have && b.mode[state_trace[s]] < OTR_MODES ? b.mode[state_trace[s]] : 0;
   // the mode's parameters by selects (G = 2: the mode is a per-group register, and a
   // register-indexed kernel argument would go through scratch)
+  static_assert(OTR_MODES == 3, "pick() selects among exactly three modes");
   auto pick = [&](auto f) { return mode == 0 ? f(mp.m[0]) : (mode == 1 ? f(mp.m[1]) : f(mp.m[OTR_MODES - 1])); };
   const uint32_t mode_bit = 1u << mode;
   const int kmax = pick([](const MatchParams& q) { return q.kmax; });
