@@ -164,7 +164,16 @@ typedef struct otr_tile_row {
 enum { OTR_STAGE_STATES = 0, OTR_STAGE_CANDIDATES, OTR_STAGE_LINK, OTR_STAGE_ROUTE, OTR_STAGE_ROUTE_BIG,
        OTR_STAGE_VITERBI, OTR_STAGE_PATHS, OTR_STAGE_PATHS_BIG, OTR_STAGE_SEGMENTS, OTR_STAGE_HISTOGRAM,
        OTR_STAGE_TOTAL };
-#define OTR_HIST_BINS 8        /* speed bins of 20 km/h: [0,20) … [140,∞) */
+/* kernel_ms[OTR_VITERBI_VARIANT] is not a time: the host writes there, with or without
+ * OTR_BATCH_TIMING, which k_viterbi instance the batch ran: 11 one trace per wave with the
+ * predecessor scan split over the wave's halves (k_viterbi<1, true>: every mode keeps <= 32
+ * candidates and the batch has fewer than OTR_VIT_SPLIT traces, default 8192), 20 two traces
+ * per wave (k_viterbi<2>: <= 32 candidates, larger batches; OTR_VIT_SPLIT=0 selects it at any
+ * size), 10 one trace per wave (k_viterbi<1>: some mode keeps more than 32 candidates).
+ * (counters[15], the one counter word no kernel counts into, is pinned to 0 together with
+ * every route_tier_* slot by tests/golden/route_tier_slots.json, so the code lives here.) */
+#define OTR_VITERBI_VARIANT 15
+#define OTR_HIST_BINS 8       /* speed bins of 20 km/h: [0,20) … [140,∞) */
 
 /* All pointers below are owned by the matcher and stay valid until the next batch
  * call or otr_matcher_free.  Host arrays are filled only with OTR_BATCH_COPY_OUT;
@@ -202,7 +211,8 @@ typedef struct otr_batch_result {
                                   and 14 table keys (first-tier route launch),
                                   16-21 diagnostic-build search phase cycles, 22/23 edge-state
                                   searches resumed from / dumped to HBM (next table) */
-  float kernel_ms[16];         /* OTR_BATCH_TIMING: device time per stage, OTR_STAGE_* */
+  float kernel_ms[16];         /* OTR_BATCH_TIMING: device time per stage, OTR_STAGE_*;
+                                  [OTR_VITERBI_VARIANT]: the k_viterbi instance code (always) */
   int32_t* trace_status;       /* host, per trace (with COPY_OUT / COPY_REPORTS): OTR_OK, or
                                   OTR_MATCH_ERROR when its search outgrew the largest LDS table */
   otr_tile_row* d_rows;        /* OTR_BATCH_TILE_ROWS: n_rows tile rows in HBM (matcher-owned),

@@ -39,9 +39,9 @@ def _close(name, a, b, errors, stats):
     rel = np.abs(a - b) / den
     bad = rel > REL_TOL
     if bad.any():
-        i = np.flatnonzero(bad)[:5]
-        errors.append('%s: %d values beyond %g rel, e.g. %s vs %s' % (name, int(bad.sum()), REL_TOL,
-                                                                      a[i].tolist(), b[i].tolist()))
+        i = np.flatnonzero(bad)[:5]  # (flat indices: stats_len is two-dimensional)
+        errors.append('%s: %d values beyond %g rel, e.g. %s vs %s' % (
+            name, int(bad.sum()), REL_TOL, a.reshape(-1)[i].tolist(), b.reshape(-1)[i].tolist()))
 
 
 def compare(gpu, orc):

@@ -32,6 +32,7 @@ HIST_BINS = 8
 KMAX = 64
 STAGES = ['states', 'candidates', 'link', 'route', 'route_big', 'viterbi', 'paths', 'paths_big', 'segments',
           'histogram']
+VITERBI_VARIANT = 15  # kernel_ms slot of the k_viterbi instance code (otr.h OTR_VITERBI_VARIANT)
 
 # every symbol include/otr.h declares
 EXPORTS = ['otr_configure', 'otr_configure_json', 'otr_matcher_new', 'otr_matcher_free', 'otr_match',

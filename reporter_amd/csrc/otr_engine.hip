@@ -794,6 +794,7 @@ struct Batch {
   int32_t *state_trace = nullptr, *path_len = nullptr;
   uint32_t turn_modes = 0;  // modes whose searches carry turn costs (edge-based, k_general)
   bool k32 = true;          // no mode keeps more than 32 candidates (K <= 32 lanes)
+  int vit_variant = 0;      // the k_viterbi instance viterbi() launched (otr.h: OTR_VITERBI_VARIANT)
   // the first tiers' size estimate (link())
   int route_g = 2, n_est_tiers = 0;
   float est_k = 0.f, est_v[OTR_MODES] = {};
@@ -1592,11 +1593,14 @@ int Batch::viterbi() {
     // one trace per wave with each step's predecessor scan split over the two halves
     static const int64_t split_below = getenv("OTR_VIT_SPLIT") ? atoll(getenv("OTR_VIT_SPLIT")) : 8192;  // A/B knob
     if (k32 && T < split_below) {
+      vit_variant = 11;
       k_viterbi<1, true><<<(unsigned)(T < 1048576 ? T : 1048576), 64, 0, stream>>>(va, d_counters);
     } else if (k32) {
+      vit_variant = 20;
       const int64_t w = (T + 1) / 2;
       k_viterbi<2><<<(unsigned)(w < 1048576 ? w : 1048576), 64, 0, stream>>>(va, d_counters);
     } else {
+      vit_variant = 10;
       k_viterbi<1><<<(unsigned)(T < 1048576 ? T : 1048576), 64, 0, stream>>>(va, d_counters);
     }
   }
@@ -2022,6 +2026,7 @@ void Batch::fold_counters() {
   else out->counters[8] = (uint64_t)out->n_rows;  // K9 counted them (K8 may not have run)
   out->d_hist = ha.hist;
   out->hist_len = (int64_t)hist_len;
+  out->kernel_ms[OTR_VITERBI_VARIANT] = (float)vit_variant;  // (a code, not a time: otr.h)
   if (timing) {
     for (int k = 0; k < 10; ++k)
       if (used[k]) (void)hipEventElapsedTime(&out->kernel_ms[k], mat.ev[2 * k], mat.ev[2 * k + 1]);
