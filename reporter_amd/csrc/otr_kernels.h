@@ -815,12 +815,10 @@ __host__ __device__ inline bool pack_fits(uint32_t bmm, uint32_t sh) {
 // label and the smallest pending time + its entry time breaks the time bound) settled
 // 3.2 % fewer nodes at C2 and made the first tier 2.5 % slower (the per-round minimum,
 // six more registers).
-template <int CAP, int LM, bool OLD = false>
-__device__ inline bool target_resolved(const SearchLds<CAP, LM>& L, const Pack& K, int tslot, uint32_t tpart,
-                                       uint32_t gapT, uint32_t pd, uint32_t kmin, bool pend_empty) {
-  const int ts = tslot < 0 ? 0 : tslot;
-  const uint32_t key = L.key[ts];
-  const typename LabelT<LM>::W lw = LabelT<LM>::label(L.lab[ts]);
+// (target_test: the test on the slot's words; search_run reads them a round ahead)
+template <int LM, bool OLD = false>
+__device__ inline bool target_test(uint32_t key, typename LabelT<LM>::W lw, const Pack& K, int tslot, uint32_t tpart,
+                                   uint32_t gapT, uint32_t pd, uint32_t kmin, bool pend_empty) {
   if constexpr (LM != 2 && !OLD) {
     // 32-bit label words: the whole test in 32-bit arithmetic (otr_pred.h)
     const bool fin = target_final32(lw == LabelT<LM>::kNone, K.d(lw), kmin, gapT, tpart, pd);
@@ -832,6 +830,20 @@ __device__ inline bool target_resolved(const SearchLds<CAP, LM>& L, const Pack& 
     return (tslot < 0) | pend_empty | ((key & kRel) != 0u) | (lab < next) | unreach;
   }
 }
+template <int CAP, int LM, bool OLD = false>
+__device__ inline bool target_resolved(const SearchLds<CAP, LM>& L, const Pack& K, int tslot, uint32_t tpart,
+                                       uint32_t gapT, uint32_t pd, uint32_t kmin, bool pend_empty) {
+  const int ts = tslot < 0 ? 0 : tslot;
+  const uint32_t key = L.key[ts];
+  const typename LabelT<LM>::W lw = LabelT<LM>::label(L.lab[ts]);
+  return target_test<LM, OLD>(key, lw, K, tslot, tpart, gapT, pd, kmin, pend_empty);
+}
+
+// search_run's lane word (`tail`): kAdjMore, the lane's node has a CSR tail; kProbeOut, a
+// probe chain of the lane ran out of table this round (L.overflow is written as well: the
+// rounds read the lane bits by ballot instead of the LDS word)
+constexpr uint32_t kProbeOut = 1u;
+static_assert((kProbeOut & kAdjMore) == 0u, "two bits of one lane word");
 
 // Relax edge (u → dw) with u's FINAL packed label pu: the offer (length nd, time tt) is
 // pruned when it breaks a bound (pd / pt: B and bt relative to the root),
@@ -844,7 +856,7 @@ template <int CAP, int LM, bool COUNT = true, bool OLD = false>
 __device__ inline int relax_one(SearchLds<CAP, LM>& L, const Pack& K, uint32_t dw, uint32_t len_mm,
                                 uint32_t time_ds, uint32_t minin, typename LabelT<LM>::W pu, uint32_t edge,
                                 uint32_t pd, uint32_t pt, uint32_t mode_bit, uint32_t& relaxed, uint32_t& knext,
-                                bool& isnew) {
+                                bool& isnew, uint32_t& lanew) {
   using W = typename LabelT<LM>::W;
   isnew = false;
   if (!(((dw >> 28) & 7u) & mode_bit)) return -1;
@@ -855,7 +867,10 @@ __device__ inline int relax_one(SearchLds<CAP, LM>& L, const Pack& K, uint32_t d
   if (tt > pt) return -1;
   const W nw = ((W)nd << K.sh) | (W)tt;  // tt <= pt <= bt < 2^sh - 1
   const int sl = lds_insert<CAP, LM, COUNT>(L, dw & kAdjDstMask, &isnew);
-  if (sl < 0) return -1;
+  if (sl < 0) {  // (only a probe chain that ran out of table: L.overflow is set)
+    lanew |= kProbeOut;
+    return -1;
+  }
   if (isnew) L.mi[sl] = SearchLds<CAP, LM>::code(minin);
   const typename LabelT<LM>::T nb = LabelT<LM>::make(nw, edge);
   const typename LabelT<LM>::T old = atomicMin(&L.lab[sl], nb);
@@ -886,7 +901,7 @@ __device__ inline int relax_one(SearchLds<CAP, LM>& L, const Pack& K, uint32_t d
 template <int CAP, bool OLD = false>
 __device__ inline int relax_sink(SearchLds<CAP, 0>& L, uint32_t* sink, const Pack& K, uint32_t dw, uint32_t len_mm,
                                  uint32_t time_ds, uint32_t minin, uint32_t pu, uint32_t pd, uint32_t pt,
-                                 uint32_t mode_bit, uint32_t& relaxed, uint32_t& knext, bool& isnew) {
+                                 uint32_t mode_bit, uint32_t& relaxed, uint32_t& knext, bool& isnew, uint32_t& lanew) {
   const bool mode_ok = (((dw >> 28) & 7u) & mode_bit) != 0u;
   relaxed += mode_ok ? 1u : 0u;
   const uint32_t nd = K.d(pu) + len_mm;  // d <= bound < 2^31, len_mm < 2^31: no wrap
@@ -916,7 +931,10 @@ __device__ inline int relax_sink(SearchLds<CAP, 0>& L, uint32_t* sink, const Pac
           break;
         }
       }
-      if (sl < 0) L.overflow = 1;
+      if (sl < 0) {
+        L.overflow = 1;
+        lanew |= kProbeOut;
+      }
     }
   }
   go = go && sl >= 0;
@@ -1055,13 +1073,43 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
 #ifdef OTR_FORCE_RETRY
   int force_round = 0;
 #endif
-  int nkeys = 0;               // keys the main relax loop added (group-uniform; L.n_keys has the rest)
+  // keys the main relax loop added (group-uniform; L.n_keys has the rest); AHEAD: all keys
+  int nkeys = 0;
+  // AHEAD (every k_route tier but the eight-search one): the rounds keep in registers
+  // what they read from LDS one wait at a time before.  nkeys: the table's key count, from
+  // L.n_keys after the pre-inserts and the resume; a CSR-tail pass counts its keys in the LDS
+  // word, which gets nkeys before the pass and gives it back after; the word is written at
+  // the end for the caller.  ovf: L.overflow, from the lanes' kProbeOut bits and the
+  // pending-list capacity test (the LDS word is still written, and read again only after a
+  // tail pass).  tkey / tlab / p0: the target slot's words and the first pending chunk of
+  // the next round, read right after the relax phase's closing barrier, so one wait covers
+  // them and the kmin reduction hides it.
+  // (not the PRED tables of k_paths: their searches are short, and the path stage measured
+  // 2 % slower with it, outside its spread)
+  constexpr bool AHEAD = !OLD && LM != 1;
+  static_assert(!AHEAD || Gr::GL <= SearchLds<CAP, LM>::PCAP, "the first pending chunk lies inside the list");
+  const int ts = tslot < 0 ? 0 : tslot;
+  int p0 = 0;
+  bool ovf = false;
+  uint32_t tkey = 0u;
+  typename LabelT<LM>::T tlab = LabelT<LM>::kInf;
+  if constexpr (AHEAD) {
+    nkeys = L.n_keys;
+    ovf = L.overflow != 0;
+    tkey = L.key[ts];
+    tlab = L.lab[ts];
+    p0 = (int)L.pend[gl];
+  }
   for (;;) {
     OTR_STAMP(t0);
     const int np = done ? 0 : npend;
     OTR_STAMP(t1);
-    const bool res =
-        done | (gl >= n_tgt) | target_resolved<CAP, LM, OLD>(L, K, tslot, tpart, gapT, pd, kmin, np == 0);
+    bool res;
+    if constexpr (AHEAD)
+      res = done | (gl >= n_tgt) |
+            target_test<LM, OLD>(tkey, LabelT<LM>::label(tlab), K, tslot, tpart, gapT, pd, kmin, np == 0);
+    else
+      res = done | (gl >= n_tgt) | target_resolved<CAP, LM, OLD>(L, K, tslot, tpart, gapT, pd, kmin, np == 0);
     done = done || Gr::mine(__ballot(!res)) == 0ull || np == 0;
     OTR_STAMP(t2);
     cyc[0] += t1 - t0;
@@ -1079,7 +1127,14 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
       const bool in = k < np;
       // unconditional reads (k < CAP; a lane past its group's list reads slot 0), so no
       // exec-mask branch around them
-      const int sl = in ? (int)L.pend[k] : 0;
+      int sl;
+      if constexpr (AHEAD) {
+        int pk = p0;  // the first chunk was read ahead; a later one is read here (wave-uniform branch)
+        if (base != 0) pk = (int)L.pend[k];
+        sl = in ? pk : 0;
+      } else {
+        sl = in ? (int)L.pend[k] : 0;
+      }
       const W lb = LabelT<LM>::label(L.lab[sl]);
       const uint32_t key = L.key[sl];
       const uint32_t d = K.d(lb);
@@ -1119,6 +1174,8 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
     // relax: lane = (work node, adjacency slot), so a round's dependent chain is a single
     // relaxation; slot 3 of a node with more than 4 out-edges also walks the CSR tail
     uint32_t tail = 0u;  // (a lane word, not a lane mask: VALU ors instead of scalar mask updates)
+    uint32_t unread = 0u;
+    uint32_t& lanew = AHEAD ? tail : unread;  // (kProbeOut goes into a spare bit of the lane word)
     const int nwx = OLD ? Gr::umax(4 * nw) : 0;
     for (int base = 0; OLD ? base < nwx : __ballot(base + gl < 4 * nw) != 0ull; base += Gr::GL) {
       const int k = base + gl;
@@ -1137,15 +1194,15 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
         if constexpr (LM == 0) {
 #ifdef OTR_NO_SINK  // (A/B build: the branching relax_one)
           psl = relax_one<CAP, LM, false, OLD>(L, K, r.x & ~kAdjMore, r.y, tt, r.z, wk.lab, 0u, pd, pt, mode_bit,
-                                               my_relaxed, knext, isnew);
+                                               my_relaxed, knext, isnew, lanew);
 #else  // (every 32-bit table has its scratch row: no run-time test of `sink`)
           psl = relax_sink<CAP, OLD>(L, sink, K, r.x & ~kAdjMore, r.y, tt, r.z, wk.lab, pd, pt, mode_bit, my_relaxed,
-                                     knext, isnew);
+                                     knext, isnew, lanew);
 #endif
         } else {
           const uint32_t e0 = LM == 1 ? g.node_row[wnode] : 0u;  // edge id = CSR row start + slot
           psl = relax_one<CAP, LM, false, OLD>(L, K, r.x & ~kAdjMore, r.y, tt, r.z, wk.lab, e0 + slot, pd, pt,
-                                               mode_bit, my_relaxed, knext, isnew);
+                                               mode_bit, my_relaxed, knext, isnew, lanew);
         }
         tail |= slot == 3 ? (r.x & kAdjMore) : 0u;
       }
@@ -1174,11 +1231,13 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
     if (SearchLds<CAP, LM>::PCAP < CAP && npend > SearchLds<CAP, LM>::PCAP) {
       if (gl == 0) L.overflow = 1;
       npend = SearchLds<CAP, LM>::PCAP;
+      ovf = true;
     }
-    if (__ballot(tail != 0u) != 0ull) {
+    if (__ballot(AHEAD ? (tail & kAdjMore) != 0u : tail != 0u) != 0ull) {
       // rare: slot 3 of a node with more than 4 out-edges walks the CSR tail; appends
       // through the shared counter
       if (gl == 0) L.n_pend = npend;
+      if (AHEAD && gl == 0) L.n_keys = nkeys;
       __syncthreads();
       for (int base = 0; OLD ? base < nwx : __ballot(base + gl < 4 * nw) != 0ull; base += Gr::GL) {
         const int k = base + gl;
@@ -1191,7 +1250,7 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
               const uint32_t tt = timed ? g.et(__builtin_ctz(mode_bit))[e] : 0u;
               bool isnew;
               const int psl = relax_one<CAP, LM, true, OLD>(L, K, pk.x | ((pk.z & 7u) << 28), pk.y, tt, pk.w, wk.lab, e,
-                                                            pd, pt, mode_bit, my_relaxed, knext, isnew);
+                                                            pd, pt, mode_bit, my_relaxed, knext, isnew, lanew);
               if (psl >= 0) {
                 const int p = atomicAdd(&L.n_pend, 1);
                 if (p < SearchLds<CAP, LM>::PCAP) L.pend[p] = (Idx)psl;
@@ -1203,31 +1262,49 @@ __device__ bool search_run(SearchLds<CAP, LM>* Ls, const DevGraph& g, const Pack
       __syncthreads();
       npend = L.n_pend;
       if (npend > SearchLds<CAP, LM>::PCAP) npend = SearchLds<CAP, LM>::PCAP;
+      if constexpr (AHEAD) {  // the tail pass counts its keys and flags its overflows in LDS
+        nkeys = L.n_keys;
+        ovf = ovf || L.overflow != 0;
+      }
     }
     __syncthreads();
+    if constexpr (AHEAD) {  // the next round's first reads, in flight during the reduction below
+      tkey = L.key[ts];
+      tlab = L.lab[ts];
+      p0 = (int)L.pend[gl];
+      ovf = ovf || Gr::mine(__ballot((tail & kProbeOut) != 0u)) != 0ull;
+    }
     OTR_STAMP(t4);
     cyc[3] += t4 - t3;
     // a finished group's kmin stays that of its last round (G = 2: the other group may run
     // on; an outgrown search's dump needs the kmin it stopped with)
     const uint32_t km = Gr::min_u32(knext);
     if (!done) kmin = km;
-    const int keys = L.n_keys + nkeys;
-    if (!done && (L.overflow || keys > kMaxKeys)) {
-      grew = !L.overflow && keys > kMaxKeys;
+    const int keys = AHEAD ? nkeys : L.n_keys + nkeys;
+    const bool over = AHEAD ? ovf : L.overflow != 0;
+    if (!done && (over || keys > kMaxKeys)) {
+      grew = !over && keys > kMaxKeys;
       done = true;
     }
 #ifdef OTR_FORCE_RETRY
     ++force_round;
     if (ROUT && !done && nd->base != nullptr && nd->stop_rounds > 0 && force_round >= nd->stop_rounds &&
-        !L.overflow) {
+        !over) {
       grew = true;
       done = true;
     }
 #endif
-    __syncthreads();
+    // (AHEAD: no lane has read L.overflow since the barrier above, so the store needs none of
+    // its own, and the reads ahead stay in flight up to the target test)
+    if constexpr (!AHEAD) __syncthreads();
     if (done && active && gl == 0 && (keys > kMaxKeys || grew)) L.overflow = 1;
   }
-  if (gl == 0) L.n_keys += nkeys;  // the table's key count, for the caller
+  // the table's key count, for the caller
+  if constexpr (AHEAD) {
+    if (gl == 0) L.n_keys = nkeys;
+  } else {
+    if (gl == 0) L.n_keys += nkeys;
+  }
   if (ROUT) *dslot = -1;
   if (ROUT && LM == 0 && __ballot(grew && active && nd->base != nullptr) != 0ull) {
     // dump the outgrown tables to claimed slots: keys in slot order, compacted by ballot

@@ -954,6 +954,16 @@ void nr_set_term(int t) { g_nr_term = t; }
  * root (one task on the GPU), the XCD order of the units. */
 #define NR_POOL_ROUNDS 4096
 static int64_t g_nr_pool[4];
+/* [0] relax iterations of the pairs if a lane covered two adjacency slots (2 nw
+ * lanes per round: max(ceil(2 nwa / 32), ceil(2 nwb / 32))); the first tier's 160-slot table
+ * (hslot<160>, linear probing, keys inserted in lane order; root, targets and relaxed heads;
+ * a search is followed until it ends a round past the load limit of 140 keys, or runs out of
+ * slots): [1] inserts,
+ * [2] inserts that leave their home slot, [3] relax iterations of 32 (node, slot) lanes (a
+ * search alone, not paired), [4] sum over them of the slowest lane's slots past home (lookups of
+ * keys in the table probe too), [5] the same with four slots read per probe (slots past home
+ * / 4), [6] searches that outgrow the table. */
+static int64_t g_nr_chain[7];
 static int g_nr_prev_n = -1, g_nr_prev[NR_POOL_ROUNDS];
 static void nr_pool_pair(const int* a, int na, const int* b, int nb) {
   const int n = na > nb ? na : nb;
@@ -962,8 +972,40 @@ static void nr_pool_pair(const int* a, int na, const int* b, int nb) {
     const int ia = (4 * x + 31) / 32, ib = (4 * y + 31) / 32;
     g_nr_pool[0] += ia > ib ? ia : ib;
     g_nr_pool[1] += (4 * (x + y) + 63) / 64;
+    const int ja = (2 * x + 31) / 32, jb = (2 * y + 31) / 32;
+    g_nr_chain[0] += ja > jb ? ja : jb;
   }
   g_nr_pool[2] += n;
+}
+/* the first tier's table of one search (otr_kernels.h hslot<160>, lds_insert) */
+#define NR_CAP 160
+static uint32_t g_nr_tab[NR_CAP];
+static int g_nr_tabn, g_nr_tab_off;
+static void nr_tab_reset(void) {
+  memset(g_nr_tab, 0xFF, sizeof(g_nr_tab));
+  g_nr_tabn = 0;
+  g_nr_tab_off = 0;
+}
+/* slots past home of the node's probe chain (inserting it if new); -1: the table is full */
+static int nr_tab_probe(uint32_t node) {
+  const uint32_t p = (uint32_t)(((uint64_t)(node & 0xFFFFFFu) * 0x9E3779u) & 0xFFFFFFFFu);
+  uint32_t h = (((p >> 8) & 0xFFFFu) * NR_CAP) >> 16;
+  for (int d = 0; d < NR_CAP; ++d) {
+    if (g_nr_tab[h] == 0xFFFFFFFFu) {
+      g_nr_tab[h] = node;
+      ++g_nr_tabn;
+      ++g_nr_chain[1];
+      if (d > 0) ++g_nr_chain[2];
+      return d;
+    }
+    if (g_nr_tab[h] == node) return d;
+    h = h + 1 == NR_CAP ? 0 : h + 1;
+  }
+  return -1;
+}
+void nr_chain_get(int64_t* out) {
+  memcpy(out, g_nr_chain, sizeof(g_nr_chain));
+  memset(g_nr_chain, 0, sizeof(g_nr_chain));
 }
 static void nr_pool_search(const int* nw, int n) {
   g_nr_pool[3]++;
@@ -1086,6 +1128,12 @@ int nr_run(const orc_graph* g, const orc_params* p, int32_t n_traces, const int6
             hq[root] = fmax(0.0, sqrt(dx * dx + dy * dy) - R);
           }
           pend[np++] = root;
+          if (mode == 0) {
+            nr_tab_reset();
+            nr_tab_probe(root);
+            for (int j = 0; j < Kb; ++j)
+              if (tv[j] != 0xFFFFFFFFu) nr_tab_probe(tv[j]);
+          }
           int64_t settled = 0, rounds = 0, stalls = 0;
           static int nwr[NR_POOL_ROUNDS];
           int nwn = 0;
@@ -1142,6 +1190,9 @@ int nr_run(const orc_graph* g, const orc_params* p, int32_t n_traces, const int6
             }
             np = kept;
             if (mode == 0 && nwn < NR_POOL_ROUNDS) nwr[nwn++] = (int)nf;
+            const int tab = mode == 0 && !g_nr_tab_off; /* the 160-slot table follows this round */
+            int it_cur = 0, it_max = 0;
+            if (tab) g_nr_chain[3] += (4 * (int64_t)nf + 31) / 32;
             for (uint32_t f = 0; f < nf; ++f) {
               const uint32_t u = nxt[f];
               flag[u] = 2;
@@ -1152,6 +1203,22 @@ int nr_run(const orc_graph* g, const orc_params* p, int32_t n_traces, const int6
                 const rkey kk = step_key(&X, L, e, -1);
                 if (!feasible(&X, kk)) continue;
                 const uint32_t v = g->edge_dst[e];
+                if (tab && !g_nr_tab_off) {
+                  const int d = nr_tab_probe(v);
+                  if (d < 0) {
+                    g_nr_tab_off = 1;
+                    ++g_nr_chain[6];
+                  } else if (e - g->node_row[u] < 4) { /* (the CSR tail's probes are not in an iteration) */
+                    const int it = (int)((4 * f + (e - g->node_row[u])) / 32);
+                    if (it != it_cur) {
+                      g_nr_chain[4] += it_max;
+                      g_nr_chain[5] += it_max / 4;
+                      it_cur = it;
+                      it_max = 0;
+                    }
+                    if (d > it_max) it_max = d;
+                  }
+                }
                 if (stamp[v] != gen) {
                   stamp[v] = gen;
                   flag[v] = 0;
@@ -1167,6 +1234,14 @@ int nr_run(const orc_graph* g, const orc_params* p, int32_t n_traces, const int6
                     pend[np++] = v;
                   }
                 }
+              }
+            }
+            if (tab) {
+              g_nr_chain[4] += it_max;
+              g_nr_chain[5] += it_max / 4;
+              if (!g_nr_tab_off && g_nr_tabn > NR_CAP * 7 / 8) { /* the load limit, between two rounds */
+                g_nr_tab_off = 1;
+                ++g_nr_chain[6];
               }
             }
           }

@@ -49,10 +49,22 @@ def main():
     out = (ctypes.c_int64 * 4)()
     L.nr_pool_get(out)
     per_group, pooled, rounds, searches = (int(x) for x in out)
+    # two adjacency slots per lane, and the probe chains of the 160-slot table
+    ch = (ctypes.c_int64 * 7)()
+    L.nr_chain_get(ch)
+    two_slot, inserts, off_home, iters, past_home, past_home4, outgrown = (int(x) for x in ch)
     print(json.dumps({'traces': args.traces, 'searches': searches, 'settled_per_search': S.settled_base / max(searches, 1),
                       'rounds_per_search': S.rounds_base / max(searches, 1), 'pair_rounds': rounds,
                       'relax_iterations_per_group_rule': per_group, 'relax_iterations_pooled': pooled,
-                      'pooled_fewer': round(1.0 - pooled / max(per_group, 1), 4)}))
+                      'pooled_fewer': round(1.0 - pooled / max(per_group, 1), 4),
+                      'relax_iterations_per_pair_round': round(per_group / max(rounds, 1), 3),
+                      'relax_iterations_two_slots': two_slot,
+                      'two_slots_fewer': round(1.0 - two_slot / max(per_group, 1), 4),
+                      'table160_inserts': inserts, 'inserts_off_home': round(off_home / max(inserts, 1), 4),
+                      'table160_relax_iterations': iters,
+                      'slowest_lane_slots_past_home': round(past_home / max(iters, 1), 4),
+                      'slowest_lane_with_4_slot_reads': round(past_home4 / max(iters, 1), 4),
+                      'searches_outgrowing_160': round(outgrown / max(searches, 1), 4)}))
 
 
 if __name__ == '__main__':
