@@ -130,6 +130,8 @@ typedef struct otr_trace_batch {
 #define OTR_BATCH_TILE_ROWS 8  /* also emit simple_reporter tile rows on device (d_rows / n_rows) */
 #define OTR_BATCH_ROUTE_WORK 16  /* count the LDS route tiers' work (route_tier_work, counters
                                     3, 4, 9, 10, 13, 14): instrumentation, ~7% of the first tier */
+#define OTR_BATCH_MATCHED_POINTS 32  /* also compute every probe's matched point (K12): read it
+                                        with otr_matched_points after the call */
 
 /* One simple_reporter tile line (simple_reporter.py:188-195) in binary form: the line
  * "id,next_id,duration,1,length,queue_length,start,end,source,MODE" of the file
@@ -244,6 +246,37 @@ int otr_match_batch(otr_matcher* m, const otr_trace_batch* in, otr_batch_result*
  * a batch of otr_max_batch_probes() probes stays below 2^32.  Host-only (no device). */
 int64_t otr_max_batch_probes(void);
 uint64_t otr_launch_max_items(int64_t n_states, int64_t n_traces, int32_t states_per_wave);
+
+/* ---- matched points: where on the road every probe ended up --------
+ * One entry per probe of the batch, in input order.  kind: OTR_POINT_STATE the probe of an
+ * HMM state that has candidates and a winner (edge / frac: the winning candidate),
+ * OTR_POINT_INTERPOLATED a probe between two such states of one sub-path (projected onto
+ * the winner route between them, never moving backwards), OTR_POINT_UNMATCHED everything
+ * else (edge 0xFFFFFFFF, state and pos_mm -1, the rest 0).  frac: fraction of the edge's
+ * length; lat / lon: the snapped coordinate; dist: metres from the probe to it; state: index
+ * of the (preceding) state in the batch's state arrays; pos_mm: position along the matched
+ * route from the start of the sub-path, whole millimetres.
+ * Refers to the matcher's last otr_match_batch, which must have set
+ * OTR_BATCH_MATCHED_POINTS (OTR_BAD_REQUEST otherwise, or when there was no batch).  The
+ * pointers are owned by the matcher and stay valid until its next batch call; the host
+ * arrays are filled only when that batch also set OTR_BATCH_COPY_OUT. */
+#define OTR_POINT_UNMATCHED 0
+#define OTR_POINT_STATE 1
+#define OTR_POINT_INTERPOLATED 2
+
+typedef struct otr_point_result {
+  int64_t n_probes;
+  float kernel_ms;             /* OTR_BATCH_TIMING: device time of K12 */
+  int32_t reserved;
+  /* host (OTR_BATCH_COPY_OUT) */
+  uint8_t* kind;  uint32_t* edge;  double* frac;  double* lat;
+  double* lon;  double* dist;  int64_t* state;  int64_t* pos_mm;
+  /* device, always */
+  uint8_t* d_kind;  uint32_t* d_edge;  double* d_frac;  double* d_lat;
+  double* d_lon;  double* d_dist;  int64_t* d_state;  int64_t* d_pos_mm;
+} otr_point_result;
+
+int otr_matched_points(otr_matcher* m, otr_point_result* out);
 
 /* simple_reporter's tile stage (simple_reporter.py:211-239) on device: sort the rows
  * by file, then in the line order of segments.sort() (:218, string order of the whole

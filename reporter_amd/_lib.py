@@ -18,6 +18,9 @@ OTR_BATCH_TIMING = 2
 OTR_BATCH_COPY_REPORTS = 4
 OTR_BATCH_TILE_ROWS = 8
 OTR_BATCH_ROUTE_WORK = 16
+OTR_BATCH_MATCHED_POINTS = 32
+OTR_BAD_REQUEST = 400
+POINT_UNMATCHED, POINT_STATE, POINT_INTERPOLATED = 0, 1, 2
 OTR_TILE_RULES_SIMPLE = 0
 OTR_TILE_RULES_STREAM = 1
 OTR_INGEST_SHARD = 0
@@ -40,7 +43,7 @@ EXPORTS = ['otr_configure', 'otr_configure_json', 'otr_matcher_new', 'otr_matche
            'otr_graph_info', 'otr_matcher_stream', 'otr_device', 'otr_report_batch', 'otr_coalesce',
            'otr_tiles_cull', 'otr_tiles_format', 'otr_ingest', 'otr_report_lists_device', 'otr_hist_reduce',
            'otr_tilehier_row', 'otr_tilehier_col', 'otr_tilehier_file', 'otr_tilehier_files', 'otr_flatten',
-           'otr_max_batch_probes', 'otr_launch_max_items', 'otr_service_stats']
+           'otr_max_batch_probes', 'otr_launch_max_items', 'otr_service_stats', 'otr_matched_points']
 
 
 class ServiceSplit(ctypes.Structure):
@@ -116,6 +119,19 @@ class BatchResult(ctypes.Structure):
                 ('route_tier_work', (ctypes.c_uint64 * 4) * 16)]
 
 
+# the per-probe arrays of otr_point_result, in the struct's order
+POINT_FIELDS = [('kind', ctypes.c_uint8, np.uint8), ('edge', ctypes.c_uint32, np.uint32),
+                ('frac', ctypes.c_double, np.float64), ('lat', ctypes.c_double, np.float64),
+                ('lon', ctypes.c_double, np.float64), ('dist', ctypes.c_double, np.float64),
+                ('state', ctypes.c_int64, np.int64), ('pos_mm', ctypes.c_int64, np.int64)]
+
+
+class PointResult(ctypes.Structure):
+    """otr_point_result (include/otr.h): every probe's matched point, host and device arrays."""
+    _fields_ = ([('n_probes', ctypes.c_int64), ('kernel_ms', ctypes.c_float), ('reserved', ctypes.c_int32)] +
+                [(k, P(ct)) for k, ct, _ in POINT_FIELDS] + [('d_' + k, ctypes.c_void_p) for k, _, _ in POINT_FIELDS])
+
+
 # otr_hist_entry (include/otr.h), 32 bytes
 HIST_ENTRY = np.dtype([('file', '<u8'), ('id', '<u8'), ('next_id', '<u8'), ('speed_bin', '<u4'), ('count', '<u4')])
 
@@ -155,6 +171,8 @@ def lib():
     L.otr_free.argtypes = [ctypes.c_void_p]
     L.otr_last_error.restype = ctypes.c_char_p
     L.otr_match_batch.argtypes = [ctypes.c_void_p, P(TraceBatch), P(BatchResult)]
+    if hasattr(L, 'otr_matched_points'):  # (an A/B build of an earlier round may lack it)
+        L.otr_matched_points.argtypes = [ctypes.c_void_p, P(PointResult)]
     L.otr_graph_info.argtypes = [P(ctypes.c_int64), P(ctypes.c_int64), P(ctypes.c_int64)]
     L.otr_matcher_stream.argtypes = [ctypes.c_void_p]
     L.otr_matcher_stream.restype = ctypes.c_void_p
@@ -249,6 +267,11 @@ def result_to_numpy(r):
     out['status'] = r.status
     out['n_overflow'] = r.n_overflow_traces
     return out
+
+
+def points_to_numpy(r):
+    """Host arrays of an otr_point_result (copies): kind, edge, frac, lat, lon, dist, state, pos_mm."""
+    return {k: _arr(getattr(r, k), int(r.n_probes), dt) for k, _, dt in POINT_FIELDS}
 
 
 def service_stats(reset=False):

@@ -371,6 +371,18 @@ int otr_match_batch(otr_matcher* m, const otr_trace_batch* in, otr_batch_result*
   return rc;
 }
 
+// the matched points of the matcher's last batch (OTR_BATCH_MATCHED_POINTS)
+int otr_matched_points(otr_matcher* m, otr_point_result* out) {
+  if (!m || !out) {
+    g_last_error = "null argument";
+    return OTR_BAD_REQUEST;
+  }
+  std::string err;
+  const int rc = m->m.matched_points(out, &err);
+  if (rc != OTR_OK) g_last_error = err;
+  return rc;
+}
+
 // simple_reporter.py:211-239 (sort + privacy cull) on device
 int otr_tiles_cull(otr_matcher* m, const otr_tile_row* rows, int64_t n, int32_t memory, int32_t privacy,
                    int32_t rules, const otr_tile_row** out, int64_t* n_out) {

@@ -96,7 +96,15 @@ struct Matcher {
   std::vector<unsigned long long> h_seg_id, h_rep_id, h_rep_next;
   std::vector<uint8_t> h_seg_internal;
   std::vector<otr_tile_row> h_tile_rows;
-  hipEvent_t ev[kEvents];  // 0..19 batch stages, 20..23 ingest, then a pair per route tier slot (otr_tiers.h)
+  // matched points (K12) of the last batch: whether it asked for them, and the result
+  // otr_matched_points hands out (device arrays in the matcher's slots, host copies here)
+  bool pts_have = false;
+  otr_point_result pts{};
+  std::vector<uint8_t> h_pt_kind;
+  std::vector<uint32_t> h_pt_edge;
+  std::vector<double> h_pt_frac, h_pt_lat, h_pt_lon, h_pt_dist;
+  std::vector<int64_t> h_pt_state, h_pt_pos;
+  hipEvent_t ev[kEvents];  // 0..19 batch stages, 20..23 ingest, a pair per route tier slot, K12's pair (otr_tiers.h)
   bool ev_init = false;
 
   template <class T>
@@ -113,6 +121,7 @@ struct Matcher {
   // entry points: a device allocation failure inside returns OTR_DEVICE_ERROR (no kernel
   // runs on a missing buffer); the *_impl bodies do the work
   int run(const otr_trace_batch* in, const ModeParams& mp, otr_batch_result* out, std::string* err);
+  int matched_points(otr_point_result* out, std::string* err) const;  // of the last run (host only)
   int tiles_cull(const otr_tile_row* rows, int64_t n, int memory, int privacy, int rules, const otr_tile_row** out,
                  int64_t* n_out, std::string* err);
   int hist_reduce(const void* in, int64_t n, int memory, int rows_in, int privacy, const otr_hist_entry** out,

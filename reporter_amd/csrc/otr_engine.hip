@@ -16,6 +16,7 @@
 #include "otr_edge1.h"
 #include "otr_ingest.h"
 #include "otr_launch.h"
+#include "otr_points.h"
 
 namespace otr {
 static_assert(kTraceWaves == 4, "grid_trace_rows (otr_launch.h) assumes 4 traces per block");
@@ -418,6 +419,7 @@ enum Slot {
   S_IN_T_OFF, S_IN_T_LAT, S_IN_T_LON, S_IN_T_TIME, S_IN_T_ACC, S_IN_T_MODE, S_IN_T_UOFF, S_IN_T_ULEN,
   S_CLEN, S_CAND_NROOT, S_FLAGGED, S_HE_FIDX, S_HE_FHEAD, S_HE_PFILE, S_HE_FFIRST, S_HE_PKEY, S_QUEUE, S_PQUEUE,
   S_E1DUMP0, S_E1DUMP1, S_TASK_DUMP, S_NDUMP0, S_NDUMP1, S_SORT_LIST, S_SORT_HIST,
+  S_PT_KIND, S_PT_EDGE, S_PT_FRAC, S_PT_LAT, S_PT_LON, S_PT_DIST, S_PT_STATE, S_PT_POS, S_PT_STATUS,
   S_NUM
 };
 
@@ -743,6 +745,8 @@ static const std::vector<int>& route_tiers() {
 }
 
 int Matcher::run(const otr_trace_batch* in, const ModeParams& mp, otr_batch_result* out, std::string* err) {
+  pts_have = false;  // (points() sets it once this batch's points exist)
+  pts = otr_point_result{};
   try {
     const int rc = run_impl(in, mp, out, err);
     opt_busy = false;
@@ -788,6 +792,8 @@ struct Batch {
   ViterbiArgs va{};
   SegArgs sa{};
   HistArgs ha{};
+  PointArgs pta{};  // K12, with OTR_BATCH_MATCHED_POINTS
+  bool want_points = false;
   size_t hist_len = 0, scan_bytes = 0;
   int64_t *trace_state_off = nullptr, *state_probe = nullptr, *trans_off = nullptr, *path_off = nullptr,
           *cap_off = nullptr;
@@ -827,9 +833,9 @@ struct Batch {
 
   // the stages, in order
   int upload(), states(), candidates(), link(), route_first(), route_retry(), route_edge(), route_global(), viterbi();
-  int paths(), paths_attempt(int64_t capacity), segments(), drain(), debug_fail(), name_failed();
+  int paths(), paths_attempt(int64_t capacity), segments(), points(), drain(), debug_fail(), name_failed();
   void fold_counters();
-  int copy_out();
+  int copy_out(), points_out();
 
   template <class X> X* need(int slot, size_t n) { return mat.need<X>(slot, n); }
   template <class X> X* want(int slot, size_t n) { return mat.want<X>(slot, n); }
@@ -883,16 +889,22 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
   }
   memset(out, 0, sizeof(*out));
   out->n_traces = in->n_traces;
-  if (in->n_traces <= 0) return OTR_OK;
+  if (in->n_traces <= 0) {
+    pts_have = (in->flags & OTR_BATCH_MATCHED_POINTS) != 0;  // (no probe, no point)
+    return OTR_OK;
+  }
   Batch c{*this, in, mp, out, err, gs.dg, stream, (in->flags & OTR_BATCH_TIMING) != 0};
   c.T = in->n_traces;
+  c.want_points = (in->flags & OTR_BATCH_MATCHED_POINTS) != 0;
   int rc;
   if ((rc = c.upload()) || (rc = c.states()) || (rc = c.candidates()) || (rc = c.link()) || (rc = c.route_first()) ||
       (rc = c.route_retry()) || (rc = c.route_edge()) || (rc = c.route_global()) || (rc = c.viterbi()) ||
-      (rc = c.paths()) || (rc = c.segments()) || (rc = c.drain()) || (rc = c.debug_fail()) || (rc = c.name_failed()))
+      (rc = c.paths()) || (rc = c.segments()) || (rc = c.points()) || (rc = c.drain()) || (rc = c.debug_fail()) ||
+      (rc = c.name_failed()))
     return rc;
   c.fold_counters();
-  return c.copy_out();
+  if ((rc = c.copy_out())) return rc;
+  return c.points_out();
 }
 
 // input upload (host batches), the batch-size check, the work counters
@@ -1908,6 +1920,93 @@ int Batch::segments() {
     out->n_rows = R;
   }
   HIPCHK(hipGetLastError());
+  return OTR_OK;
+}
+
+// ---- K12: every probe's matched point (optional), 53 B per probe
+int Batch::points() {
+  if (!want_points) return OTR_OK;
+  pta.b = b;
+  pta.trace_state_off = trace_state_off;
+  pta.state_probe = state_probe;
+  pta.cand_count = cb.count;
+  pta.cand_edge = cb.edge;
+  pta.cand_p = cb.p;
+  pta.winner = va.winner;
+  pta.brk = va.brk;
+  pta.path_off = path_off;
+  pta.path_len = path_len;
+  pta.path = sa.path;
+  pta.act = sa.act;
+  pta.pos = sa.pos;
+  pta.kind = need<uint8_t>(S_PT_KIND, N);
+  pta.edge = need<uint32_t>(S_PT_EDGE, N);
+  pta.frac = need<double>(S_PT_FRAC, N);
+  pta.lat = need<double>(S_PT_LAT, N);
+  pta.lon = need<double>(S_PT_LON, N);
+  pta.dist = need<double>(S_PT_DIST, N);
+  pta.state = need<int64_t>(S_PT_STATE, N);
+  pta.pos_mm = need<int64_t>(S_PT_POS, N);
+  if (timing) (void)hipEventRecord(mat.ev[kPointsEvent], stream);
+  k_matched_points<<<(unsigned)grid_segments(T).blocks, 64, 0, stream>>>(g, pta);
+  if (timing) (void)hipEventRecord(mat.ev[kPointsEvent + 1], stream);
+  HIPCHK(hipGetLastError());
+  return OTR_OK;
+}
+
+// after the batch drained: the traces beyond every tier lose their points, the stage's
+// time, the host copies (OTR_BATCH_COPY_OUT); the matcher remembers the result
+int Batch::points_out() {
+  int rc;
+  if (!want_points) return OTR_OK;
+  if (out->n_overflow_traces > 0) {
+    int32_t* d_status = need<int32_t>(S_PT_STATUS, T);
+    HIPCHK(hipMemcpyAsync(d_status, mat.h_trace_status.data(), 4 * (size_t)T, hipMemcpyHostToDevice, stream));
+    k_points_failed<<<(unsigned)std::min<int64_t>(T, 1024), 64, 0, stream>>>(pta, d_status);
+    HIPCHK(hipGetLastError());
+  }
+  otr_point_result& r = mat.pts;
+  r.n_probes = N;
+  if (timing) {
+    (void)hipEventElapsedTime(&r.kernel_ms, mat.ev[kPointsEvent], mat.ev[kPointsEvent + 1]);
+    (void)hipGetLastError();
+  }
+  r.d_kind = pta.kind;
+  r.d_edge = pta.edge;
+  r.d_frac = pta.frac;
+  r.d_lat = pta.lat;
+  r.d_lon = pta.lon;
+  r.d_dist = pta.dist;
+  r.d_state = pta.state;
+  r.d_pos_mm = pta.pos_mm;
+  if (in->flags & OTR_BATCH_COPY_OUT) {
+    if ((rc = dl(mat.h_pt_kind, pta.kind, N)) || (rc = dl(mat.h_pt_edge, pta.edge, N)) ||
+        (rc = dl(mat.h_pt_frac, pta.frac, N)) || (rc = dl(mat.h_pt_lat, pta.lat, N)) ||
+        (rc = dl(mat.h_pt_lon, pta.lon, N)) || (rc = dl(mat.h_pt_dist, pta.dist, N)) ||
+        (rc = dl(mat.h_pt_state, pta.state, N)) || (rc = dl(mat.h_pt_pos, pta.pos_mm, N)))
+      return rc;
+    r.kind = mat.h_pt_kind.data();
+    r.edge = mat.h_pt_edge.data();
+    r.frac = mat.h_pt_frac.data();
+    r.lat = mat.h_pt_lat.data();
+    r.lon = mat.h_pt_lon.data();
+    r.dist = mat.h_pt_dist.data();
+    r.state = mat.h_pt_state.data();
+    r.pos_mm = mat.h_pt_pos.data();
+  }
+  HIPCHK(hipStreamSynchronize(stream));
+  mat.pts_have = true;
+  return OTR_OK;
+}
+
+int Matcher::matched_points(otr_point_result* out, std::string* err) const {
+  if (!pts_have) {
+    if (err)
+      *err = "otr_matched_points: the matcher has run no batch, or its last otr_match_batch did not set "
+             "OTR_BATCH_MATCHED_POINTS";
+    return OTR_BAD_REQUEST;
+  }
+  *out = pts;
   return OTR_OK;
 }
 

@@ -10,6 +10,7 @@
 //   K6 k_paths           group/step     winner path reconstruction
 //   K7 k_segments        wave/trace     route stitch, OSMLR segments, report()
 //   K8 k_histogram       thread/trace   simple_reporter filter + hour buckets
+//   K12 k_matched_points wave/trace     every probe's matched point, opt-in (otr_points.h)
 //
 // Every decision-path expression mirrors oracle/oracle.c operation for operation
 // (DESIGN.md §3); the tests compare the two bit for bit.

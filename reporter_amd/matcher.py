@@ -147,13 +147,15 @@ class Matcher:
     def match_batch(self, traces, report_levels=(0, 1), transition_levels=(0, 1), threshold_sec=15,
                     quantisation=3600, hist_base_time=0, hist_hours=0, copy_out=True, timing=False,
                     device_arrays=None, hist_device=None, tile_rows=False, tile_rules=0, host_arrays=None,
-                    copy_reports=False, route_work=False):
+                    copy_reports=False, route_work=False, matched_points=False):
         """Match a gen.Traces-like SoA batch.  With device_arrays (dict of device
         pointers: trace_offsets, lat, lon, time, accuracy, mode) the inputs are
         already resident in HBM; host_arrays: the same as host pointers (e.g. pinned
         buffers the caller keeps alive).  copy_reports: segments, reports and stats
         come back to the host (the JSON path's copy-out).  route_work: the LDS route
-        tiers count their work (route_tier_work; instrumentation, ~7% of the first tier)."""
+        tiers count their work (route_tier_work; instrumentation, ~7% of the first tier).
+        matched_points: every probe's matched point is computed too (K12); read it with
+        matched_points() / matched_points_result() before the next batch."""
         b = _lib.TraceBatch()
         b.n_traces = int(traces.n_traces)
         arrs = device_arrays if device_arrays is not None else host_arrays
@@ -184,13 +186,35 @@ class Matcher:
         b.tile_rules = int(tile_rules)
         b.flags = (_lib.OTR_BATCH_COPY_OUT if copy_out else 0) | (_lib.OTR_BATCH_TIMING if timing else 0) | \
             (_lib.OTR_BATCH_TILE_ROWS if tile_rows else 0) | (_lib.OTR_BATCH_COPY_REPORTS if copy_reports else 0) | \
-            (_lib.OTR_BATCH_ROUTE_WORK if route_work else 0)
+            (_lib.OTR_BATCH_ROUTE_WORK if route_work else 0) | \
+            (_lib.OTR_BATCH_MATCHED_POINTS if matched_points else 0)
         r = _lib.BatchResult()
         rc = self._L.otr_match_batch(self._h, ctypes.byref(b), ctypes.byref(r))
         if rc != 0:
             raise RuntimeError('otr_match_batch failed (%d): %s' % (rc, _lib.last_error()))
         r._owner = self  # the host arrays belong to this matcher: keep it alive with the result
         return r
+
+    def matched_points_result(self):
+        """otr_matched_points: the PointResult of the last match_batch(..., matched_points=True)
+        (host pointers with copy_out, device pointers d_* always; valid until the next batch).
+        Raises RuntimeError when that batch did not ask for points."""
+        r = _lib.PointResult()
+        rc = self._L.otr_matched_points(self._h, ctypes.byref(r))
+        if rc != 0:
+            raise RuntimeError('otr_matched_points failed (%d): %s' % (rc, _lib.last_error()))
+        r._owner = self
+        return r
+
+    def matched_points(self):
+        """Every probe's matched point of the last match_batch(..., matched_points=True,
+        copy_out=True): a dict of numpy arrays (host copies) kind, edge, frac, lat, lon, dist,
+        state, pos_mm, one entry per probe in input order (include/otr.h otr_point_result)."""
+        r = self.matched_points_result()
+        if r.n_probes > 0 and not r.kind:
+            raise RuntimeError('matched_points: the batch ran without copy_out (device arrays only: '
+                               'matched_points_result())')
+        return _lib.points_to_numpy(r)
 
     def ingest(self, text, rules=0, separator='|', uuid_index=1, time_index=0, lat_index=9, lon_index=10,
                accuracy_index=5, time_format=None, inactivity=120, mode='auto', bbox=None, device_ptr=None,
