@@ -132,6 +132,9 @@ typedef struct otr_trace_batch {
                                     3, 4, 9, 10, 13, 14): instrumentation, ~7% of the first tier */
 #define OTR_BATCH_MATCHED_POINTS 32  /* also compute every probe's matched point (K12): read it
                                         with otr_matched_points after the call */
+#define OTR_BATCH_EDGE_TRAVERSALS 64  /* also compute the edge traversals of the matched route
+                                         (K13): read them with otr_edge_traversals and
+                                         otr_edge_observations after the call */
 
 /* One simple_reporter tile line (simple_reporter.py:188-195) in binary form: the line
  * "id,next_id,duration,1,length,queue_length,start,end,source,MODE" of the file
@@ -278,6 +281,40 @@ typedef struct otr_point_result {
 
 int otr_matched_points(otr_matcher* m, otr_point_result* out);
 
+/* ---- edge traversals: when the vehicle entered and left each edge --
+ * One entry per edge portion of the matched route, densely, trace by trace: trace t owns
+ * entries trace_off[t] .. trace_off[t+1]-1 (trace_off has n_traces + 1 elements), and their
+ * edges are the trace's route_edge entries without the 0xFFFFFFFF separators, in order.
+ * edge / way: the edge and its way id; seg_id: the OSMLR id of the edge's segment or
+ * OTR_NO_ID; first_state: batch index of the first state of the entry's sub-path (entries
+ * of one sub-path share it); f0 / f1: fractions of the edge's length where the traversal
+ * starts and ends (0 and 1 except at the two ends of a sub-path); s0_mm / s1_mm: the same
+ * places as positions along the sub-path's route, whole millimetres (an entry's s1 is its
+ * successor's s0; s0 == s1 occurs and is kept); t_enter / t_exit: epoch seconds, linear in
+ * route position between the states around the place, always filled.  A sub-path with one
+ * state has no entry.
+ * The entries of a trace whose trace_status is not OTR_OK are what its route and segments
+ * are: left over from a search that gave up, in bounds but without meaning; skip them.
+ * Refers to the matcher's last otr_match_batch, which must have set
+ * OTR_BATCH_EDGE_TRAVERSALS (OTR_BAD_REQUEST otherwise, or when there was no batch).  The
+ * pointers are owned by the matcher and stay valid until its next batch call; the host
+ * arrays are filled only when that batch also set OTR_BATCH_COPY_OUT (NULL otherwise).  An
+ * empty batch has n_traversals 0 and a trace_off of one zero. */
+typedef struct otr_traversal_result {
+  int64_t n_traversals;
+  int64_t n_traces;
+  float kernel_ms;             /* OTR_BATCH_TIMING: device time of K13 (count, offsets, fill) */
+  int32_t reserved;
+  /* host (OTR_BATCH_COPY_OUT) */
+  int64_t* trace_off;  uint32_t* edge;  uint32_t* way;  uint64_t* seg_id;  int64_t* first_state;
+  double* f0;  double* f1;  int64_t* s0_mm;  int64_t* s1_mm;  double* t_enter;  double* t_exit;
+  /* device, always */
+  int64_t* d_trace_off;  uint32_t* d_edge;  uint32_t* d_way;  uint64_t* d_seg_id;  int64_t* d_first_state;
+  double* d_f0;  double* d_f1;  int64_t* d_s0_mm;  int64_t* d_s1_mm;  double* d_t_enter;  double* d_t_exit;
+} otr_traversal_result;
+
+int otr_edge_traversals(otr_matcher* m, otr_traversal_result* out);
+
 /* simple_reporter's tile stage (simple_reporter.py:211-239) on device: sort the rows
  * by file, then in the line order of segments.sort() (:218, string order of the whole
  * line), and delete the (id, next_id) runs seen fewer than `privacy` times with the
@@ -312,6 +349,17 @@ typedef struct otr_hist_entry {
  * their number.  rows_in != 0: the input is n tile rows, count 1 each. */
 int otr_hist_reduce(otr_matcher* m, const void* in, int64_t n, int32_t memory, int32_t rows_in, int32_t privacy,
                     otr_hist_entry* out, int64_t out_cap, int32_t out_memory, int64_t* n_out);
+
+/* Per-edge speed entries of the edge traversals (otr_edge_traversals above), in HBM, in
+ * traversal order: one otr_hist_entry per complete traversal (f0 == 0 and f1 == 1) that
+ * took more than half a second: file = (floor(t_enter) / quantisation) << 25 | road level << 22 (tile index 0),
+ * id the edge, next_id the edge of the next traversal of the same sub-path or
+ * OTR_INVALID_SEGMENT_ID, speed_bin from (s1_mm - s0_mm) and t_exit - t_enter in 20 km/h
+ * steps (7 at most), count 1.  quantisation <= 0 means 3600.  *d_entries is owned by the
+ * matcher until its next batch or otr_edge_observations call and can be handed to
+ * otr_hist_reduce(m, *d_entries, *n, OTR_MEM_DEVICE, 0, ...) as it is.  Same errors as
+ * otr_edge_traversals. */
+int otr_edge_observations(otr_matcher* m, int32_t quantisation, otr_hist_entry** d_entries, int64_t* n);
 
 /* The CSV lines of n (host) rows in order.  OTR_TILE_RULES_SIMPLE: "id,next,duration,1,
  * length,queue,start,end,source,MODE\n" each (simple_reporter.py:188-195).

@@ -19,6 +19,7 @@ OTR_BATCH_COPY_REPORTS = 4
 OTR_BATCH_TILE_ROWS = 8
 OTR_BATCH_ROUTE_WORK = 16
 OTR_BATCH_MATCHED_POINTS = 32
+OTR_BATCH_EDGE_TRAVERSALS = 64
 OTR_BAD_REQUEST = 400
 POINT_UNMATCHED, POINT_STATE, POINT_INTERPOLATED = 0, 1, 2
 OTR_TILE_RULES_SIMPLE = 0
@@ -43,7 +44,8 @@ EXPORTS = ['otr_configure', 'otr_configure_json', 'otr_matcher_new', 'otr_matche
            'otr_graph_info', 'otr_matcher_stream', 'otr_device', 'otr_report_batch', 'otr_coalesce',
            'otr_tiles_cull', 'otr_tiles_format', 'otr_ingest', 'otr_report_lists_device', 'otr_hist_reduce',
            'otr_tilehier_row', 'otr_tilehier_col', 'otr_tilehier_file', 'otr_tilehier_files', 'otr_flatten',
-           'otr_max_batch_probes', 'otr_launch_max_items', 'otr_service_stats', 'otr_matched_points']
+           'otr_max_batch_probes', 'otr_launch_max_items', 'otr_service_stats', 'otr_matched_points',
+           'otr_edge_traversals', 'otr_edge_observations']
 
 
 class ServiceSplit(ctypes.Structure):
@@ -132,6 +134,24 @@ class PointResult(ctypes.Structure):
                 [(k, P(ct)) for k, ct, _ in POINT_FIELDS] + [('d_' + k, ctypes.c_void_p) for k, _, _ in POINT_FIELDS])
 
 
+# the arrays of otr_traversal_result, in the struct's order (trace_off has n_traces + 1 elements,
+# the others n_traversals)
+TRAVERSAL_FIELDS = [('trace_off', ctypes.c_int64, np.int64), ('edge', ctypes.c_uint32, np.uint32),
+                    ('way', ctypes.c_uint32, np.uint32), ('seg_id', ctypes.c_uint64, np.uint64),
+                    ('first_state', ctypes.c_int64, np.int64), ('f0', ctypes.c_double, np.float64),
+                    ('f1', ctypes.c_double, np.float64), ('s0_mm', ctypes.c_int64, np.int64),
+                    ('s1_mm', ctypes.c_int64, np.int64), ('t_enter', ctypes.c_double, np.float64),
+                    ('t_exit', ctypes.c_double, np.float64)]
+
+
+class TraversalResult(ctypes.Structure):
+    """otr_traversal_result (include/otr.h): the edge traversals of the matched routes, host and
+    device arrays."""
+    _fields_ = ([('n_traversals', ctypes.c_int64), ('n_traces', ctypes.c_int64), ('kernel_ms', ctypes.c_float),
+                 ('reserved', ctypes.c_int32)] + [(k, P(ct)) for k, ct, _ in TRAVERSAL_FIELDS] +
+                [('d_' + k, ctypes.c_void_p) for k, _, _ in TRAVERSAL_FIELDS])
+
+
 # otr_hist_entry (include/otr.h), 32 bytes
 HIST_ENTRY = np.dtype([('file', '<u8'), ('id', '<u8'), ('next_id', '<u8'), ('speed_bin', '<u4'), ('count', '<u4')])
 
@@ -173,6 +193,9 @@ def lib():
     L.otr_match_batch.argtypes = [ctypes.c_void_p, P(TraceBatch), P(BatchResult)]
     if hasattr(L, 'otr_matched_points'):  # (an A/B build of an earlier round may lack it)
         L.otr_matched_points.argtypes = [ctypes.c_void_p, P(PointResult)]
+    if hasattr(L, 'otr_edge_traversals'):
+        L.otr_edge_traversals.argtypes = [ctypes.c_void_p, P(TraversalResult)]
+        L.otr_edge_observations.argtypes = [ctypes.c_void_p, ctypes.c_int32, P(ctypes.c_void_p), P(ctypes.c_int64)]
     L.otr_graph_info.argtypes = [P(ctypes.c_int64), P(ctypes.c_int64), P(ctypes.c_int64)]
     L.otr_matcher_stream.argtypes = [ctypes.c_void_p]
     L.otr_matcher_stream.restype = ctypes.c_void_p
@@ -272,6 +295,13 @@ def result_to_numpy(r):
 def points_to_numpy(r):
     """Host arrays of an otr_point_result (copies): kind, edge, frac, lat, lon, dist, state, pos_mm."""
     return {k: _arr(getattr(r, k), int(r.n_probes), dt) for k, _, dt in POINT_FIELDS}
+
+
+def traversals_to_numpy(r):
+    """Host arrays of an otr_traversal_result (copies): trace_off, edge, way, seg_id, first_state,
+    f0, f1, s0_mm, s1_mm, t_enter, t_exit."""
+    return {k: _arr(getattr(r, k), int(r.n_traces) + 1 if k == 'trace_off' else int(r.n_traversals), dt)
+            for k, _, dt in TRAVERSAL_FIELDS}
 
 
 def service_stats(reset=False):

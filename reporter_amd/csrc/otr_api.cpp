@@ -383,6 +383,30 @@ int otr_matched_points(otr_matcher* m, otr_point_result* out) {
   return rc;
 }
 
+// the edge traversals of the matcher's last batch (OTR_BATCH_EDGE_TRAVERSALS)
+int otr_edge_traversals(otr_matcher* m, otr_traversal_result* out) {
+  if (!m || !out) {
+    g_last_error = "null argument";
+    return OTR_BAD_REQUEST;
+  }
+  std::string err;
+  const int rc = m->m.edge_traversals(out, &err);
+  if (rc != OTR_OK) g_last_error = err;
+  return rc;
+}
+
+// their per-edge speed entries, in HBM
+int otr_edge_observations(otr_matcher* m, int32_t quantisation, otr_hist_entry** d_entries, int64_t* n) {
+  if (!m || !d_entries || !n) {
+    g_last_error = "null argument";
+    return OTR_BAD_REQUEST;
+  }
+  std::string err;
+  const int rc = m->m.edge_observations(quantisation, d_entries, n, &err);
+  if (rc != OTR_OK) g_last_error = err;
+  return rc;
+}
+
 // simple_reporter.py:211-239 (sort + privacy cull) on device
 int otr_tiles_cull(otr_matcher* m, const otr_tile_row* rows, int64_t n, int32_t memory, int32_t privacy,
                    int32_t rules, const otr_tile_row** out, int64_t* n_out) {

@@ -104,7 +104,15 @@ struct Matcher {
   std::vector<uint32_t> h_pt_edge;
   std::vector<double> h_pt_frac, h_pt_lat, h_pt_lon, h_pt_dist;
   std::vector<int64_t> h_pt_state, h_pt_pos;
-  hipEvent_t ev[kEvents];  // 0..19 batch stages, 20..23 ingest, a pair per route tier slot, K12's pair (otr_tiers.h)
+  // edge traversals (K13) of the last batch, kept the same way for otr_edge_traversals and
+  // otr_edge_observations
+  bool trv_have = false;
+  otr_traversal_result trv{};
+  std::vector<int64_t> h_tr_off, h_tr_first, h_tr_s0, h_tr_s1;
+  std::vector<uint32_t> h_tr_edge, h_tr_way;
+  std::vector<uint64_t> h_tr_seg;
+  std::vector<double> h_tr_f0, h_tr_f1, h_tr_t0, h_tr_t1;
+  hipEvent_t ev[kEvents];  // 0..19 batch stages, 20..23 ingest, a pair per route tier slot, K12's and K13's pairs (otr_tiers.h)
   bool ev_init = false;
 
   template <class T>
@@ -122,6 +130,8 @@ struct Matcher {
   // runs on a missing buffer); the *_impl bodies do the work
   int run(const otr_trace_batch* in, const ModeParams& mp, otr_batch_result* out, std::string* err);
   int matched_points(otr_point_result* out, std::string* err) const;  // of the last run (host only)
+  int edge_traversals(otr_traversal_result* out, std::string* err) const;  // of the last run (host only)
+  int edge_observations(int quantisation, otr_hist_entry** d_entries, int64_t* n, std::string* err);
   int tiles_cull(const otr_tile_row* rows, int64_t n, int memory, int privacy, int rules, const otr_tile_row** out,
                  int64_t* n_out, std::string* err);
   int hist_reduce(const void* in, int64_t n, int memory, int rows_in, int privacy, const otr_hist_entry** out,
@@ -129,6 +139,7 @@ struct Matcher {
   int run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch_result* out, std::string* err);
   int tiles_cull_impl(const otr_tile_row* rows, int64_t n, int memory, int privacy, int rules,
                       const otr_tile_row** out, int64_t* n_out, std::string* err);
+  int edge_observations_impl(int quantisation, otr_hist_entry** d_entries, int64_t* n, std::string* err);
   int hist_reduce_impl(const void* in, int64_t n, int memory, int rows_in, int privacy, const otr_hist_entry** out,
                        int64_t* n_out, std::string* err);
   int ingest_impl(const char* text, int64_t len, int memory, const otr_ingest_format* fmt, otr_ingest_result* out,

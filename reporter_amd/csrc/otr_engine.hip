@@ -17,6 +17,7 @@
 #include "otr_ingest.h"
 #include "otr_launch.h"
 #include "otr_points.h"
+#include "otr_traversals.h"
 
 namespace otr {
 static_assert(kTraceWaves == 4, "grid_trace_rows (otr_launch.h) assumes 4 traces per block");
@@ -420,6 +421,8 @@ enum Slot {
   S_CLEN, S_CAND_NROOT, S_FLAGGED, S_HE_FIDX, S_HE_FHEAD, S_HE_PFILE, S_HE_FFIRST, S_HE_PKEY, S_QUEUE, S_PQUEUE,
   S_E1DUMP0, S_E1DUMP1, S_TASK_DUMP, S_NDUMP0, S_NDUMP1, S_SORT_LIST, S_SORT_HIST,
   S_PT_KIND, S_PT_EDGE, S_PT_FRAC, S_PT_LAT, S_PT_LON, S_PT_DIST, S_PT_STATE, S_PT_POS, S_PT_STATUS,
+  S_TR_CNT, S_TR_OFF, S_TR_EDGE, S_TR_WAY, S_TR_SEG, S_TR_FIRST, S_TR_F0, S_TR_F1, S_TR_S0, S_TR_S1, S_TR_T0, S_TR_T1,
+  S_TR_KEEP, S_TR_KEEP_OFF, S_TR_ENTRIES, S_TR_TMP,
   S_NUM
 };
 
@@ -747,6 +750,8 @@ static const std::vector<int>& route_tiers() {
 int Matcher::run(const otr_trace_batch* in, const ModeParams& mp, otr_batch_result* out, std::string* err) {
   pts_have = false;  // (points() sets it once this batch's points exist)
   pts = otr_point_result{};
+  trv_have = false;
+  trv = otr_traversal_result{};
   try {
     const int rc = run_impl(in, mp, out, err);
     opt_busy = false;
@@ -794,6 +799,9 @@ struct Batch {
   HistArgs ha{};
   PointArgs pta{};  // K12, with OTR_BATCH_MATCHED_POINTS
   bool want_points = false;
+  TravArgs tva{};  // K13, with OTR_BATCH_EDGE_TRAVERSALS
+  bool want_traversals = false;
+  int64_t n_trav = 0;
   size_t hist_len = 0, scan_bytes = 0;
   int64_t *trace_state_off = nullptr, *state_probe = nullptr, *trans_off = nullptr, *path_off = nullptr,
           *cap_off = nullptr;
@@ -833,9 +841,10 @@ struct Batch {
 
   // the stages, in order
   int upload(), states(), candidates(), link(), route_first(), route_retry(), route_edge(), route_global(), viterbi();
-  int paths(), paths_attempt(int64_t capacity), segments(), points(), drain(), debug_fail(), name_failed();
+  int paths(), paths_attempt(int64_t capacity), segments(), points(), traversals(), drain(), debug_fail(),
+      name_failed();
   void fold_counters();
-  int copy_out(), points_out();
+  int copy_out(), points_out(), traversals_out();
 
   template <class X> X* need(int slot, size_t n) { return mat.need<X>(slot, n); }
   template <class X> X* want(int slot, size_t n) { return mat.want<X>(slot, n); }
@@ -891,20 +900,31 @@ int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch
   out->n_traces = in->n_traces;
   if (in->n_traces <= 0) {
     pts_have = (in->flags & OTR_BATCH_MATCHED_POINTS) != 0;  // (no probe, no point)
+    if (in->flags & OTR_BATCH_EDGE_TRAVERSALS) {  // (no trace, no traversal: a trace_off of one zero)
+      trv.d_trace_off = need<int64_t>(S_TR_OFF, 1);
+      HIPCHK(hipMemsetAsync(trv.d_trace_off, 0, 8, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      if (in->flags & OTR_BATCH_COPY_OUT) {
+        h_tr_off.assign(1, 0);
+        trv.trace_off = h_tr_off.data();
+      }
+      trv_have = true;
+    }
     return OTR_OK;
   }
   Batch c{*this, in, mp, out, err, gs.dg, stream, (in->flags & OTR_BATCH_TIMING) != 0};
   c.T = in->n_traces;
   c.want_points = (in->flags & OTR_BATCH_MATCHED_POINTS) != 0;
+  c.want_traversals = (in->flags & OTR_BATCH_EDGE_TRAVERSALS) != 0;
   int rc;
   if ((rc = c.upload()) || (rc = c.states()) || (rc = c.candidates()) || (rc = c.link()) || (rc = c.route_first()) ||
       (rc = c.route_retry()) || (rc = c.route_edge()) || (rc = c.route_global()) || (rc = c.viterbi()) ||
-      (rc = c.paths()) || (rc = c.segments()) || (rc = c.points()) || (rc = c.drain()) || (rc = c.debug_fail()) ||
-      (rc = c.name_failed()))
+      (rc = c.paths()) || (rc = c.segments()) || (rc = c.points()) || (rc = c.traversals()) || (rc = c.drain()) ||
+      (rc = c.debug_fail()) || (rc = c.name_failed()))
     return rc;
   c.fold_counters();
-  if ((rc = c.copy_out())) return rc;
-  return c.points_out();
+  if ((rc = c.copy_out()) || (rc = c.points_out())) return rc;
+  return c.traversals_out();
 }
 
 // input upload (host batches), the batch-size check, the work counters
@@ -2007,6 +2027,175 @@ int Matcher::matched_points(otr_point_result* out, std::string* err) const {
     return OTR_BAD_REQUEST;
   }
   *out = pts;
+  return OTR_OK;
+}
+
+// ---- K13: the edge traversals of the matched route (optional), 76 B
+// per traversal: count per trace, offsets (one more host read, for the arrays' size), fill
+int Batch::traversals() {
+  int rc;
+  if (!want_traversals) return OTR_OK;
+  tva.b = b;
+  tva.trace_state_off = trace_state_off;
+  tva.state_probe = state_probe;
+  tva.cand_count = cb.count;
+  tva.cand_edge = cb.edge;
+  tva.cand_p = cb.p;
+  tva.winner = va.winner;
+  tva.act = sa.act;
+  tva.pos = sa.pos;
+  tva.subb = sa.subb;
+  tva.por_e = sa.por_e;
+  tva.por_s0 = sa.por_s0;
+  tva.por_s1 = sa.por_s1;
+  tva.por_sa = sa.por_sa;
+  tva.cap_off = cap_off;
+  tva.route = sa.route;
+  tva.route_n = sa.route_n;
+  tva.count = need<int64_t>(S_TR_CNT, T);
+  int64_t* off = need<int64_t>(S_TR_OFF, T + 1);
+  tva.trav_off = off;
+  if (timing) (void)hipEventRecord(mat.ev[kTravEvent], stream);
+  k_trav_count<<<(unsigned)grid_segments(T).blocks, 64, 0, stream>>>(tva);
+  if ((rc = scan(tva.count, off, T))) return rc;
+  if ((rc = read_i64(off + T, &n_trav))) return rc;
+  const size_t n = (size_t)n_trav;
+  tva.edge = need<uint32_t>(S_TR_EDGE, n);
+  tva.way = need<uint32_t>(S_TR_WAY, n);
+  tva.seg_id = need<unsigned long long>(S_TR_SEG, n);
+  tva.first_state = need<int64_t>(S_TR_FIRST, n);
+  tva.f0 = need<double>(S_TR_F0, n);
+  tva.f1 = need<double>(S_TR_F1, n);
+  tva.s0_mm = need<int64_t>(S_TR_S0, n);
+  tva.s1_mm = need<int64_t>(S_TR_S1, n);
+  tva.t_enter = need<double>(S_TR_T0, n);
+  tva.t_exit = need<double>(S_TR_T1, n);
+  if (n_trav > 0) k_edge_traversals<<<(unsigned)grid_segments(T).blocks, 64, 0, stream>>>(g, tva);
+  if (timing) (void)hipEventRecord(mat.ev[kTravEvent + 1], stream);
+  HIPCHK(hipGetLastError());
+  return OTR_OK;
+}
+
+// after the batch drained: the stage's time, the host copies (OTR_BATCH_COPY_OUT); the
+// matcher remembers the result
+int Batch::traversals_out() {
+  int rc;
+  if (!want_traversals) return OTR_OK;
+  otr_traversal_result& r = mat.trv;
+  r.n_traversals = n_trav;
+  r.n_traces = T;
+  if (timing) {
+    (void)hipEventElapsedTime(&r.kernel_ms, mat.ev[kTravEvent], mat.ev[kTravEvent + 1]);
+    (void)hipGetLastError();
+  }
+  r.d_trace_off = const_cast<int64_t*>(tva.trav_off);
+  r.d_edge = tva.edge;
+  r.d_way = tva.way;
+  r.d_seg_id = reinterpret_cast<uint64_t*>(tva.seg_id);
+  r.d_first_state = tva.first_state;
+  r.d_f0 = tva.f0;
+  r.d_f1 = tva.f1;
+  r.d_s0_mm = tva.s0_mm;
+  r.d_s1_mm = tva.s1_mm;
+  r.d_t_enter = tva.t_enter;
+  r.d_t_exit = tva.t_exit;
+  if (in->flags & OTR_BATCH_COPY_OUT) {
+    const size_t n = (size_t)n_trav;
+    if ((rc = dl(mat.h_tr_off, tva.trav_off, (size_t)T + 1)) || (rc = dl(mat.h_tr_edge, tva.edge, n)) ||
+        (rc = dl(mat.h_tr_way, tva.way, n)) || (rc = dl(mat.h_tr_seg, tva.seg_id, n)) ||
+        (rc = dl(mat.h_tr_first, tva.first_state, n)) || (rc = dl(mat.h_tr_f0, tva.f0, n)) ||
+        (rc = dl(mat.h_tr_f1, tva.f1, n)) || (rc = dl(mat.h_tr_s0, tva.s0_mm, n)) ||
+        (rc = dl(mat.h_tr_s1, tva.s1_mm, n)) || (rc = dl(mat.h_tr_t0, tva.t_enter, n)) ||
+        (rc = dl(mat.h_tr_t1, tva.t_exit, n)))
+      return rc;
+    r.trace_off = mat.h_tr_off.data();
+    r.edge = mat.h_tr_edge.data();
+    r.way = mat.h_tr_way.data();
+    r.seg_id = mat.h_tr_seg.data();
+    r.first_state = mat.h_tr_first.data();
+    r.f0 = mat.h_tr_f0.data();
+    r.f1 = mat.h_tr_f1.data();
+    r.s0_mm = mat.h_tr_s0.data();
+    r.s1_mm = mat.h_tr_s1.data();
+    r.t_enter = mat.h_tr_t0.data();
+    r.t_exit = mat.h_tr_t1.data();
+  }
+  HIPCHK(hipStreamSynchronize(stream));
+  mat.trv_have = true;
+  return OTR_OK;
+}
+
+static const char kNoTraversals[] =
+    ": the matcher has run no batch, or its last otr_match_batch did not set OTR_BATCH_EDGE_TRAVERSALS";
+
+int Matcher::edge_traversals(otr_traversal_result* out, std::string* err) const {
+  if (!trv_have) {
+    if (err) *err = std::string("otr_edge_traversals") + kNoTraversals;
+    return OTR_BAD_REQUEST;
+  }
+  *out = trv;
+  return OTR_OK;
+}
+
+int Matcher::edge_observations(int quantisation, otr_hist_entry** d_entries, int64_t* n, std::string* err) {
+  try {
+    return edge_observations_impl(quantisation, d_entries, n, err);
+  } catch (const DeviceOom& o) {
+    return oom_error(stream, o, err);
+  }
+}
+
+// the speed entries of the last batch's complete traversals: keep flags, their scan, fill
+int Matcher::edge_observations_impl(int quantisation, otr_hist_entry** d_entries, int64_t* n, std::string* err) {
+  *d_entries = nullptr;
+  *n = 0;
+  if (!trv_have) {
+    if (err) *err = std::string("otr_edge_observations") + kNoTraversals;
+    return OTR_BAD_REQUEST;
+  }
+  const int64_t nt = trv.n_traversals;
+  if (nt <= 0) return OTR_OK;
+  if (nt >= (int64_t)INT32_MAX) {
+    if (err) *err = "too many traversals for one call";
+    return OTR_BAD_REQUEST;
+  }
+  GraphState& gs = graph_state();
+  std::shared_lock<std::shared_mutex> graph_lock(gs.mu);
+  HIPCHK(hipSetDevice(gs.device));
+  TravObsArgs oa{};
+  oa.n = nt;
+  oa.edge = trv.d_edge;
+  oa.first_state = trv.d_first_state;
+  oa.f0 = trv.d_f0;
+  oa.f1 = trv.d_f1;
+  oa.s0_mm = trv.d_s0_mm;
+  oa.s1_mm = trv.d_s1_mm;
+  oa.t_enter = trv.d_t_enter;
+  oa.t_exit = trv.d_t_exit;
+  oa.quantisation = quantisation > 0 ? quantisation : 3600;
+  oa.keep = need<int64_t>(S_TR_KEEP, (size_t)nt);
+  int64_t* keep_off = need<int64_t>(S_TR_KEEP_OFF, (size_t)nt + 1);
+  oa.keep_off = keep_off;
+  const unsigned grid = (unsigned)std::min<int64_t>(kTravObsGrid, (nt + 255) / 256);
+  k_trav_obs_keep<<<grid, 256, 0, stream>>>(oa);
+  HIPCHK(hipMemsetAsync(keep_off, 0, 8, stream));
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, oa.keep, keep_off + 1, (int)nt, stream));
+  void* tmp = need<char>(S_TR_TMP, tb);
+  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, oa.keep, keep_off + 1, (int)nt, stream));
+  int64_t ne = 0;
+  HIPCHK(hipMemcpyAsync(&ne, keep_off + nt, 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (ne < 0 || ne > nt) {
+    if (err) *err = "edge observations: the keep scan failed";
+    return OTR_DEVICE_ERROR;
+  }
+  oa.entries = need<otr_hist_entry>(S_TR_ENTRIES, (size_t)ne);
+  if (ne > 0) k_trav_obs_fill<<<grid, 256, 0, stream>>>(gs.dg, oa);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(stream));
+  *d_entries = oa.entries;
+  *n = ne;
   return OTR_OK;
 }
 

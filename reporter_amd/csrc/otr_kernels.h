@@ -11,6 +11,7 @@
 //   K7 k_segments        wave/trace     route stitch, OSMLR segments, report()
 //   K8 k_histogram       thread/trace   simple_reporter filter + hour buckets
 //   K12 k_matched_points wave/trace     every probe's matched point, opt-in (otr_points.h)
+//   K13 k_edge_traversals wave/trace    the route's edge traversals with times, opt-in (otr_traversals.h)
 //
 // Every decision-path expression mirrors oracle/oracle.c operation for operation
 // (DESIGN.md §3); the tests compare the two bit for bit.

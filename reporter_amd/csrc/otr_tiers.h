@@ -22,8 +22,9 @@ constexpr int kQueueWords = 16 * 8; // 8 counters per queue, 128 B apart
 constexpr int kDumpLineWords = 16;  // a dump-slot counter has a 128 B line of a queue to itself
 constexpr int kNodeTiers = 5;       // node retry tiers at most (OTR_TIERS: four and the 4096-slot one)
 constexpr int kStageEvents = 24;    // events 0..19 the batch stages, 20..23 ingest
-constexpr int kEvents = 56;         // Matcher::ev
+constexpr int kEvents = 58;         // Matcher::ev
 constexpr int kPointsEvent = 54;    // 54, 55: the matched-points stage (K12), after the route tier slots' pairs
+constexpr int kTravEvent = 56;      // 56, 57: the edge-traversals stage (K13)
 
 // the words of the device-side list counters (one allocation, cleared per batch)
 enum CntWord {
@@ -183,6 +184,7 @@ static_assert(kRouteSlots <= kRouteSlotsAbi, "route tier slots: otr_batch_result
 static_assert(SLOT_NODE + kNodeTiers == SLOT_GLOBAL && kEdgeSlots[2] == SLOT_EDGE_1024, "slot ranges");
 static_assert(route_event(kRouteSlots - 1) + 1 < kEvents, "every slot's event pair lies inside Matcher::ev");
 static_assert(route_event(kRouteSlots - 1) + 1 < kPointsEvent && kPointsEvent + 1 < kEvents, "K12's event pair");
+static_assert(kTravEvent == kPointsEvent + 2 && kTravEvent + 1 < kEvents, "K13's event pair");
 static_assert(tier_check::in_range(), "banks < kBanks, list words < 32, queues and dump lines < 16 queues");
 static_assert(tier_check::distinct(), "banks, list words, queues and dump lines are distinct among the tiers");
 

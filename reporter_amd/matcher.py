@@ -147,7 +147,7 @@ class Matcher:
     def match_batch(self, traces, report_levels=(0, 1), transition_levels=(0, 1), threshold_sec=15,
                     quantisation=3600, hist_base_time=0, hist_hours=0, copy_out=True, timing=False,
                     device_arrays=None, hist_device=None, tile_rows=False, tile_rules=0, host_arrays=None,
-                    copy_reports=False, route_work=False, matched_points=False):
+                    copy_reports=False, route_work=False, matched_points=False, edge_traversals=False):
         """Match a gen.Traces-like SoA batch.  With device_arrays (dict of device
         pointers: trace_offsets, lat, lon, time, accuracy, mode) the inputs are
         already resident in HBM; host_arrays: the same as host pointers (e.g. pinned
@@ -155,7 +155,9 @@ class Matcher:
         come back to the host (the JSON path's copy-out).  route_work: the LDS route
         tiers count their work (route_tier_work; instrumentation, ~7% of the first tier).
         matched_points: every probe's matched point is computed too (K12); read it with
-        matched_points() / matched_points_result() before the next batch."""
+        matched_points() / matched_points_result() before the next batch.  edge_traversals:
+        when the vehicle entered and left each edge of the matched route is computed too (K13);
+        read it with edge_traversals() / edge_traversals_result() / edge_observations()."""
         b = _lib.TraceBatch()
         b.n_traces = int(traces.n_traces)
         arrs = device_arrays if device_arrays is not None else host_arrays
@@ -187,7 +189,8 @@ class Matcher:
         b.flags = (_lib.OTR_BATCH_COPY_OUT if copy_out else 0) | (_lib.OTR_BATCH_TIMING if timing else 0) | \
             (_lib.OTR_BATCH_TILE_ROWS if tile_rows else 0) | (_lib.OTR_BATCH_COPY_REPORTS if copy_reports else 0) | \
             (_lib.OTR_BATCH_ROUTE_WORK if route_work else 0) | \
-            (_lib.OTR_BATCH_MATCHED_POINTS if matched_points else 0)
+            (_lib.OTR_BATCH_MATCHED_POINTS if matched_points else 0) | \
+            (_lib.OTR_BATCH_EDGE_TRAVERSALS if edge_traversals else 0)
         r = _lib.BatchResult()
         rc = self._L.otr_match_batch(self._h, ctypes.byref(b), ctypes.byref(r))
         if rc != 0:
@@ -215,6 +218,37 @@ class Matcher:
             raise RuntimeError('matched_points: the batch ran without copy_out (device arrays only: '
                                'matched_points_result())')
         return _lib.points_to_numpy(r)
+
+    def edge_traversals_result(self):
+        """otr_edge_traversals: the TraversalResult of the last match_batch(..., edge_traversals=True)
+        (host pointers with copy_out, device pointers d_* always; valid until the next batch).
+        Raises RuntimeError when that batch did not ask for traversals."""
+        r = _lib.TraversalResult()
+        rc = self._L.otr_edge_traversals(self._h, ctypes.byref(r))
+        if rc != 0:
+            raise RuntimeError('otr_edge_traversals failed (%d): %s' % (rc, _lib.last_error()))
+        r._owner = self
+        return r
+
+    def edge_traversals(self):
+        """The edge traversals of the last match_batch(..., edge_traversals=True, copy_out=True): a
+        dict of numpy arrays (host copies) trace_off (n_traces + 1), edge, way, seg_id, first_state,
+        f0, f1, s0_mm, s1_mm, t_enter, t_exit (include/otr.h otr_traversal_result)."""
+        r = self.edge_traversals_result()
+        if not r.trace_off:
+            raise RuntimeError('edge_traversals: the batch ran without copy_out (device arrays only: '
+                               'edge_traversals_result())')
+        return _lib.traversals_to_numpy(r)
+
+    def edge_observations(self, quantisation=3600):
+        """otr_edge_observations: (device pointer, n) of the per-edge speed entries (otr_hist_entry,
+        _lib.HIST_ENTRY) of the last batch's complete traversals, in traversal order; matcher-owned
+        until the next batch or call.  Feed them to simple_reporter.hist_reduce(m, ptr, n, ...)."""
+        ptr, n = ctypes.c_void_p(), ctypes.c_int64()
+        rc = self._L.otr_edge_observations(self._h, int(quantisation), ctypes.byref(ptr), ctypes.byref(n))
+        if rc != 0:
+            raise RuntimeError('otr_edge_observations failed (%d): %s' % (rc, _lib.last_error()))
+        return int(ptr.value or 0), int(n.value)
 
     def ingest(self, text, rules=0, separator='|', uuid_index=1, time_index=0, lat_index=9, lon_index=10,
                accuracy_index=5, time_format=None, inactivity=120, mode='auto', bbox=None, device_ptr=None,
