@@ -120,7 +120,8 @@ __device__ inline bool project_edge(const DevGraph& g, uint4 rec, uint4 pts01, u
   const uint32_t k0 = rec.y, k1 = rec.z;
   // the first kPre shape points travel in the cell record itself (DevGraph::cell_rec:
   // no dependent shape load for edges of up to 4 points — every edge of the synthetic
-  // graphs); longer polylines continue point by point from shape_ll
+  // graphs); longer polylines continue point by point from shape_ll (the continuation is
+  // covered by the `poly` edges of tests/candidates_ref.py: 5 to 70 points)
   constexpr uint32_t kPre = 4;
   const int2 pre0 = make_int2((int)pts01.x, (int)pts01.y);
   int2 q1 = make_int2((int)pts01.z, (int)pts01.w);
