@@ -484,6 +484,114 @@ typedef struct otr_ingest_result {
 int otr_ingest(otr_matcher* m, const char* text, int64_t len, int32_t memory, const otr_ingest_format* fmt,
                otr_ingest_result* out);
 
+/* ---- session store: the streaming reporter's per-key state ----
+ * What BatchingProcessor.java:58-106 and Batch.java:43-90 keep per uuid, in HBM: a session
+ * of points per 64-bit key, the report gate (max separation from the first point, point
+ * count, elapsed time), the trim by the report's shape_used and the eviction of sessions
+ * that went quiet.  One store per matcher.  max_points bounds a session (the reference's
+ * lists are unbounded): a session that reaches it after an append is reported as at
+ * eviction (n >= 2 and a non-negative elapsed time; counted in n_forced) or, failing that,
+ * cleared (n_dropped).  Keys have no String order: evictions go by ascending key value. */
+typedef struct otr_session_config {
+  int32_t max_sessions;        /* live sessions at a time; the key table has twice as many entries */
+  int32_t max_points;          /* per session, >= 2 */
+  float report_dist;           /* metres, 500 (compared with the float max separation) */
+  int32_t report_count;        /* points, 10 */
+  int64_t report_time;         /* 60, units of time */
+  int64_t session_gap;         /* 60000, units of timestamp */
+  int32_t mode;                /* 0 auto, 1 bicycle, 2 pedestrian: every report's mode */
+  uint32_t report_levels;      /* bit masks as in otr_trace_batch */
+  uint32_t transition_levels;
+  int32_t threshold_sec;
+  int64_t batch_probes;        /* most probes per device batch of a round; <= 0: otr_max_batch_probes() */
+} otr_session_config;
+
+/* Keyed points in arrival order, host or device memory.  Key OTR_NO_ID is refused. */
+typedef struct otr_session_points {
+  int64_t n;
+  int32_t memory;              /* OTR_MEM_HOST or OTR_MEM_DEVICE */
+  int32_t reserved;
+  const uint64_t* key;
+  const float* lat;            /* Point.java:15-17: float coordinates, int accuracy, long time */
+  const float* lon;
+  const int32_t* accuracy;
+  const int64_t* time;
+  const int64_t* timestamp;    /* the record's stream time (session_gap's units) */
+} otr_session_points;
+
+/* What Batch.report hands to BatchingProcessor.forward, for every window of a call.
+ * Windows come in round order (a key's next window needs its previous trim), within a
+ * round by ascending trigger; the reference's forward order is ascending trigger over the
+ * whole chunk: sort by it to get that.  trigger: the arrival index, in the pushed chunk, of
+ * the point that tripped the gate, or -1 - rank for the eviction of rank `rank` in key
+ * order.  shape_used: -1 when the report has none (K7's 0 included) or the trace failed;
+ * status: the trace's OTR_OK / OTR_MATCH_ERROR; trimmed: points dropped from the session's
+ * front; window w owns reports rep_off[w] .. rep_off[w+1]-1 (rep_off has n_windows + 1
+ * elements; a failed trace has none).  All pointers are owned by the matcher and stay
+ * valid until its next session call; host and device arrays are both filled.
+ * n_forced / n_dropped count this call; n_rebuilds counts the key table's rebuilds since
+ * otr_sessions_open; n_live is the number of sessions after the call. */
+typedef struct otr_session_result {
+  int64_t n_windows;
+  int64_t n_reports;
+  int32_t n_rounds;
+  int32_t n_live;
+  int32_t n_forced;
+  int32_t n_dropped;
+  int32_t n_evicted;           /* punctuate: sessions deleted, reporting or not */
+  int32_t n_rebuilds;
+  float device_ms;             /* HIP-event time from the call's first kernel to its last */
+  float match_ms;              /* host wall time of the matcher's batches inside the call */
+  /* host */
+  uint64_t* key;  int64_t* trigger;  int32_t* n_points;  int32_t* shape_used;  int32_t* status;
+  int32_t* trimmed;  int64_t* rep_off;
+  uint64_t* id;  uint64_t* next_id;  double* t0;  double* t1;  int32_t* length;  int32_t* queue_length;
+  /* device */
+  uint64_t* d_key;  int64_t* d_trigger;  int32_t* d_n_points;  int32_t* d_shape_used;  int32_t* d_status;
+  int32_t* d_trimmed;  int64_t* d_rep_off;
+  uint64_t* d_id;  uint64_t* d_next_id;  double* d_t0;  double* d_t1;  int32_t* d_length;  int32_t* d_queue_length;
+} otr_session_result;
+
+/* Every live session in ascending key order (the content of Batch.Serder): session i owns
+ * points point_off[i] .. point_off[i+1]-1.  Host arrays owned by the matcher, valid until
+ * its next session call. */
+typedef struct otr_session_snapshot {
+  int64_t n_sessions;
+  int64_t n_points;
+  uint64_t* key;  int64_t* point_off;  float* max_sep;  int64_t* last_update;
+  float* lat;  float* lon;  int32_t* accuracy;  int64_t* time;
+} otr_session_snapshot;
+
+/* Opens the matcher's store (OTR_BAD_REQUEST when it has one, or for a config out of
+ * range; OTR_DEVICE_ERROR naming the buffer when it does not fit the device). */
+int otr_sessions_open(otr_matcher* m, const otr_session_config* cfg);
+int otr_sessions_close(otr_matcher* m);
+
+/* BatchingProcessor.process over a chunk of points: every key's points are appended one by
+ * one; the keys whose gate passed are matched as one device batch (several beyond
+ * batch_probes), trimmed, and the chunk goes on after the trigger points, round by round,
+ * to its end.  Any chunking of one arrival stream gives the same windows.  A chunk that
+ * would take the live sessions beyond max_sessions is refused with OTR_BAD_REQUEST and
+ * the store untouched. */
+int otr_sessions_push(otr_matcher* m, const otr_session_points* pts, otr_session_result* out);
+
+/* BatchingProcessor.punctuate: every session with ts - last_update > session_gap is deleted
+ * and, when it holds n >= 2 points with a non-negative elapsed time, reported. */
+int otr_sessions_punctuate(otr_matcher* m, int64_t ts, otr_session_result* out);
+
+/* The two halves of a round, for callers with their own matching policy.  Advance takes a
+ * new chunk (pts) or continues the current one (pts NULL) and leaves the tripped windows
+ * as a batch in HBM (memory OTR_MEM_DEVICE, levels and threshold from the config; owned by
+ * the matcher until the commit); n_traces == 0: the chunk is consumed.  Commit takes one
+ * shape_used and one trace status per window (host or device memory) and trims.
+ * otr_sessions_windows describes the windows of the last advance (after the commit also
+ * shape_used, status and trimmed; no reports). */
+int otr_sessions_advance(otr_matcher* m, const otr_session_points* pts, otr_trace_batch* out);
+int otr_sessions_commit(otr_matcher* m, const int32_t* shape_used, const int32_t* status, int32_t memory);
+int otr_sessions_windows(otr_matcher* m, otr_session_result* out);
+
+int otr_sessions_snapshot(otr_matcher* m, otr_session_snapshot* out);
+
 /* report() (reporter_service.py:79-179) over n segment lists at once, evaluated by the
  * device code of the segment scan K7 (otr_report.h compiled for gfx950, one thread per
  * list) — what pins the device tail against the reference's own report() outputs.  Host

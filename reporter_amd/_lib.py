@@ -45,7 +45,9 @@ EXPORTS = ['otr_configure', 'otr_configure_json', 'otr_matcher_new', 'otr_matche
            'otr_tiles_cull', 'otr_tiles_format', 'otr_ingest', 'otr_report_lists_device', 'otr_hist_reduce',
            'otr_tilehier_row', 'otr_tilehier_col', 'otr_tilehier_file', 'otr_tilehier_files', 'otr_flatten',
            'otr_max_batch_probes', 'otr_launch_max_items', 'otr_service_stats', 'otr_matched_points',
-           'otr_edge_traversals', 'otr_edge_observations']
+           'otr_edge_traversals', 'otr_edge_observations', 'otr_sessions_open', 'otr_sessions_close',
+           'otr_sessions_push', 'otr_sessions_punctuate', 'otr_sessions_advance', 'otr_sessions_commit',
+           'otr_sessions_windows', 'otr_sessions_snapshot']
 
 
 class ServiceSplit(ctypes.Structure):
@@ -152,6 +154,76 @@ class TraversalResult(ctypes.Structure):
                 [('d_' + k, ctypes.c_void_p) for k, _, _ in TRAVERSAL_FIELDS])
 
 
+class SessionConfig(ctypes.Structure):
+    """otr_session_config (include/otr.h): the session store's sizes, gates and report options."""
+    _fields_ = [('max_sessions', ctypes.c_int32), ('max_points', ctypes.c_int32), ('report_dist', ctypes.c_float),
+                ('report_count', ctypes.c_int32), ('report_time', ctypes.c_int64), ('session_gap', ctypes.c_int64),
+                ('mode', ctypes.c_int32), ('report_levels', ctypes.c_uint32), ('transition_levels', ctypes.c_uint32),
+                ('threshold_sec', ctypes.c_int32), ('batch_probes', ctypes.c_int64)]
+
+
+# the arrays of otr_session_points, in the struct's order
+SESSION_POINT_FIELDS = [('key', np.uint64), ('lat', np.float32), ('lon', np.float32), ('accuracy', np.int32),
+                        ('time', np.int64), ('timestamp', np.int64)]
+
+
+class SessionPoints(ctypes.Structure):
+    _fields_ = ([('n', ctypes.c_int64), ('memory', ctypes.c_int32), ('reserved', ctypes.c_int32)] +
+                [(k, ctypes.c_void_p) for k, _ in SESSION_POINT_FIELDS])
+
+
+# the per-window and per-report arrays of otr_session_result, in the struct's order
+SESSION_WINDOW_FIELDS = [('key', ctypes.c_uint64, np.uint64), ('trigger', ctypes.c_int64, np.int64),
+                         ('n_points', ctypes.c_int32, np.int32), ('shape_used', ctypes.c_int32, np.int32),
+                         ('status', ctypes.c_int32, np.int32), ('trimmed', ctypes.c_int32, np.int32),
+                         ('rep_off', ctypes.c_int64, np.int64)]
+SESSION_REPORT_FIELDS = [('id', ctypes.c_uint64, np.uint64), ('next_id', ctypes.c_uint64, np.uint64),
+                         ('t0', ctypes.c_double, np.float64), ('t1', ctypes.c_double, np.float64),
+                         ('length', ctypes.c_int32, np.int32), ('queue_length', ctypes.c_int32, np.int32)]
+SESSION_COUNTS = ['n_windows', 'n_reports', 'n_rounds', 'n_live', 'n_forced', 'n_dropped', 'n_evicted', 'n_rebuilds']
+
+
+class SessionResult(ctypes.Structure):
+    """otr_session_result (include/otr.h): the windows of a session call and their reports."""
+    _fields_ = ([('n_windows', ctypes.c_int64), ('n_reports', ctypes.c_int64)] +
+                [(k, ctypes.c_int32) for k in SESSION_COUNTS[2:]] +
+                [('device_ms', ctypes.c_float), ('match_ms', ctypes.c_float)] +
+                [(k, P(ct)) for k, ct, _ in SESSION_WINDOW_FIELDS + SESSION_REPORT_FIELDS] +
+                [('d_' + k, ctypes.c_void_p) for k, _, _ in SESSION_WINDOW_FIELDS + SESSION_REPORT_FIELDS])
+
+
+SNAPSHOT_FIELDS = [('key', ctypes.c_uint64, np.uint64), ('point_off', ctypes.c_int64, np.int64),
+                   ('max_sep', ctypes.c_float, np.float32), ('last_update', ctypes.c_int64, np.int64),
+                   ('lat', ctypes.c_float, np.float32), ('lon', ctypes.c_float, np.float32),
+                   ('accuracy', ctypes.c_int32, np.int32), ('time', ctypes.c_int64, np.int64)]
+
+
+class SessionSnapshot(ctypes.Structure):
+    """otr_session_snapshot (include/otr.h): every live session in key order."""
+    _fields_ = ([('n_sessions', ctypes.c_int64), ('n_points', ctypes.c_int64)] +
+                [(k, P(ct)) for k, ct, _ in SNAPSHOT_FIELDS])
+
+
+def session_result_to_numpy(r):
+    """Host arrays of an otr_session_result (copies) and its counts."""
+    nw, nr = int(r.n_windows), int(r.n_reports)
+    out = {k: _arr(getattr(r, k), nw + 1 if k == 'rep_off' else nw, dt) for k, _, dt in SESSION_WINDOW_FIELDS}
+    if not r.rep_off:
+        out['rep_off'] = np.zeros(1, np.int64)
+    out.update({k: _arr(getattr(r, k), nr, dt) for k, _, dt in SESSION_REPORT_FIELDS})
+    out.update({k: int(getattr(r, k)) for k in SESSION_COUNTS})
+    out['device_ms'] = float(r.device_ms)
+    out['match_ms'] = float(r.match_ms)
+    return out
+
+
+def snapshot_to_numpy(r):
+    ns, npt = int(r.n_sessions), int(r.n_points)
+    per_session = ('key', 'max_sep', 'last_update')
+    return {k: _arr(getattr(r, k), ns + 1 if k == 'point_off' else (ns if k in per_session else npt), dt)
+            for k, _, dt in SNAPSHOT_FIELDS}
+
+
 # otr_hist_entry (include/otr.h), 32 bytes
 HIST_ENTRY = np.dtype([('file', '<u8'), ('id', '<u8'), ('next_id', '<u8'), ('speed_bin', '<u4'), ('count', '<u4')])
 
@@ -196,6 +268,15 @@ def lib():
     if hasattr(L, 'otr_edge_traversals'):
         L.otr_edge_traversals.argtypes = [ctypes.c_void_p, P(TraversalResult)]
         L.otr_edge_observations.argtypes = [ctypes.c_void_p, ctypes.c_int32, P(ctypes.c_void_p), P(ctypes.c_int64)]
+    if hasattr(L, 'otr_sessions_open'):  # (an A/B build of an earlier round may lack them)
+        L.otr_sessions_open.argtypes = [ctypes.c_void_p, P(SessionConfig)]
+        L.otr_sessions_close.argtypes = [ctypes.c_void_p]
+        L.otr_sessions_push.argtypes = [ctypes.c_void_p, P(SessionPoints), P(SessionResult)]
+        L.otr_sessions_punctuate.argtypes = [ctypes.c_void_p, ctypes.c_int64, P(SessionResult)]
+        L.otr_sessions_advance.argtypes = [ctypes.c_void_p, P(SessionPoints), P(TraceBatch)]
+        L.otr_sessions_commit.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
+        L.otr_sessions_windows.argtypes = [ctypes.c_void_p, P(SessionResult)]
+        L.otr_sessions_snapshot.argtypes = [ctypes.c_void_p, P(SessionSnapshot)]
     L.otr_graph_info.argtypes = [P(ctypes.c_int64), P(ctypes.c_int64), P(ctypes.c_int64)]
     L.otr_matcher_stream.argtypes = [ctypes.c_void_p]
     L.otr_matcher_stream.restype = ctypes.c_void_p

@@ -453,6 +453,47 @@ int otr_ingest(otr_matcher* m, const char* text, int64_t len, int32_t memory, co
   return rc;
 }
 
+// the session store (K14): BatchingProcessor.java:58-106 / Batch.java:43-90 per key, in HBM
+#define OTR_SESSIONS_CALL(null_test, call)   \
+  if (null_test) {                           \
+    g_last_error = "null argument";          \
+    return OTR_BAD_REQUEST;                  \
+  }                                          \
+  std::string err;                           \
+  const int rc = m->m.call;                  \
+  if (rc != OTR_OK) g_last_error = err;      \
+  return rc
+
+int otr_sessions_open(otr_matcher* m, const otr_session_config* cfg) {
+  OTR_SESSIONS_CALL(!m || !cfg, sessions_open(cfg, &err));
+}
+
+int otr_sessions_close(otr_matcher* m) { OTR_SESSIONS_CALL(!m, sessions_close(&err)); }
+
+int otr_sessions_push(otr_matcher* m, const otr_session_points* pts, otr_session_result* out) {
+  OTR_SESSIONS_CALL(!m || !pts || !out, sessions_push(pts, out, &err));
+}
+
+int otr_sessions_punctuate(otr_matcher* m, int64_t ts, otr_session_result* out) {
+  OTR_SESSIONS_CALL(!m || !out, sessions_punctuate(ts, out, &err));
+}
+
+int otr_sessions_advance(otr_matcher* m, const otr_session_points* pts, otr_trace_batch* out) {
+  OTR_SESSIONS_CALL(!m || !out, sessions_advance(pts, out, &err));
+}
+
+int otr_sessions_commit(otr_matcher* m, const int32_t* shape_used, const int32_t* status, int32_t memory) {
+  OTR_SESSIONS_CALL(!m, sessions_commit(shape_used, status, memory, &err));
+}
+
+int otr_sessions_windows(otr_matcher* m, otr_session_result* out) {
+  OTR_SESSIONS_CALL(!m || !out, sessions_windows(out, &err));
+}
+
+int otr_sessions_snapshot(otr_matcher* m, otr_session_snapshot* out) {
+  OTR_SESSIONS_CALL(!m || !out, sessions_snapshot(out, &err));
+}
+
 // simple_reporter.py:188-195: ','.join([id, next, duration, '1', length, queue, start, end,
 // source, mode.upper()]) + os.linesep
 // Segment.appendToStringBuffer (Segment.java:59-74) for OTR_TILE_RULES_STREAM

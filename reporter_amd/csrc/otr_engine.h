@@ -81,8 +81,12 @@ struct GSlab {
 // (oracle orc_turn_table: the same operations)
 void turn_table(double factor, int32_t* tab181);
 
+struct SessionStore;                    // otr_sessions.hip (K14)
+void sessions_destroy(SessionStore* s);  // frees the store's device memory
+
 struct Matcher {
   hipStream_t stream = nullptr;
+  SessionStore* ses = nullptr;  // the session store (otr_sessions_open), owned
   std::vector<DevBuf> bufs;
   GSlab gslab[2];
   std::vector<int32_t> h_turn;
@@ -147,6 +151,15 @@ struct Matcher {
   int copy_out(void* dst, const void* src, size_t bytes, int dst_memory, std::string* err);
   int ingest(const char* text, int64_t len, int memory, const otr_ingest_format* fmt, otr_ingest_result* out,
              std::string* err);
+  // the session store (K14, otr_sessions.hip)
+  int sessions_open(const otr_session_config* cfg, std::string* err);
+  int sessions_close(std::string* err);
+  int sessions_push(const otr_session_points* pts, otr_session_result* out, std::string* err);
+  int sessions_punctuate(int64_t ts, otr_session_result* out, std::string* err);
+  int sessions_advance(const otr_session_points* pts, otr_trace_batch* out, std::string* err);
+  int sessions_commit(const int32_t* shape_used, const int32_t* status, int memory, std::string* err);
+  int sessions_windows(otr_session_result* out, std::string* err);
+  int sessions_snapshot(otr_session_snapshot* out, std::string* err);
   ~Matcher();
 };
 

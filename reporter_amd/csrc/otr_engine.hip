@@ -525,6 +525,7 @@ static int oom_error(hipStream_t stream, const DeviceOom& o, std::string* err) {
 }
 
 Matcher::~Matcher() {
+  if (ses) sessions_destroy(ses);
   for (auto& b : bufs)
     if (b.p) (void)hipFree(b.p);
   for (auto& sl : gslab)

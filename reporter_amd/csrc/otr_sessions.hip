@@ -1,0 +1,815 @@
+// otr_sessions.hip — host side of the session store (K14, otr_sessions.h): the store's
+// device memory, the passes of a chunk (insert, assign, group), the rounds (advance, gather,
+// match, commit), punctuate and the snapshot.  include/otr.h otr_sessions_* for the rules.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "otr_engine.h"
+#include "otr_launch.h"
+#include "otr_sessions.h"
+
+#define HIPCHK(x)                                                                        \
+  do {                                                                                   \
+    hipError_t e_ = (x);                                                                 \
+    if (e_ != hipSuccess) {                                                              \
+      if (err) *err = std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x;    \
+      return OTR_DEVICE_ERROR;                                                           \
+    }                                                                                    \
+  } while (0)
+
+namespace otr {
+
+namespace {
+
+struct SesOom {
+  const char* name;
+  size_t bytes;
+};
+
+unsigned ses_grid(int64_t n, int threads) { return (unsigned)std::max<int64_t>(1, (n + threads - 1) / threads); }
+
+// growable buffers of a chunk, a round and a result
+enum SesBuf {
+  B_KEY, B_LAT, B_LON, B_ACC, B_TIME, B_TS, B_ENTRY, B_NEW, B_RANK, B_LANE_SLOT, B_IDX, B_SORT_SLOT, B_SORT_IDX,
+  B_HEAD, B_SEG_INCL, B_SEG_SLOT, B_SEG_CUR, B_SEG_END, B_TRIP, B_TRIP_INCL, B_TMP,
+  B_W_SLOT, B_W_TRIG, B_W_N, B_W_KEY, B_W_SU, B_W_STATUS, B_W_TRIM, B_W_SU_OUT,
+  B_G_OFF, B_G_LAT, B_G_LON, B_G_TIME, B_G_ACC, B_G_MODE, B_SUB_OFF,
+  B_FLAG, B_FLAG_INCL, B_L_KEY, B_L_SLOT, B_L_KEY2, B_L_SLOT2, B_L_REP, B_L_REP_INCL, B_L_N,
+  B_S_LAT, B_S_LON, B_S_ACC,
+  B_R_KEY, B_R_TRIG, B_R_N, B_R_SU, B_R_STATUS, B_R_TRIM, B_R_OFF, B_R_ID, B_R_NEXT, B_R_T0, B_R_T1, B_R_LEN,
+  B_R_QUEUE,
+  B_NUM
+};
+const char* const kBufName[B_NUM] = {
+    "chunk key", "chunk lat", "chunk lon", "chunk accuracy", "chunk time", "chunk timestamp", "lane entry",
+    "lane creator", "creator rank", "lane session", "lane index", "sorted session", "sorted index", "segment head",
+    "segment rank", "segment session", "segment cursor", "segment end", "trigger flag", "trigger rank",
+    "scan / sort workspace", "window session", "window trigger", "window size", "window key", "window shape_used in",
+    "window status", "window trimmed", "window shape_used", "batch offsets", "batch lat", "batch lon", "batch time",
+    "batch accuracy", "batch mode", "sub-batch offsets", "session flag", "session rank", "list key", "list session",
+    "sorted list key", "sorted list session", "eviction report flag", "eviction report rank", "list size",
+    "snapshot lat", "snapshot lon", "snapshot accuracy", "result key", "result trigger", "result size",
+    "result shape_used", "result status", "result trimmed", "result report offsets", "result id", "result next id",
+    "result t0", "result t1", "result length", "result queue length"};
+
+}  // namespace
+
+struct SessionStore {
+  otr_session_config cfg{};
+  hipStream_t stream = nullptr;
+  std::vector<void*> fixed;
+  SesTable tab{}, spare{};
+  SesStore st{};
+  int32_t* free_list = nullptr;
+  int32_t* cnt = nullptr;
+  int32_t h_cnt[SES_WORDS] = {0, 0, 0, 0, 0};
+  int32_t n_rebuilds = 0;
+  hipEvent_t ev[2];
+  bool ev_init = false;
+  struct {
+    void* p = nullptr;
+    size_t bytes = 0;
+  } b[B_NUM];
+  // the chunk and the round
+  SesChunk ch{};
+  int32_t n_seg = 0, W = 0, n_list = 0;
+  int64_t P = 0;
+  bool chunk_open = false, pending = false;
+  std::vector<unsigned long long> w_key;
+  std::vector<int64_t> w_trig, w_n;
+  std::vector<int32_t> w_su, w_status, w_trim;
+  // what a call returns
+  std::vector<unsigned long long> r_key, r_id, r_next;
+  std::vector<int64_t> r_trig, r_off;
+  std::vector<int32_t> r_n, r_su, r_status, r_trim, r_len, r_queue;
+  std::vector<double> r_t0, r_t1;
+  int32_t r_rounds = 0, r_evicted = 0, forced0 = 0, dropped0 = 0;
+  double r_match_ms = 0.0;
+  // snapshot
+  std::vector<unsigned long long> s_key;
+  std::vector<int64_t> s_off, s_last, s_time, all_last;
+  std::vector<float> s_sep, s_lat, s_lon, all_sep;
+  std::vector<int32_t> s_acc, s_slot;
+
+  int32_t live() const { return cfg.max_sessions - h_cnt[SES_NFREE]; }
+
+  template <class T>
+  T* buf(int slot, size_t n) {
+    const size_t bytes = (n ? n : 1) * sizeof(T);
+    if (b[slot].bytes < bytes) {
+      if (b[slot].p) (void)hipFree(b[slot].p);
+      b[slot].p = nullptr;
+      b[slot].bytes = 0;
+      const size_t nb = bytes + bytes / 4;
+      if (hipMalloc(&b[slot].p, nb) != hipSuccess) {
+        (void)hipGetLastError();
+        b[slot].p = nullptr;
+        throw SesOom{kBufName[slot], nb};
+      }
+      b[slot].bytes = nb;
+    }
+    return (T*)b[slot].p;
+  }
+  template <class T>
+  T* fix(size_t n, const char* name) {
+    void* p = nullptr;
+    const size_t bytes = (n ? n : 1) * sizeof(T);
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      throw SesOom{name, bytes};
+    }
+    fixed.push_back(p);
+    return (T*)p;
+  }
+
+  int scan32(const int32_t* in, int32_t* out, int64_t n, std::string* err);
+  int scan64(const int64_t* in, int64_t* out, int64_t n, std::string* err);
+  int alloc(std::string* err);
+  int rebuild(std::string* err);
+  int chunk_begin(const otr_session_points* pts, std::string* err);
+  int round(std::string* err);
+  int gather(std::string* err);
+  int commit(const int32_t* su, const int32_t* status, int memory, std::string* err);
+  int match(Matcher& m, std::string* err);
+  void result_begin();
+  void result_round();
+  int result_end(otr_session_result* out, bool with_device, std::string* err);
+  void fill_batch(otr_trace_batch* bt);
+  int list_sessions(int stale_only, int64_t ts, std::string* err);
+  int release_list(const int32_t* list, int32_t n, std::string* err);
+};
+
+void sessions_destroy(SessionStore* s) {
+  if (!s) return;
+  if (s->stream) (void)hipStreamSynchronize(s->stream);
+  for (void* p : s->fixed) (void)hipFree(p);
+  for (auto& x : s->b)
+    if (x.p) (void)hipFree(x.p);
+  if (s->ev_init)
+    for (auto& e : s->ev) (void)hipEventDestroy(e);
+  delete s;
+}
+
+int SessionStore::scan32(const int32_t* in, int32_t* out, int64_t n, std::string* err) {
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, in, out, (int)n, stream));
+  void* tmp = buf<char>(B_TMP, tb);
+  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, in, out, (int)n, stream));
+  return OTR_OK;
+}
+
+int SessionStore::scan64(const int64_t* in, int64_t* out, int64_t n, std::string* err) {
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, in, out, (int)n, stream));
+  void* tmp = buf<char>(B_TMP, tb);
+  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, in, out, (int)n, stream));
+  return OTR_OK;
+}
+
+int SessionStore::alloc(std::string* err) {
+  const size_t ms = (size_t)cfg.max_sessions, cap = 2 * ms, np = ms * (size_t)cfg.max_points;
+  tab.cap = spare.cap = (uint32_t)cap;
+  tab.key = fix<unsigned long long>(cap, "key table");
+  tab.slot = fix<int32_t>(cap, "key table sessions");
+  spare.key = fix<unsigned long long>(cap, "spare key table");
+  spare.slot = fix<int32_t>(cap, "spare key table sessions");
+  st.max_sessions = cfg.max_sessions;
+  st.max_points = cfg.max_points;
+  st.n = fix<int32_t>(ms, "session sizes");
+  st.max_sep = fix<float>(ms, "session max_sep");
+  st.last = fix<int64_t>(ms, "session last_update");
+  st.skey = fix<unsigned long long>(ms, "session keys");
+  st.entry = fix<int32_t>(ms, "session entries");
+  st.lat = fix<float>(np, "session points lat");
+  st.lon = fix<float>(np, "session points lon");
+  st.acc = fix<int32_t>(np, "session points accuracy");
+  st.time = fix<int64_t>(np, "session points time");
+  free_list = fix<int32_t>(ms, "free sessions");
+  cnt = fix<int32_t>(SES_WORDS, "store counters");
+  HIPCHK(hipMemsetAsync(tab.key, 0xFF, 8 * cap, stream));
+  HIPCHK(hipMemsetAsync(tab.slot, 0xFF, 4 * cap, stream));
+  HIPCHK(hipMemsetAsync(st.n, 0, 4 * ms, stream));
+  HIPCHK(hipMemsetAsync(st.max_sep, 0, 4 * ms, stream));
+  HIPCHK(hipMemsetAsync(st.last, 0, 8 * ms, stream));
+  HIPCHK(hipMemsetAsync(st.skey, 0xFF, 8 * ms, stream));
+  std::vector<int32_t> fl(ms);
+  for (size_t i = 0; i < ms; ++i) fl[i] = (int32_t)(ms - 1 - i);  // session 0 on top
+  h_cnt[SES_NFREE] = cfg.max_sessions;
+  HIPCHK(hipMemcpyAsync(free_list, fl.data(), 4 * ms, hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(cnt, h_cnt, sizeof(h_cnt), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+  ev_init = true;
+  return OTR_OK;
+}
+
+// live + dead entries beyond half the table: the live ones into the spare table
+int SessionStore::rebuild(std::string* err) {
+  HIPCHK(hipMemsetAsync(spare.key, 0xFF, 8 * (size_t)spare.cap, stream));
+  HIPCHK(hipMemsetAsync(spare.slot, 0xFF, 4 * (size_t)spare.cap, stream));
+  k_ses_rebuild<<<ses_grid(tab.cap, 256), 256, 0, stream>>>(tab, spare, st);
+  HIPCHK(hipGetLastError());
+  std::swap(tab, spare);
+  h_cnt[SES_DEAD] = 0;
+  HIPCHK(hipMemsetAsync(cnt + SES_DEAD, 0, 4, stream));
+  ++n_rebuilds;
+  return OTR_OK;
+}
+
+int SessionStore::chunk_begin(const otr_session_points* pts, std::string* err) {
+  int rc;
+  const int64_t n = pts->n;
+  W = 0;
+  if (n <= 0) return OTR_OK;
+  if (n > (int64_t)1 << 30) {
+    if (err) *err = "too many points for one chunk (2^30 at most)";
+    return OTR_BAD_REQUEST;
+  }
+  if (h_cnt[SES_DEAD] > 0 && live() + h_cnt[SES_DEAD] > cfg.max_sessions && (rc = rebuild(err))) return rc;
+  unsigned long long* key = buf<unsigned long long>(B_KEY, n);
+  float* lat = buf<float>(B_LAT, n);
+  float* lon = buf<float>(B_LON, n);
+  int32_t* acc = buf<int32_t>(B_ACC, n);
+  int64_t* time = buf<int64_t>(B_TIME, n);
+  int64_t* ts = buf<int64_t>(B_TS, n);
+  int32_t* entry = buf<int32_t>(B_ENTRY, n);
+  int32_t* fresh = buf<int32_t>(B_NEW, n);
+  int32_t* rank = buf<int32_t>(B_RANK, n);
+  uint32_t* lane_slot = buf<uint32_t>(B_LANE_SLOT, n);
+  int32_t* idx = buf<int32_t>(B_IDX, n);
+  uint32_t* sorted_slot = buf<uint32_t>(B_SORT_SLOT, n);
+  int32_t* sorted_idx = buf<int32_t>(B_SORT_IDX, n);
+  int32_t* head = buf<int32_t>(B_HEAD, n);
+  int32_t* seg_incl = buf<int32_t>(B_SEG_INCL, n);
+  int32_t* trip = buf<int32_t>(B_TRIP, n);
+  buf<int32_t>(B_TRIP_INCL, n);
+  const hipMemcpyKind kind = pts->memory == OTR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  HIPCHK(hipMemcpyAsync(key, pts->key, 8 * n, kind, stream));
+  HIPCHK(hipMemcpyAsync(lat, pts->lat, 4 * n, kind, stream));
+  HIPCHK(hipMemcpyAsync(lon, pts->lon, 4 * n, kind, stream));
+  HIPCHK(hipMemcpyAsync(acc, pts->accuracy, 4 * n, kind, stream));
+  HIPCHK(hipMemcpyAsync(time, pts->time, 8 * n, kind, stream));
+  HIPCHK(hipMemcpyAsync(ts, pts->timestamp, 8 * n, kind, stream));
+  ch = SesChunk{n, key, lat, lon, acc, time, ts};
+  const unsigned g = ses_grid(n, 256);
+  // 1. keys into the table
+  HIPCHK(hipMemsetAsync(cnt + SES_FLAGS, 0, 4, stream));
+  k_ses_insert<<<g, 256, 0, stream>>>(tab, ch, entry, fresh, cnt);
+  if ((rc = scan32(fresh, rank, n, err))) return rc;
+  int32_t n_new = 0, flags = 0;
+  HIPCHK(hipMemcpyAsync(&n_new, rank + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(&flags, cnt + SES_FLAGS, 4, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (flags || n_new > h_cnt[SES_NFREE]) {
+    k_ses_rollback<<<g, 256, 0, stream>>>(tab, n, entry, fresh);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    if (err)
+      *err = (flags & kSesFlagNoId) ? "key OTR_NO_ID is the store's empty mark"
+                                    : "the chunk would take the live sessions beyond max_sessions (" +
+                                          std::to_string(live()) + " live, " + std::to_string(cfg.max_sessions) +
+                                          " at most)";
+    return OTR_BAD_REQUEST;
+  }
+  // 2. storage for the new keys, 3. the chunk grouped by session, arrival order kept
+  if (n_new) {
+    k_ses_assign<<<g, 256, 0, stream>>>(tab, st, ch, entry, fresh, rank, free_list, h_cnt[SES_NFREE]);
+    k_ses_add<<<1, 1, 0, stream>>>(cnt + SES_NFREE, -n_new);
+    h_cnt[SES_NFREE] -= n_new;
+  }
+  k_ses_lane_slot<<<g, 256, 0, stream>>>(tab, n, entry, lane_slot, idx);
+  int bits = 1;
+  while (bits < 32 && ((int64_t)1 << bits) < (int64_t)cfg.max_sessions) ++bits;
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, lane_slot, sorted_slot, idx, sorted_idx, (int)n, 0, bits,
+                                            stream));
+  void* tmp = buf<char>(B_TMP, tb);
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, lane_slot, sorted_slot, idx, sorted_idx, (int)n, 0, bits,
+                                            stream));
+  k_ses_heads<<<g, 256, 0, stream>>>(sorted_slot, n, head);
+  if ((rc = scan32(head, seg_incl, n, err))) return rc;
+  HIPCHK(hipMemcpyAsync(&n_seg, seg_incl + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  int32_t* seg_slot = buf<int32_t>(B_SEG_SLOT, n_seg);
+  int32_t* seg_cur = buf<int32_t>(B_SEG_CUR, n_seg);
+  int32_t* seg_end = buf<int32_t>(B_SEG_END, n_seg);
+  k_ses_segments<<<g, 256, 0, stream>>>(sorted_slot, seg_incl, n, seg_slot, seg_cur, seg_end);
+  HIPCHK(hipMemsetAsync(trip, 0, 4 * n, stream));
+  HIPCHK(hipGetLastError());
+  chunk_open = true;
+  return OTR_OK;
+}
+
+int SessionStore::release_list(const int32_t* list, int32_t n, std::string* err) {
+  k_ses_release<<<ses_grid(n, 256), 256, 0, stream>>>(n, list, tab, st, free_list, cnt);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  return OTR_OK;
+}
+
+// offsets, then one wave per window (win_slot / win_n of W windows are in place)
+int SessionStore::gather(std::string* err) {
+  int rc;
+  int64_t* off = buf<int64_t>(B_G_OFF, (size_t)W + 1);
+  HIPCHK(hipMemsetAsync(off, 0, 8, stream));
+  if ((rc = scan64((int64_t*)b[B_W_N].p, off + 1, W, err))) return rc;
+  w_key.resize(W);
+  w_trig.resize(W);
+  w_n.resize(W);
+  HIPCHK(hipMemcpyAsync(&P, off + W, 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(w_key.data(), b[B_W_KEY].p, 8 * (size_t)W, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(w_trig.data(), b[B_W_TRIG].p, 8 * (size_t)W, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(w_n.data(), b[B_W_N].p, 8 * (size_t)W, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  double* lat = buf<double>(B_G_LAT, P);
+  double* lon = buf<double>(B_G_LON, P);
+  int64_t* time = buf<int64_t>(B_G_TIME, P);
+  float* acc = buf<float>(B_G_ACC, P);
+  uint8_t* mode = buf<uint8_t>(B_G_MODE, W);
+  k_ses_gather<false><<<(unsigned)W, 64, 0, stream>>>(W, (const int32_t*)b[B_W_SLOT].p, off, st, lat, lon, time, acc,
+                                                      mode, (uint8_t)cfg.mode, nullptr, nullptr, nullptr);
+  HIPCHK(hipGetLastError());
+  w_su.assign(W, -1);
+  w_status.assign(W, OTR_OK);
+  w_trim.assign(W, 0);
+  return OTR_OK;
+}
+
+// one round: advance every key with unconsumed points, list the tripped ones by trigger
+int SessionStore::round(std::string* err) {
+  int rc;
+  const int64_t n = ch.n;
+  int32_t* trip = (int32_t*)b[B_TRIP].p;
+  int32_t* trip_incl = (int32_t*)b[B_TRIP_INCL].p;
+  const SesGate gate{cfg.report_dist, cfg.report_count, cfg.report_time};
+  k_ses_advance<<<ses_grid(n_seg, 64), 64, 0, stream>>>(n_seg, (const int32_t*)b[B_SEG_SLOT].p,
+                                                        (int32_t*)b[B_SEG_CUR].p, (const int32_t*)b[B_SEG_END].p,
+                                                        (const int32_t*)b[B_SORT_IDX].p, ch, st, gate, trip, cnt);
+  if ((rc = scan32(trip, trip_incl, n, err))) return rc;
+  HIPCHK(hipMemcpyAsync(&W, trip_incl + (n - 1), 4, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (W == 0) {  // the chunk is consumed: sessions left empty are deleted
+    chunk_open = false;
+    return release_list((const int32_t*)b[B_SEG_SLOT].p, n_seg, err);
+  }
+  int32_t* win_slot = buf<int32_t>(B_W_SLOT, W);
+  int64_t* win_trig = buf<int64_t>(B_W_TRIG, W);
+  int64_t* win_n = buf<int64_t>(B_W_N, W);
+  unsigned long long* win_key = buf<unsigned long long>(B_W_KEY, W);
+  k_ses_windows<<<ses_grid(n, 256), 256, 0, stream>>>(n, trip, trip_incl, (const uint32_t*)b[B_LANE_SLOT].p, st,
+                                                      win_slot, win_trig, win_n, win_key);
+  if ((rc = gather(err))) return rc;
+  pending = true;
+  return OTR_OK;
+}
+
+void SessionStore::fill_batch(otr_trace_batch* bt) {
+  memset(bt, 0, sizeof(*bt));
+  bt->memory = OTR_MEM_DEVICE;
+  bt->report_levels = cfg.report_levels;
+  bt->transition_levels = cfg.transition_levels;
+  bt->threshold_sec = cfg.threshold_sec;
+  bt->quantisation = 3600;
+  bt->n_traces = W;
+  bt->trace_offsets = (const int64_t*)b[B_G_OFF].p;
+  if (W > 0) {
+    bt->lat = (const double*)b[B_G_LAT].p;
+    bt->lon = (const double*)b[B_G_LON].p;
+    bt->time = (const int64_t*)b[B_G_TIME].p;
+    bt->accuracy = (const float*)b[B_G_ACC].p;
+    bt->mode = (const uint8_t*)b[B_G_MODE].p;
+  }
+}
+
+int SessionStore::commit(const int32_t* su, const int32_t* status, int memory, std::string* err) {
+  int32_t* d_su = buf<int32_t>(B_W_SU, W);
+  int32_t* d_status = buf<int32_t>(B_W_STATUS, W);
+  int32_t* d_su_out = buf<int32_t>(B_W_SU_OUT, W);
+  int32_t* d_trim = buf<int32_t>(B_W_TRIM, W);
+  const hipMemcpyKind kind = memory == OTR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  HIPCHK(hipMemcpyAsync(d_su, su, 4 * (size_t)W, kind, stream));
+  HIPCHK(hipMemcpyAsync(d_status, status, 4 * (size_t)W, kind, stream));
+  k_ses_commit<<<(unsigned)W, 64, 0, stream>>>(W, (const int32_t*)b[B_W_SLOT].p, d_su, d_status, st, d_su_out, d_trim);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(w_su.data(), d_su_out, 4 * (size_t)W, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(w_trim.data(), d_trim, 4 * (size_t)W, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(w_status.data(), d_status, 4 * (size_t)W, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  pending = false;
+  return OTR_OK;
+}
+
+void SessionStore::result_begin() {
+  for (auto* v : {&r_key, &r_id, &r_next}) v->clear();
+  for (auto* v : {&r_trig, &r_off}) v->clear();
+  for (auto* v : {&r_n, &r_su, &r_status, &r_trim, &r_len, &r_queue}) v->clear();
+  r_t0.clear();
+  r_t1.clear();
+  r_off.push_back(0);
+  r_rounds = 0;
+  r_evicted = 0;
+  r_match_ms = 0.0;
+  forced0 = h_cnt[SES_FORCED];
+  dropped0 = h_cnt[SES_DROPPED];
+}
+
+// the windows of the round into the call's result (their reports are already in r_id ...
+// with one r_off entry per window)
+void SessionStore::result_round() {
+  for (int32_t w = 0; w < W; ++w) {
+    r_key.push_back(w_key[w]);
+    r_trig.push_back(w_trig[w]);
+    r_n.push_back((int32_t)w_n[w]);
+    r_su.push_back(w_su[w]);
+    r_status.push_back(w_status[w]);
+    r_trim.push_back(w_trim[w]);
+  }
+}
+
+// the windows of the round through the matcher, in device batches of at most batch_probes
+// probes: shape_used, status and the reports of every window
+int SessionStore::match(Matcher& m, std::string* err) {
+  const int64_t limit = cfg.batch_probes > 0 ? std::min<int64_t>(cfg.batch_probes, kMaxBatchProbes) : kMaxBatchProbes;
+  std::vector<int64_t> sub;
+  int32_t w0 = 0;
+  int64_t p0 = 0;
+  while (w0 < W) {
+    int32_t w1 = w0 + 1;
+    int64_t np = w_n[w0];
+    while (w1 < W && np + w_n[w1] <= limit) np += w_n[w1++];
+    otr_trace_batch bt;
+    fill_batch(&bt);
+    bt.flags = OTR_BATCH_COPY_REPORTS;
+    bt.n_traces = w1 - w0;
+    if (w0 > 0 || w1 < W) {  // offsets from zero for this part
+      sub.assign(1, 0);
+      for (int32_t w = w0; w < w1; ++w) sub.push_back(sub.back() + w_n[w]);
+      int64_t* d_sub = buf<int64_t>(B_SUB_OFF, sub.size());
+      HIPCHK(hipMemcpyAsync(d_sub, sub.data(), 8 * sub.size(), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      bt.trace_offsets = d_sub;
+      bt.lat += p0;
+      bt.lon += p0;
+      bt.time += p0;
+      bt.accuracy += p0;
+      bt.mode += w0;
+    }
+    otr_batch_result br;
+    std::string e2;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = m.run(&bt, graph_state().defaults, &br, &e2);
+    r_match_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (int32_t w = w0; w < w1; ++w) {
+      const int32_t t = w - w0;
+      const int32_t status = rc != OTR_OK ? rc : br.trace_status[t];
+      w_status[w] = status;
+      w_su[w] = status == OTR_OK ? br.shape_used[t] : -1;
+      if (status == OTR_OK)
+        for (int64_t k = br.trace_rep_off[t]; k < br.trace_rep_off[t + 1]; ++k) {
+          r_id.push_back(br.rep_id[k]);
+          r_next.push_back(br.rep_next[k]);
+          r_t0.push_back(br.rep_t0[k]);
+          r_t1.push_back(br.rep_t1[k]);
+          r_len.push_back(br.rep_length[k]);
+          r_queue.push_back(br.rep_queue[k]);
+        }
+      r_off.push_back((int64_t)r_id.size());
+    }
+    if (rc != OTR_OK && err) *err = e2;
+    p0 += np;
+    w0 = w1;
+  }
+  return OTR_OK;
+}
+
+int SessionStore::result_end(otr_session_result* out, bool with_device, std::string* err) {
+  memset(out, 0, sizeof(*out));
+  const size_t nw = r_key.size(), nr = r_id.size();
+  out->n_windows = (int64_t)nw;
+  out->n_reports = (int64_t)nr;
+  out->n_rounds = r_rounds;
+  out->n_live = live();
+  out->n_forced = h_cnt[SES_FORCED] - forced0;
+  out->n_dropped = h_cnt[SES_DROPPED] - dropped0;
+  out->n_evicted = r_evicted;
+  out->n_rebuilds = n_rebuilds;
+  out->match_ms = (float)r_match_ms;
+  auto P_ = [](auto& v) { return v.empty() ? nullptr : v.data(); };
+  out->key = (uint64_t*)P_(r_key);
+  out->trigger = P_(r_trig);
+  out->n_points = P_(r_n);
+  out->shape_used = P_(r_su);
+  out->status = P_(r_status);
+  out->trimmed = P_(r_trim);
+  out->rep_off = P_(r_off);
+  out->id = (uint64_t*)P_(r_id);
+  out->next_id = (uint64_t*)P_(r_next);
+  out->t0 = P_(r_t0);
+  out->t1 = P_(r_t1);
+  out->length = P_(r_len);
+  out->queue_length = P_(r_queue);
+  if (!with_device) return OTR_OK;
+  auto up = [&](int slot, auto& v, auto** dst) -> int {
+    using T = typename std::remove_reference_t<decltype(v)>::value_type;
+    T* d = buf<T>(slot, v.size());
+    if (!v.empty()) HIPCHK(hipMemcpyAsync(d, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, stream));
+    *dst = d;
+    return OTR_OK;
+  };
+  int rc;
+  unsigned long long *dk, *di, *dn;
+  if ((rc = up(B_R_KEY, r_key, &dk)) || (rc = up(B_R_TRIG, r_trig, &out->d_trigger)) ||
+      (rc = up(B_R_N, r_n, &out->d_n_points)) || (rc = up(B_R_SU, r_su, &out->d_shape_used)) ||
+      (rc = up(B_R_STATUS, r_status, &out->d_status)) || (rc = up(B_R_TRIM, r_trim, &out->d_trimmed)) ||
+      (rc = up(B_R_OFF, r_off, &out->d_rep_off)) || (rc = up(B_R_ID, r_id, &di)) ||
+      (rc = up(B_R_NEXT, r_next, &dn)) || (rc = up(B_R_T0, r_t0, &out->d_t0)) || (rc = up(B_R_T1, r_t1, &out->d_t1)) ||
+      (rc = up(B_R_LEN, r_len, &out->d_length)) || (rc = up(B_R_QUEUE, r_queue, &out->d_queue_length)))
+    return rc;
+  out->d_key = (uint64_t*)dk;
+  out->d_id = (uint64_t*)di;
+  out->d_next_id = (uint64_t*)dn;
+  HIPCHK(hipEventRecord(ev[1], stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  HIPCHK(hipEventElapsedTime(&out->device_ms, ev[0], ev[1]));
+  return OTR_OK;
+}
+
+// sessions (all live ones, or the stale ones at ts) in ascending key order: n_list of them
+// in B_L_KEY2 / B_L_SLOT2
+int SessionStore::list_sessions(int stale_only, int64_t ts, std::string* err) {
+  int rc;
+  const int32_t ms = cfg.max_sessions;
+  int32_t* flag = buf<int32_t>(B_FLAG, ms);
+  int32_t* incl = buf<int32_t>(B_FLAG_INCL, ms);
+  k_ses_flag<<<ses_grid(ms, 256), 256, 0, stream>>>(st, stale_only, ts, cfg.session_gap, flag);
+  if ((rc = scan32(flag, incl, ms, err))) return rc;
+  HIPCHK(hipMemcpyAsync(&n_list, incl + (ms - 1), 4, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (n_list == 0) return OTR_OK;
+  unsigned long long* key = buf<unsigned long long>(B_L_KEY, n_list);
+  int32_t* slot = buf<int32_t>(B_L_SLOT, n_list);
+  unsigned long long* key2 = buf<unsigned long long>(B_L_KEY2, n_list);
+  int32_t* slot2 = buf<int32_t>(B_L_SLOT2, n_list);
+  k_ses_list<<<ses_grid(ms, 256), 256, 0, stream>>>(st, flag, incl, key, slot);
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key, key2, slot, slot2, n_list, 0, 64, stream));
+  void* tmp = buf<char>(B_TMP, tb);
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key2, slot, slot2, n_list, 0, 64, stream));
+  HIPCHK(hipGetLastError());
+  return OTR_OK;
+}
+
+// ---- the matcher's entry points -------------------------------------------------------------
+
+namespace {
+
+template <class F>
+int guarded(Matcher& m, std::string* err, bool need_store, F&& f) {
+  if (need_store && !m.ses) {
+    if (err) *err = "no session store: call otr_sessions_open first";
+    return OTR_BAD_REQUEST;
+  }
+  try {
+    return f();
+  } catch (const SesOom& o) {
+    if (m.stream) (void)hipStreamSynchronize(m.stream);
+    (void)hipGetLastError();
+    if (err)
+      *err = std::string("out of device memory: session buffer '") + o.name + "' needs " +
+             std::to_string((o.bytes >> 20) + 1) + " MiB";
+    return OTR_DEVICE_ERROR;
+  }
+}
+
+int bad(std::string* err, const char* what) {
+  if (err) *err = what;
+  return OTR_BAD_REQUEST;
+}
+
+bool points_ok(const otr_session_points* p) {
+  return p->n <= 0 || (p->key && p->lat && p->lon && p->accuracy && p->time && p->timestamp);
+}
+
+}  // namespace
+
+int Matcher::sessions_open(const otr_session_config* cfg, std::string* err) {
+  if (ses) return bad(err, "the matcher already has a session store");
+  if (cfg->max_sessions < 1 || cfg->max_sessions > (1 << 30) || cfg->max_points < 2 || cfg->mode < 0 ||
+      cfg->mode > 2 || (int64_t)cfg->max_sessions * cfg->max_points > ((int64_t)1 << 40) || cfg->report_count < 0)
+    return bad(err, "session config out of range");
+  HIPCHK(hipSetDevice(graph_state().device));
+  if (!stream) HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+  SessionStore* s = new SessionStore();
+  s->cfg = *cfg;
+  s->stream = stream;
+  const int rc = guarded(*this, err, false, [&] { return s->alloc(err); });
+  if (rc != OTR_OK) {
+    sessions_destroy(s);
+    return rc;
+  }
+  ses = s;
+  return OTR_OK;
+}
+
+int Matcher::sessions_close(std::string* err) {
+  if (!ses) return bad(err, "no session store");
+  sessions_destroy(ses);
+  ses = nullptr;
+  return OTR_OK;
+}
+
+int Matcher::sessions_advance(const otr_session_points* pts, otr_trace_batch* out, std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    SessionStore& s = *ses;
+    int rc;
+    HIPCHK(hipSetDevice(graph_state().device));
+    if (s.pending) return bad(err, "the last advance has not been committed");
+    if (pts) {
+      if (s.chunk_open) return bad(err, "the current chunk is not consumed");
+      if (!points_ok(pts)) return bad(err, "null argument");
+      if ((rc = s.chunk_begin(pts, err))) return rc;
+    }
+    s.W = 0;
+    if (s.chunk_open && (rc = s.round(err))) return rc;
+    if (s.W == 0) {
+      int64_t* off = s.buf<int64_t>(B_G_OFF, 1);
+      HIPCHK(hipMemsetAsync(off, 0, 8, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+    }
+    s.fill_batch(out);
+    return OTR_OK;
+  });
+}
+
+int Matcher::sessions_commit(const int32_t* shape_used, const int32_t* status, int memory, std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    HIPCHK(hipSetDevice(graph_state().device));
+    if (!ses->pending) return bad(err, "nothing to commit: no advance with windows is open");
+    if (!shape_used || !status) return bad(err, "null argument");
+    return ses->commit(shape_used, status, memory, err);
+  });
+}
+
+int Matcher::sessions_windows(otr_session_result* out, std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    SessionStore& s = *ses;
+    s.result_begin();
+    s.result_round();
+    for (int32_t w = 0; w < s.W; ++w) s.r_off.push_back(0);
+    return s.result_end(out, false, err);
+  });
+}
+
+int Matcher::sessions_push(const otr_session_points* pts, otr_session_result* out, std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    SessionStore& s = *ses;
+    int rc;
+    if (!graph_state().ready) {
+      if (err) *err = "otr_configure has not been called";
+      return OTR_NOT_CONFIGURED;
+    }
+    HIPCHK(hipSetDevice(graph_state().device));
+    if (s.pending || s.chunk_open) return bad(err, "an advance / commit sequence is open");
+    if (!points_ok(pts)) return bad(err, "null argument");
+    s.result_begin();
+    HIPCHK(hipEventRecord(s.ev[0], stream));
+    if ((rc = s.chunk_begin(pts, err))) return rc;
+    while (s.chunk_open) {
+      if ((rc = s.round(err))) return rc;
+      if (s.W == 0) break;
+      ++s.r_rounds;
+      if ((rc = s.match(*this, err))) return rc;
+      if ((rc = s.commit(s.w_su.data(), s.w_status.data(), OTR_MEM_HOST, err))) return rc;
+      s.result_round();
+    }
+    s.W = 0;
+    return s.result_end(out, true, err);
+  });
+}
+
+int Matcher::sessions_punctuate(int64_t ts, otr_session_result* out, std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    SessionStore& s = *ses;
+    int rc;
+    if (!graph_state().ready) {
+      if (err) *err = "otr_configure has not been called";
+      return OTR_NOT_CONFIGURED;
+    }
+    HIPCHK(hipSetDevice(graph_state().device));
+    if (s.pending || s.chunk_open) return bad(err, "an advance / commit sequence is open");
+    s.result_begin();
+    s.W = 0;
+    HIPCHK(hipEventRecord(s.ev[0], stream));
+    if ((rc = s.list_sessions(1, ts, err))) return rc;
+    const int32_t ne = s.n_list;
+    if (ne > 0) {
+      const int32_t* list = (const int32_t*)s.b[B_L_SLOT2].p;
+      int32_t* rep = s.buf<int32_t>(B_L_REP, ne);
+      int32_t* rep_incl = s.buf<int32_t>(B_L_REP_INCL, ne);
+      int64_t* cnt_n = s.buf<int64_t>(B_L_N, ne);
+      k_ses_evict_gate<<<ses_grid(ne, 256), 256, 0, stream>>>(ne, list, s.st, rep, cnt_n);
+      if ((rc = s.scan32(rep, rep_incl, ne, err))) return rc;
+      HIPCHK(hipMemcpyAsync(&s.W, rep_incl + (ne - 1), 4, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      if (s.W > 0) {
+        int32_t* win_slot = s.buf<int32_t>(B_W_SLOT, s.W);
+        int64_t* win_trig = s.buf<int64_t>(B_W_TRIG, s.W);
+        int64_t* win_n = s.buf<int64_t>(B_W_N, s.W);
+        unsigned long long* win_key = s.buf<unsigned long long>(B_W_KEY, s.W);
+        k_ses_evict_windows<<<ses_grid(ne, 256), 256, 0, stream>>>(
+            ne, list, (const unsigned long long*)s.b[B_L_KEY2].p, rep, rep_incl, cnt_n, win_slot, win_trig, win_n,
+            win_key);
+        if ((rc = s.gather(err))) return rc;
+        s.r_rounds = 1;
+        if ((rc = s.match(*this, err))) return rc;
+        for (int32_t w = 0; w < s.W; ++w) {  // the session is deleted whatever the report used
+          s.w_trim[w] = (int32_t)s.w_n[w];
+          if (s.w_su[w] <= 0) s.w_su[w] = -1;
+        }
+        s.result_round();
+      }
+      k_ses_clear<<<ses_grid(ne, 256), 256, 0, stream>>>(ne, list, s.st);
+      if ((rc = s.release_list(list, ne, err))) return rc;
+      s.r_evicted = ne;
+    }
+    s.W = 0;
+    return s.result_end(out, true, err);
+  });
+}
+
+int Matcher::sessions_snapshot(otr_session_snapshot* out, std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    SessionStore& s = *ses;
+    int rc;
+    HIPCHK(hipSetDevice(graph_state().device));
+    if (s.pending) return bad(err, "the last advance has not been committed");
+    memset(out, 0, sizeof(*out));
+    if ((rc = s.list_sessions(0, 0, err))) return rc;
+    const int32_t ns = s.n_list;
+    s.s_off.assign((size_t)ns + 1, 0);
+    out->point_off = s.s_off.data();
+    if (ns == 0) return OTR_OK;
+    const int32_t* list = (const int32_t*)s.b[B_L_SLOT2].p;
+    int32_t* rep = s.buf<int32_t>(B_L_REP, ns);
+    int64_t* cnt_n = s.buf<int64_t>(B_L_N, ns);
+    // (B_SUB_OFF, not the batch's offsets: an advance's empty batch stays what it is)
+    int64_t* off = s.buf<int64_t>(B_SUB_OFF, (size_t)ns + 1);
+    k_ses_evict_gate<<<ses_grid(ns, 256), 256, 0, stream>>>(ns, list, s.st, rep, cnt_n);
+    HIPCHK(hipMemsetAsync(off, 0, 8, stream));
+    if ((rc = s.scan64(cnt_n, off + 1, ns, err))) return rc;
+    const size_t ms = (size_t)s.cfg.max_sessions;
+    s.s_key.resize(ns);
+    s.s_slot.resize(ns);
+    s.all_sep.resize(ms);
+    s.all_last.resize(ms);
+    HIPCHK(hipMemcpyAsync(s.s_off.data(), off, 8 * ((size_t)ns + 1), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(s.s_key.data(), s.b[B_L_KEY2].p, 8 * (size_t)ns, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(s.s_slot.data(), list, 4 * (size_t)ns, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(s.all_sep.data(), s.st.max_sep, 4 * ms, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(s.all_last.data(), s.st.last, 8 * ms, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    const int64_t np = s.s_off[ns];
+    float* lat = s.buf<float>(B_S_LAT, np);
+    float* lon = s.buf<float>(B_S_LON, np);
+    int32_t* acc = s.buf<int32_t>(B_S_ACC, np);
+    int64_t* time = s.buf<int64_t>(B_G_TIME, np);
+    k_ses_gather<true><<<(unsigned)ns, 64, 0, stream>>>(ns, list, off, s.st, nullptr, nullptr, time, nullptr, nullptr,
+                                                        0, lat, lon, acc);
+    HIPCHK(hipGetLastError());
+    s.s_lat.resize(np);
+    s.s_lon.resize(np);
+    s.s_acc.resize(np);
+    s.s_time.resize(np);
+    HIPCHK(hipMemcpyAsync(s.s_lat.data(), lat, 4 * (size_t)np, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(s.s_lon.data(), lon, 4 * (size_t)np, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(s.s_acc.data(), acc, 4 * (size_t)np, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(s.s_time.data(), time, 8 * (size_t)np, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    s.s_sep.resize(ns);
+    s.s_last.resize(ns);
+    for (int32_t i = 0; i < ns; ++i) {
+      s.s_sep[i] = s.all_sep[s.s_slot[i]];
+      s.s_last[i] = s.all_last[s.s_slot[i]];
+    }
+    out->n_sessions = ns;
+    out->n_points = np;
+    out->key = (uint64_t*)s.s_key.data();
+    out->max_sep = s.s_sep.data();
+    out->last_update = s.s_last.data();
+    out->lat = s.s_lat.data();
+    out->lon = s.s_lon.data();
+    out->accuracy = s.s_acc.data();
+    out->time = s.s_time.data();
+    return OTR_OK;
+  });
+}
+
+}  // namespace otr

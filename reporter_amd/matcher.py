@@ -286,6 +286,88 @@ class Matcher:
             raise RuntimeError('otr_ingest failed (%d): %s' % (rc, _lib.last_error()))
         return r, IngestedBatch(r)
 
+    # --- session store (include/otr.h otr_sessions_*) ---------------
+    def _check(self, rc, what, refused=ValueError):
+        if rc == _lib.OTR_BAD_REQUEST:
+            raise refused('%s refused: %s' % (what, _lib.last_error()))
+        if rc != 0:
+            raise RuntimeError('%s failed (%d): %s' % (what, rc, _lib.last_error()))
+
+    def sessions_open(self, max_sessions, max_points, report_dist=500.0, report_count=10, report_time=60,
+                      session_gap=60000, mode='auto', report_levels=(0, 1), transition_levels=(0, 1),
+                      threshold_sec=15, batch_probes=0):
+        """Open this matcher's session store (defaults: BatchingProcessor's gates)."""
+        c = _lib.SessionConfig()
+        c.max_sessions, c.max_points = int(max_sessions), int(max_points)
+        c.report_dist, c.report_count, c.report_time = float(report_dist), int(report_count), int(report_time)
+        c.session_gap = int(session_gap)
+        c.mode = MODES[mode] if isinstance(mode, str) else int(mode)
+        c.report_levels = _lib.levels_mask(report_levels)
+        c.transition_levels = _lib.levels_mask(transition_levels)
+        c.threshold_sec = int(threshold_sec)
+        c.batch_probes = int(batch_probes)
+        self._check(self._L.otr_sessions_open(self._h, ctypes.byref(c)), 'otr_sessions_open')
+
+    def sessions_close(self):
+        self._check(self._L.otr_sessions_close(self._h), 'otr_sessions_close')
+
+    def _session_points(self, points, device):
+        """points: dict of key, lat, lon, accuracy, time, timestamp: numpy arrays, or device
+        pointers plus 'n' with device=True."""
+        p = _lib.SessionPoints()
+        if device:
+            p.n, p.memory = int(points['n']), _lib.OTR_MEM_DEVICE
+            for k, _ in _lib.SESSION_POINT_FIELDS:
+                setattr(p, k, points[k])
+        else:
+            keep = [np.ascontiguousarray(points[k], dt) for k, dt in _lib.SESSION_POINT_FIELDS]
+            if len({len(a) for a in keep}) != 1:
+                raise ValueError('session points: arrays of different lengths')
+            self._keep = keep
+            p.n, p.memory = len(keep[0]), _lib.OTR_MEM_HOST
+            for (k, _), a in zip(_lib.SESSION_POINT_FIELDS, keep):
+                setattr(p, k, a.ctypes.data)
+        return p
+
+    def sessions_push(self, points, device=False):
+        """otr_sessions_push: the chunk's windows and reports as a dict of numpy arrays
+        (_lib.session_result_to_numpy).  A refused chunk raises ValueError."""
+        p, r = self._session_points(points, device), _lib.SessionResult()
+        self._check(self._L.otr_sessions_push(self._h, ctypes.byref(p), ctypes.byref(r)), 'otr_sessions_push')
+        return _lib.session_result_to_numpy(r)
+
+    def sessions_punctuate(self, ts):
+        r = _lib.SessionResult()
+        self._check(self._L.otr_sessions_punctuate(self._h, int(ts), ctypes.byref(r)), 'otr_sessions_punctuate')
+        return _lib.session_result_to_numpy(r)
+
+    def sessions_advance(self, points=None, device=False):
+        """otr_sessions_advance: a new chunk, or None to continue the current one.  Returns
+        (TraceBatch in HBM, windows dict); n_traces == 0: the chunk is consumed."""
+        b = _lib.TraceBatch()
+        p = ctypes.byref(self._session_points(points, device)) if points is not None else None
+        self._check(self._L.otr_sessions_advance(self._h, p, ctypes.byref(b)), 'otr_sessions_advance')
+        return b, self.sessions_windows()
+
+    def sessions_commit(self, shape_used, status=None):
+        su = np.ascontiguousarray(shape_used, np.int32)
+        st = np.zeros(len(su), np.int32) if status is None else np.ascontiguousarray(status, np.int32)
+        self._check(self._L.otr_sessions_commit(self._h, su.ctypes.data, st.ctypes.data, _lib.OTR_MEM_HOST),
+                    'otr_sessions_commit')
+        return self.sessions_windows()
+
+    def sessions_windows(self):
+        r = _lib.SessionResult()
+        self._check(self._L.otr_sessions_windows(self._h, ctypes.byref(r)), 'otr_sessions_windows')
+        return _lib.session_result_to_numpy(r)
+
+    def sessions_snapshot(self):
+        """Every live session in key order: key, point_off, max_sep, last_update, lat, lon,
+        accuracy, time (numpy copies)."""
+        r = _lib.SessionSnapshot()
+        self._check(self._L.otr_sessions_snapshot(self._h, ctypes.byref(r)), 'otr_sessions_snapshot')
+        return _lib.snapshot_to_numpy(r)
+
     def match_batch_numpy(self, traces, **kw):
         r = self.match_batch(traces, copy_out=True, **kw)
         return _lib.result_to_numpy(r)

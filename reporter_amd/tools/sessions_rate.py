@@ -1,0 +1,118 @@
+"""Rate of the session store's push path (otr_sessions_push), host to host.
+
+Replays the traces of bench.py's deployed-configuration workload (c2dep: the metro graph, 100
+probes every 15 s, sigma 10 m, mode defaults) as one arrival stream: coordinates narrowed to
+float32, key = trace number, points in order of their time (stable), stream time in
+milliseconds.  The stream is pushed in chunks of `--chunk-s` seconds of stream time (1 and 10 by
+default) into a store with the reporter's gates (500 m, 10 points, 60 s), and punctuated at the
+end.  Per chunk size: probes/s over the wall time of all pushes (input arrays on the host,
+windows and reports back on the host), rounds per chunk, windows per round, and the split of
+the wall time into the matcher's batches (match_ms) and everything else (session kernels, copies,
+host).
+One warm-up replay, then `--repeats` timed ones: median, minimum and maximum are reported.
+
+    python -m reporter_amd.tools.sessions_rate --traces 2000 --out profiles/sessions_c2dep.json
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+T_BEGIN = 1483228800
+
+
+def stream(tr):
+    """The arrival stream of a gen.Traces batch and the chunk boundaries' stream times."""
+    key = np.repeat(np.arange(tr.n_traces, dtype=np.uint64) + 1, np.diff(tr.offsets))
+    tm = np.asarray(tr.time, np.int64)
+    order = np.argsort(tm, kind='stable')
+    acc = np.full(len(order), 10, np.int32) if tr.accuracy is None else np.ceil(tr.accuracy[order]).astype(np.int32)
+    return {'key': key[order], 'lat': np.asarray(tr.lat)[order].astype(np.float32),
+            'lon': np.asarray(tr.lon)[order].astype(np.float32), 'accuracy': acc, 'time': tm[order],
+            'timestamp': tm[order] * 1000}
+
+
+def replay(m, pts, cuts, max_points, batch_ms):
+    """One replay: a fresh store, every chunk pushed, a final punctuate."""
+    m.sessions_open(int(pts['key'].max()) + 1, max_points)
+    chunks = [{k: v[a:b] for k, v in pts.items()} for a, b in zip(cuts[:-1], cuts[1:])]
+    rounds = windows = reports = 0
+    dev_ms = match_ms = 0.0
+    t0 = time.perf_counter()
+    for c in chunks:
+        r = m.sessions_push(c)
+        rounds += r['n_rounds']
+        windows += r['n_windows']
+        reports += r['n_reports']
+        dev_ms += r['device_ms']
+        match_ms += r['match_ms']
+    wall = time.perf_counter() - t0
+    ev = m.sessions_punctuate(int(pts['timestamp'][-1]) + 10 ** 9)
+    m.sessions_close()
+    return {'wall_s': wall, 'rounds': rounds, 'windows': windows, 'reports': reports, 'stream_ms': dev_ms, 'match_ms': match_ms,
+            'evicted': ev['n_evicted'], 'eviction_windows': ev['n_windows'], 'chunks': len(chunks)}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--traces', type=int, default=2000, help='traces of the c2dep workload (bench.py --json-traces)')
+    ap.add_argument('--chunk-s', type=int, nargs='+', default=[1, 10])
+    ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--max-points', type=int, default=128)
+    ap.add_argument('--graphs', default=os.path.join(ROOT, 'build', 'graphs'))
+    ap.add_argument('--out', default=None)
+    args = ap.parse_args()
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    from reporter_amd import matcher as M
+    from reporter_amd.tools import gen
+    gpath = gen.graph_path('metro', args.graphs)
+    tr = gen.make_traces(gpath, args.traces, 100, 15, 10.0, 2, 0.0, 0.0, None, t_begin=T_BEGIN, t_spread=1800)
+    M.configure(M.default_config(gpath))
+    m = M.Matcher()
+    pts = stream(tr)
+    n = len(pts['key'])
+    # the device batch's fixed cost on this machine: a batch of one trace, timed alone
+    one = tr.subset([0])
+    m.match_batch(one, copy_out=False, copy_reports=True)
+    tb = []
+    for _ in range(20):
+        t0 = time.perf_counter()
+        m.match_batch(one, copy_out=False, copy_reports=True)
+        tb.append(1e3 * (time.perf_counter() - t0))
+    batch_ms = float(np.median(tb))
+    res = {'workload': 'c2dep: metro graph, %d traces x 100 probes @15 s, sigma 10 m, deployed configuration' % args.traces,
+           'probes': n, 'gates': '500 m, 10 points, 60 s; session_gap 60000; max_points %d' % args.max_points,
+           'method': 'arrays on the host -> otr_sessions_push per chunk -> windows and reports on the host; '
+                     '1 warm-up replay, %d timed; median [min, max]' % args.repeats,
+           'smallest_batch_ms': round(batch_ms, 3), 'chunks': {}}
+    for cs in args.chunk_s:
+        sec = (pts['time'] - pts['time'][0]) // cs
+        cuts = [0] + (np.flatnonzero(np.diff(sec)) + 1).tolist() + [n]
+        replay(m, pts, cuts, args.max_points, batch_ms)
+        runs = [replay(m, pts, cuts, args.max_points, batch_ms) for _ in range(args.repeats)]
+        rate = sorted(n / r['wall_s'] for r in runs)
+        r = runs[0]
+        wall = float(np.median([x['wall_s'] for x in runs]))
+        res['chunks']['%d_s' % cs] = {
+            'chunks': r['chunks'], 'points_per_chunk': round(n / r['chunks'], 1),
+            'probes_per_s': round(float(np.median(rate)), 1), 'probes_per_s_min_max': [round(rate[0], 1), round(rate[-1], 1)],
+            'wall_ms': round(1e3 * wall, 1), 'rounds_per_chunk': round(r['rounds'] / r['chunks'], 3),
+            'windows_per_round': round(r['windows'] / max(r['rounds'], 1), 2), 'windows': r['windows'],
+            'reports': r['reports'], 'evicted_at_end': r['evicted'],
+            'stream_ms': round(float(np.median([x['stream_ms'] for x in runs])), 1),
+            'match_ms': round(float(np.median([x['match_ms'] for x in runs])), 1),
+            'rounds_times_smallest_batch_ms': round(r['rounds'] * batch_ms, 1)}
+    line = json.dumps(res, indent=1)
+    print(line)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(line + '\n')
+
+
+if __name__ == '__main__':
+    main()
