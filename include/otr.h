@@ -592,6 +592,72 @@ int otr_sessions_windows(otr_matcher* m, otr_session_result* out);
 
 int otr_sessions_snapshot(otr_matcher* m, otr_session_snapshot* out);
 
+/* ---- tile store: the streaming reporter's anonymiser stage ------
+ * What sits between BatchingProcessor.forward (BatchingProcessor.java:108-141) and the tile
+ * files of AnonymisingProcessor.process / punctuate (AnonymisingProcessor.java:119-175,
+ * 222-266), in HBM: reports that pass Segment.valid are fanned out over their time buckets
+ * (TimeQuantisedTile.java:26-35) into OTR_TILE_RULES_STREAM rows, exactly the rows
+ * otr_match_batch writes with OTR_BATCH_TILE_ROWS, kept in arrival order across any number
+ * of adds, and only the flush sorts every (bucket, tile) file by Segment.compareTo, cleans it
+ * for privacy (clean, :155-175, over everything added since the last flush) and hands the
+ * files out.  One store per matcher, independent of the session store; its rows live in a
+ * buffer of their own and survive every other call on the matcher. */
+typedef struct otr_tile_store_config {
+  int64_t max_rows;      /* rows held between two flushes, 1 .. 1<<27 (sizeof(otr_tile_row) bytes each) */
+  int32_t quantisation;  /* bucket seconds, >= 60 (AnonymisingProcessor.java:78-80) */
+  int32_t privacy;       /* observations a pair needs, >= 1 (:72-74) */
+} otr_tile_store_config;
+
+typedef struct otr_tile_add_result {
+  int64_t n_reports, n_valid;    /* reports read / passing Segment.valid (forward()'s `reported`) */
+  int64_t n_rows_added, n_rows;  /* n_rows: held after the call */
+  float device_ms;               /* HIP-event time from the call's first device operation to its last */
+  int32_t reserved;
+} otr_tile_add_result;
+
+/* The flush's files: listed file f owns rows row_off[f] .. row_off[f+1]-1 (row_off has
+ * n_files + 1 elements), files by ascending `file`, within a file Segment.compareTo order
+ * (numeric id, next_id), stable in arrival order across all adds.  n_unclean: the file's rows
+ * before clean (the reference's log line).  Files cleaned to nothing are counted in
+ * n_files_empty and not listed.  Host and device copies, owned by the matcher until its
+ * next tile-store or otr_tiles_cull call. */
+typedef struct otr_tile_flush_result {
+  int64_t n_rows_in, n_rows;     /* before / after clean */
+  int32_t n_files, n_files_empty;
+  float device_ms;
+  int32_t reserved;
+  const otr_tile_row* rows;  const uint64_t* file;  const int64_t* row_off;  const int64_t* n_unclean;
+  const otr_tile_row* d_rows;  const uint64_t* d_file;  const int64_t* d_row_off;  const int64_t* d_n_unclean;
+} otr_tile_flush_result;
+
+/* Opens the matcher's tile store (OTR_BAD_REQUEST when it has one, or for a config out of
+ * range; OTR_DEVICE_ERROR naming the buffer when it does not fit the device).  Every other
+ * call below returns OTR_BAD_REQUEST on a matcher without a store. */
+int otr_tile_store_open(otr_matcher* m, const otr_tile_store_config* cfg);
+int otr_tile_store_close(otr_matcher* m);
+
+/* Adds the reports of the matcher's last otr_sessions_push / otr_sessions_punctuate result,
+ * read from its device arrays, in the reference's forward order: windows by ascending trigger
+ * (stable), the windows of an eviction in rank order, a window's reports in order, a report's
+ * buckets ascending.  Refused when there is no such result or it was added already.
+ * An add that would take the store beyond max_rows is refused with OTR_BAD_REQUEST (the
+ * message names max_rows) and the store untouched: flush, then add again. */
+int otr_tile_store_add_session(otr_matcher* m, otr_tile_add_result* out);
+
+/* The same from plain arrays in host or device memory, windows in the order given: window w
+ * owns reports rep_off[w] .. rep_off[w+1]-1 (rep_off[0] == 0, ascending); next_id OTR_NO_ID: none. */
+int otr_tile_store_add_reports(otr_matcher* m, int64_t n_windows, const int64_t* rep_off, const uint64_t* id,
+                               const uint64_t* next_id, const double* t0, const double* t1, const int32_t* length,
+                               const int32_t* queue_length, int32_t memory, otr_tile_add_result* out);
+
+/* Appends n finished rows (host or device memory), e.g. those received from another GPU. */
+int otr_tile_store_add_rows(otr_matcher* m, const otr_tile_row* rows, int64_t n, int32_t memory,
+                            otr_tile_add_result* out);
+
+/* Everything added since the last flush as cleaned files; the store is empty afterwards.  A
+ * flush of an empty store returns zero files. */
+int otr_tile_store_flush(otr_matcher* m, otr_tile_flush_result* out);
+
 /* report() (reporter_service.py:79-179) over n segment lists at once, evaluated by the
  * device code of the segment scan K7 (otr_report.h compiled for gfx950, one thread per
  * list) — what pins the device tail against the reference's own report() outputs.  Host

@@ -47,7 +47,9 @@ EXPORTS = ['otr_configure', 'otr_configure_json', 'otr_matcher_new', 'otr_matche
            'otr_max_batch_probes', 'otr_launch_max_items', 'otr_service_stats', 'otr_matched_points',
            'otr_edge_traversals', 'otr_edge_observations', 'otr_sessions_open', 'otr_sessions_close',
            'otr_sessions_push', 'otr_sessions_punctuate', 'otr_sessions_advance', 'otr_sessions_commit',
-           'otr_sessions_windows', 'otr_sessions_snapshot']
+           'otr_sessions_windows', 'otr_sessions_snapshot', 'otr_tile_store_open', 'otr_tile_store_close',
+           'otr_tile_store_add_session', 'otr_tile_store_add_reports', 'otr_tile_store_add_rows',
+           'otr_tile_store_flush']
 
 
 class ServiceSplit(ctypes.Structure):
@@ -204,6 +206,60 @@ class SessionSnapshot(ctypes.Structure):
                 [(k, P(ct)) for k, ct, _ in SNAPSHOT_FIELDS])
 
 
+class TileStoreConfig(ctypes.Structure):
+    """otr_tile_store_config (include/otr.h)."""
+    _fields_ = [('max_rows', ctypes.c_int64), ('quantisation', ctypes.c_int32), ('privacy', ctypes.c_int32)]
+
+
+TILE_ADD_COUNTS = ['n_reports', 'n_valid', 'n_rows_added', 'n_rows']
+
+
+class TileAddResult(ctypes.Structure):
+    """otr_tile_add_result (include/otr.h): what one add did to the tile store."""
+    _fields_ = ([(k, ctypes.c_int64) for k in TILE_ADD_COUNTS] +
+                [('device_ms', ctypes.c_float), ('reserved', ctypes.c_int32)])
+
+
+# the arrays of otr_tile_flush_result, in the struct's order (rows: TILE_ROW records)
+TILE_FLUSH_FIELDS = ['rows', 'file', 'row_off', 'n_unclean']
+TILE_FLUSH_COUNTS = ['n_rows_in', 'n_rows', 'n_files', 'n_files_empty']
+
+
+class TileFlushResult(ctypes.Structure):
+    """otr_tile_flush_result (include/otr.h): the flush's cleaned files, host and device arrays."""
+    _fields_ = ([('n_rows_in', ctypes.c_int64), ('n_rows', ctypes.c_int64), ('n_files', ctypes.c_int32),
+                 ('n_files_empty', ctypes.c_int32), ('device_ms', ctypes.c_float), ('reserved', ctypes.c_int32)] +
+                [(k, ctypes.c_void_p) for k in TILE_FLUSH_FIELDS] +
+                [('d_' + k, ctypes.c_void_p) for k in TILE_FLUSH_FIELDS])
+
+
+def _copy(ptr, n, dt):
+    """n records of dtype dt at the host address ptr, copied."""
+    if n <= 0 or not ptr:
+        return np.zeros(max(n, 0), dt)
+    return np.frombuffer(ctypes.string_at(ptr, n * np.dtype(dt).itemsize), dtype=dt).copy()
+
+
+def tile_add_to_dict(r):
+    out = {k: int(getattr(r, k)) for k in TILE_ADD_COUNTS}
+    out['device_ms'] = float(r.device_ms)
+    return out
+
+
+def tile_flush_to_numpy(r):
+    """Host arrays of an otr_tile_flush_result (copies), its counts and its device pointers."""
+    nf = int(r.n_files)
+    out = {k: int(getattr(r, k)) for k in TILE_FLUSH_COUNTS}
+    out['device_ms'] = float(r.device_ms)
+    out['rows'] = _copy(r.rows, int(r.n_rows), TILE_ROW)
+    out['file'] = _copy(r.file, nf, np.uint64)
+    out['row_off'] = _copy(r.row_off, nf + 1, np.int64)
+    out['n_unclean'] = _copy(r.n_unclean, nf, np.int64)
+    for k in TILE_FLUSH_FIELDS:
+        out['d_' + k] = int(getattr(r, 'd_' + k) or 0)
+    return out
+
+
 def session_result_to_numpy(r):
     """Host arrays of an otr_session_result (copies) and its counts."""
     nw, nr = int(r.n_windows), int(r.n_reports)
@@ -277,6 +333,15 @@ def lib():
         L.otr_sessions_commit.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
         L.otr_sessions_windows.argtypes = [ctypes.c_void_p, P(SessionResult)]
         L.otr_sessions_snapshot.argtypes = [ctypes.c_void_p, P(SessionSnapshot)]
+    if hasattr(L, 'otr_tile_store_open'):  # (an A/B build of an earlier round may lack them)
+        L.otr_tile_store_open.argtypes = [ctypes.c_void_p, P(TileStoreConfig)]
+        L.otr_tile_store_close.argtypes = [ctypes.c_void_p]
+        L.otr_tile_store_add_session.argtypes = [ctypes.c_void_p, P(TileAddResult)]
+        L.otr_tile_store_add_reports.argtypes = [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 7 + \
+            [ctypes.c_int32, P(TileAddResult)]
+        L.otr_tile_store_add_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                              P(TileAddResult)]
+        L.otr_tile_store_flush.argtypes = [ctypes.c_void_p, P(TileFlushResult)]
     L.otr_graph_info.argtypes = [P(ctypes.c_int64), P(ctypes.c_int64), P(ctypes.c_int64)]
     L.otr_matcher_stream.argtypes = [ctypes.c_void_p]
     L.otr_matcher_stream.restype = ctypes.c_void_p

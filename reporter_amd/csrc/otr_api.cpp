@@ -494,6 +494,35 @@ int otr_sessions_snapshot(otr_matcher* m, otr_session_snapshot* out) {
   OTR_SESSIONS_CALL(!m || !out, sessions_snapshot(out, &err));
 }
 
+// the tile store (K15): BatchingProcessor.forward → AnonymisingProcessor.process / punctuate
+// (BatchingProcessor.java:108-141, AnonymisingProcessor.java:119-175, 222-266), in HBM
+int otr_tile_store_open(otr_matcher* m, const otr_tile_store_config* cfg) {
+  OTR_SESSIONS_CALL(!m || !cfg, tile_store_open(cfg, &err));
+}
+
+int otr_tile_store_close(otr_matcher* m) { OTR_SESSIONS_CALL(!m, tile_store_close(&err)); }
+
+int otr_tile_store_add_session(otr_matcher* m, otr_tile_add_result* out) {
+  OTR_SESSIONS_CALL(!m || !out, tile_store_add_session(out, &err));
+}
+
+int otr_tile_store_add_reports(otr_matcher* m, int64_t n_windows, const int64_t* rep_off, const uint64_t* id,
+                               const uint64_t* next_id, const double* t0, const double* t1, const int32_t* length,
+                               const int32_t* queue_length, int32_t memory, otr_tile_add_result* out) {
+  OTR_SESSIONS_CALL(!m || !out,
+                    tile_store_add_reports(n_windows, rep_off, id, next_id, t0, t1, length, queue_length, memory, out,
+                                           &err));
+}
+
+int otr_tile_store_add_rows(otr_matcher* m, const otr_tile_row* rows, int64_t n, int32_t memory,
+                            otr_tile_add_result* out) {
+  OTR_SESSIONS_CALL(!m || !out, tile_store_add_rows(rows, n, memory, out, &err));
+}
+
+int otr_tile_store_flush(otr_matcher* m, otr_tile_flush_result* out) {
+  OTR_SESSIONS_CALL(!m || !out, tile_store_flush(out, &err));
+}
+
 // simple_reporter.py:188-195: ','.join([id, next, duration, '1', length, queue, start, end,
 // source, mode.upper()]) + os.linesep
 // Segment.appendToStringBuffer (Segment.java:59-74) for OTR_TILE_RULES_STREAM

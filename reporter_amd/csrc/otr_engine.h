@@ -84,9 +84,33 @@ void turn_table(double factor, int32_t* tab181);
 struct SessionStore;                    // otr_sessions.hip (K14)
 void sessions_destroy(SessionStore* s);  // frees the store's device memory
 
+// the reports of a session store's last push / punctuate result, in HBM (for the tile
+// store's add_session): valid until the store's next session call
+struct SessionReports {
+  int64_t n_windows, n_reports;
+  const int64_t *trigger, *rep_off;
+  const unsigned long long *id, *next_id;
+  const double *t0, *t1;
+  const int32_t *length, *queue_length;
+  bool* added;  // set once a tile store has taken them
+};
+bool sessions_last_reports(SessionStore* s, SessionReports* out);  // false: no such result
+
+struct TileStore;                      // otr_tilestore.hip (K15)
+void tile_store_destroy(TileStore* s);  // frees the store's device memory
+
+// what cull_device leaves in the matcher's cull slots
+struct CulledRows {
+  const otr_tile_row* sorted;  // all n rows in file, then rule order
+  const otr_tile_row* kept;    // the n_kept rows the cull keeps, same order
+  const int64_t* kept_incl;    // [n] inclusive count of kept rows along `sorted`
+  int64_t n_kept;
+};
+
 struct Matcher {
   hipStream_t stream = nullptr;
   SessionStore* ses = nullptr;  // the session store (otr_sessions_open), owned
+  TileStore* tst = nullptr;     // the tile store (otr_tile_store_open), owned
   std::vector<DevBuf> bufs;
   GSlab gslab[2];
   std::vector<int32_t> h_turn;
@@ -143,6 +167,10 @@ struct Matcher {
   int run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch_result* out, std::string* err);
   int tiles_cull_impl(const otr_tile_row* rows, int64_t n, int memory, int privacy, int rules,
                       const otr_tile_row** out, int64_t* n_out, std::string* err);
+  // sort + cull of rows already in HBM, results left in HBM (the tile store's flush)
+  int cull_device(const otr_tile_row* d_in, int64_t n, int privacy, int rules, CulledRows* out, std::string* err);
+  int cull_device_impl(const otr_tile_row* d_in, int64_t n, int privacy, int rules, CulledRows* out,
+                       std::string* err);
   int edge_observations_impl(int quantisation, otr_hist_entry** d_entries, int64_t* n, std::string* err);
   int hist_reduce_impl(const void* in, int64_t n, int memory, int rows_in, int privacy, const otr_hist_entry** out,
                        int64_t* n_out, std::string* err);
@@ -160,6 +188,15 @@ struct Matcher {
   int sessions_commit(const int32_t* shape_used, const int32_t* status, int memory, std::string* err);
   int sessions_windows(otr_session_result* out, std::string* err);
   int sessions_snapshot(otr_session_snapshot* out, std::string* err);
+  // the tile store (K15, otr_tilestore.hip)
+  int tile_store_open(const otr_tile_store_config* cfg, std::string* err);
+  int tile_store_close(std::string* err);
+  int tile_store_add_session(otr_tile_add_result* out, std::string* err);
+  int tile_store_add_reports(int64_t n_windows, const int64_t* rep_off, const uint64_t* id, const uint64_t* next_id,
+                             const double* t0, const double* t1, const int32_t* length, const int32_t* queue_length,
+                             int memory, otr_tile_add_result* out, std::string* err);
+  int tile_store_add_rows(const otr_tile_row* rows, int64_t n, int memory, otr_tile_add_result* out, std::string* err);
+  int tile_store_flush(otr_tile_flush_result* out, std::string* err);
   ~Matcher();
 };
 

@@ -526,6 +526,7 @@ static int oom_error(hipStream_t stream, const DeviceOom& o, std::string* err) {
 
 Matcher::~Matcher() {
   if (ses) sessions_destroy(ses);
+  if (tst) tile_store_destroy(tst);
   for (auto& b : bufs)
     if (b.p) (void)hipFree(b.p);
   for (auto& sl : gslab)
@@ -2574,8 +2575,42 @@ int Matcher::tiles_cull_impl(const otr_tile_row* rows, int64_t n, int memory, in
     if (err) *err = "too many tile rows for one call";
     return OTR_BAD_REQUEST;
   }
-  // staging: in (copy of the caller's rows), sorted, kept; permutation + radix keys
+  // staging: a copy of the caller's rows
   otr_tile_row* d_in = need<otr_tile_row>(S_ROWS_IN, n);
+  if (!d_in) {
+    if (err) *err = "device allocation failed (tiles)";
+    return OTR_DEVICE_ERROR;
+  }
+  HIPCHK(hipMemcpyAsync(d_in, rows, sizeof(otr_tile_row) * n,
+                        memory == OTR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+  CulledRows c;
+  const int rc = cull_device_impl(d_in, n, privacy, rules, &c, err);
+  if (rc != OTR_OK) return rc;
+  const int64_t nk = c.n_kept;
+  h_tile_rows.resize(nk > 0 ? nk : 1);
+  if (nk > 0) HIPCHK(hipMemcpy(h_tile_rows.data(), c.kept, sizeof(otr_tile_row) * nk, hipMemcpyDeviceToHost));
+  HIPCHK(hipGetLastError());
+  *out = h_tile_rows.data();
+  *n_out = nk;
+  return OTR_OK;
+}
+
+int Matcher::cull_device(const otr_tile_row* d_in, int64_t n, int privacy, int rules, CulledRows* out,
+                         std::string* err) {
+  try {
+    return cull_device_impl(d_in, n, privacy, rules, out, err);
+  } catch (const DeviceOom& o) {
+    return oom_error(stream, o, err);
+  }
+}
+
+// The sort, run split, k_cull_runs and compaction over 0 < n < 2^31 rows in HBM (d_in: any
+// device memory but the cull slots below; it is only read).  Leaves the sorted rows, the
+// kept rows and the inclusive scan of the sorted rows' keep flags in the matcher's cull
+// slots, with the stream drained.
+int Matcher::cull_device_impl(const otr_tile_row* d_in, int64_t n, int privacy, int rules, CulledRows* out,
+                              std::string* err) {
+  // staging: sorted, kept; permutation + radix keys
   otr_tile_row* d = need<otr_tile_row>(S_ROWS_OUT, n);
   otr_tile_row* d_kept = need<otr_tile_row>(S_ROWS_KEPT, n);
   int32_t* perm_a = need<int32_t>(S_IDX_A, n);
@@ -2586,12 +2621,10 @@ int Matcher::tiles_cull_impl(const otr_tile_row* rows, int64_t n, int memory, in
   int64_t* keep = need<int64_t>(S_KEEP, n);
   int64_t* pos = need<int64_t>(S_POS_SCAN, n);
   int64_t* fstart = need<int64_t>(S_FILE_START, n);
-  if (!d_in || !d || !d_kept || !perm_a || !perm_b || !key_a || !key_b || !head || !keep || !pos || !fstart) {
+  if (!d || !d_kept || !perm_a || !perm_b || !key_a || !key_b || !head || !keep || !pos || !fstart) {
     if (err) *err = "device allocation failed (tiles)";
     return OTR_DEVICE_ERROR;
   }
-  HIPCHK(hipMemcpyAsync(d_in, rows, sizeof(otr_tile_row) * n,
-                        memory == OTR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
   const int ni = (int)n;
   size_t tb_sort = 0, tb_scan = 0;
   HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, key_a, key_b, perm_a, perm_b, ni, 0, 64, stream));
@@ -2644,11 +2677,10 @@ int Matcher::tiles_cull_impl(const otr_tile_row* rows, int64_t n, int memory, in
     if (err) *err = "tile cull compaction failed";
     return OTR_DEVICE_ERROR;
   }
-  h_tile_rows.resize(nk > 0 ? nk : 1);
-  if (nk > 0) HIPCHK(hipMemcpy(h_tile_rows.data(), d_kept, sizeof(otr_tile_row) * nk, hipMemcpyDeviceToHost));
-  HIPCHK(hipGetLastError());
-  *out = h_tile_rows.data();
-  *n_out = nk;
+  out->sorted = d;
+  out->kept = d_kept;
+  out->kept_incl = pos;
+  out->n_kept = nk;
   return OTR_OK;
 }
 

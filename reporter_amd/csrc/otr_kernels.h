@@ -23,6 +23,7 @@
 #include "otr_mincode.h"  // IN-gap codes of the node tables (mi_of / in_gap, mf8_of / mf8_gap)
 #include "otr_pred.h"     // the round's 32-bit predicates (in_final32, target_final32)
 #include "otr_report.h"
+#include "otr_tilerow.h"  // the stream rules' rows and the wave scan, shared with K15
 
 // the first tier's table (slots per search, two searches per wave) and its load limit in
 // eighths (A/B knobs)
@@ -2963,16 +2964,6 @@ __global__ __launch_bounds__(64) void k_compact(CompactArgs a) {
   }
 }
 
-// inclusive prefix sum over the wave (lane order)
-__device__ inline unsigned long long wave_incl_scan_u64(unsigned long long v) {
-  const int l = lane_id();
-  for (int o = 1; o < OTR_WAVE; o <<= 1) {
-    const unsigned long long u = __shfl_up(v, o);
-    if (l >= o) v += u;
-  }
-  return v;
-}
-
 // ------------------------------------------------------------------------------
 // K8: simple_reporter filter + hour bucketing (simple_reporter.py:176-196) into a
 // dense [hour][segment][speed bin] count histogram; one wave per trace, a lane per
@@ -3070,17 +3061,7 @@ __global__ __launch_bounds__(256) void k_tile_rows(TileArgs a) {
         len = a.rep_length[co + r];
         qu = a.rep_queue[co + r];
         if (a.rules == OTR_TILE_RULES_STREAM) {
-          // BatchingProcessor.java:119-126 (Segment.valid, Segment.java:38-40) and
-          // TimeQuantisedTile.getTiles (TimeQuantisedTile.java:26-35): buckets from the
-          // truncated times, no span limit; duration Math.round (ties up), Segment.java:65-71
-          if (t0 > 0 && t1 > 0 && t1 > t0 && len > 0 && qu >= 0) {
-            sp.duration = py2_round_int(t1 - t0);
-            sp.start = (int64_t)floor(t0);
-            sp.end = (int64_t)ceil(t1);
-            sp.min_bucket = (int64_t)t0 / a.quantisation;
-            sp.max_bucket = (int64_t)t1 / a.quantisation;
-            keep = true;
-          }
+          keep = stream_span(t0, t1, len, qu, a.quantisation, &sp);
         } else if (bucket_keep(t0, t1, len, qu)) {
           sp = bucket_span(t0, t1, first, last, a.quantisation);
           keep = sp.ok;
@@ -3090,23 +3071,10 @@ __global__ __launch_bounds__(256) void k_tile_rows(TileArgs a) {
       const unsigned long long incl = wave_incl_scan_u64(nb);
       if (a.rows && keep) {
         const unsigned long long id = a.rep_id[co + r], nx = a.rep_next[co + r];
-        // the report's 20 km/h speed bin, as K8 bins it (oracle/tiles.py speed_bin)
-        const double bq = (((double)len / (t1 - t0)) * 3.6) / 20.0;
-        const int speed_bin = bq >= (double)(OTR_HIST_BINS - 1) ? OTR_HIST_BINS - 1 : (bq < 0.0 ? 0 : (int)bq);
+        const int speed_bin = tile_speed_bin(len, t0, t1);
         int64_t k = base + (int64_t)(incl - nb);
-        for (int64_t bk = sp.min_bucket; bk <= sp.max_bucket; ++bk, ++k) {
-          otr_tile_row row;
-          row.file = ((unsigned long long)bk << 25) | ((id & 7ull) << 22) | ((id >> 3) & 0x3FFFFFull);
-          row.id = id;
-          row.next_id = nx == OTR_NO_ID ? OTR_INVALID_SEGMENT_ID : nx;
-          row.start = sp.start;
-          row.end = sp.end;
-          row.duration = (int32_t)sp.duration;
-          row.length = len;
-          row.queue_length = qu;
-          row.speed_bin = speed_bin;
-          a.rows[k] = row;
-        }
+        for (int64_t bk = sp.min_bucket; bk <= sp.max_bucket; ++bk, ++k)
+          a.rows[k] = tile_row_of(bk, id, nx, sp, len, qu, speed_bin);
       }
       base += (int64_t)__shfl(incl, OTR_WAVE - 1);
     }

@@ -92,6 +92,9 @@ struct SessionStore {
   std::vector<double> r_t0, r_t1;
   int32_t r_rounds = 0, r_evicted = 0, forced0 = 0, dropped0 = 0;
   double r_match_ms = 0.0;
+  // the last push / punctuate result's reports are in the B_R_* buffers (res_have), and
+  // whether a tile store has taken them
+  bool res_have = false, res_added = false;
   // snapshot
   std::vector<unsigned long long> s_key;
   std::vector<int64_t> s_off, s_last, s_time, all_last;
@@ -408,6 +411,7 @@ int SessionStore::commit(const int32_t* su, const int32_t* status, int memory, s
 }
 
 void SessionStore::result_begin() {
+  res_have = false;
   for (auto* v : {&r_key, &r_id, &r_next}) v->clear();
   for (auto* v : {&r_trig, &r_off}) v->clear();
   for (auto* v : {&r_n, &r_su, &r_status, &r_trim, &r_len, &r_queue}) v->clear();
@@ -539,7 +543,25 @@ int SessionStore::result_end(otr_session_result* out, bool with_device, std::str
   HIPCHK(hipEventRecord(ev[1], stream));
   HIPCHK(hipStreamSynchronize(stream));
   HIPCHK(hipEventElapsedTime(&out->device_ms, ev[0], ev[1]));
+  res_have = true;
+  res_added = false;
   return OTR_OK;
+}
+
+bool sessions_last_reports(SessionStore* s, SessionReports* out) {
+  if (!s || !s->res_have) return false;
+  out->n_windows = (int64_t)s->r_key.size();
+  out->n_reports = (int64_t)s->r_id.size();
+  out->trigger = (const int64_t*)s->b[B_R_TRIG].p;
+  out->rep_off = (const int64_t*)s->b[B_R_OFF].p;
+  out->id = (const unsigned long long*)s->b[B_R_ID].p;
+  out->next_id = (const unsigned long long*)s->b[B_R_NEXT].p;
+  out->t0 = (const double*)s->b[B_R_T0].p;
+  out->t1 = (const double*)s->b[B_R_T1].p;
+  out->length = (const int32_t*)s->b[B_R_LEN].p;
+  out->queue_length = (const int32_t*)s->b[B_R_QUEUE].p;
+  out->added = &s->res_added;
+  return true;
 }
 
 // sessions (all live ones, or the stale ones at ts) in ascending key order: n_list of them

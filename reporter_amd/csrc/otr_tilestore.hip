@@ -1,0 +1,465 @@
+// otr_tilestore.hip — host side of the tile store (K15, otr_tilestore.h): the store's row
+// buffer, the two passes of an add (count, scan, capacity check, write) and the flush (the
+// matcher's device cull, then the per-file table).  include/otr.h otr_tile_store_* for the rules.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "otr_engine.h"
+#include "otr_tilestore.h"
+
+#define HIPCHK(x)                                                                        \
+  do {                                                                                   \
+    hipError_t e_ = (x);                                                                 \
+    if (e_ != hipSuccess) {                                                              \
+      if (err) *err = std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x;    \
+      return OTR_DEVICE_ERROR;                                                           \
+    }                                                                                    \
+  } while (0)
+
+namespace otr {
+
+namespace {
+
+struct TstOom {
+  const char* name;
+  size_t bytes;
+};
+
+unsigned tst_grid(int64_t n, int threads) { return (unsigned)std::max<int64_t>(1, (n + threads - 1) / threads); }
+
+constexpr int64_t kTstMaxRows = (int64_t)1 << 27;
+
+// growable buffers of an add and of a flush's file table (the rows are not among them)
+enum TstBuf {
+  T_OFF, T_ID, T_NEXT, T_T0, T_T1, T_LEN, T_QUEUE, T_KEY_A, T_KEY_B, T_IDX_A, T_IDX_B, T_CNT, T_ROW_OFF, T_TMP,
+  T_F_HEAD, T_F_INCL, T_F_START, T_F_LISTED, T_F_LINCL, T_F_FILE, T_F_ROW_OFF, T_F_UNCLEAN,
+  T_NUM
+};
+const char* const kTstName[T_NUM] = {
+    "report offsets", "report id", "report next id", "report t0", "report t1", "report length", "report queue length",
+    "window order key", "sorted window order key", "window index", "window order", "window row counts",
+    "window row offsets", "scan / sort workspace", "file head", "file rank", "file start", "file listed",
+    "listed file rank", "file table files", "file table row offsets", "file table unclean counts"};
+
+}  // namespace
+
+struct TileStore {
+  otr_tile_store_config cfg{};
+  hipStream_t stream = nullptr;
+  otr_tile_row* rows = nullptr;  // [max_rows], the store's own allocation
+  unsigned long long* counters = nullptr;
+  int64_t n_rows = 0;
+  hipEvent_t ev[2];
+  bool ev_init = false;
+  struct {
+    void* p = nullptr;
+    size_t bytes = 0;
+  } b[T_NUM];
+  // what a flush returns
+  std::vector<otr_tile_row> h_rows;
+  std::vector<unsigned long long> h_file;
+  std::vector<int64_t> h_row_off, h_unclean;
+
+  template <class T>
+  T* buf(int slot, size_t n) {
+    const size_t bytes = (n ? n : 1) * sizeof(T);
+    if (b[slot].bytes < bytes) {
+      if (b[slot].p) (void)hipFree(b[slot].p);
+      b[slot].p = nullptr;
+      b[slot].bytes = 0;
+      const size_t nb = bytes + bytes / 4;
+      if (hipMalloc(&b[slot].p, nb) != hipSuccess) {
+        (void)hipGetLastError();
+        b[slot].p = nullptr;
+        throw TstOom{kTstName[slot], nb};
+      }
+      b[slot].bytes = nb;
+    }
+    return (T*)b[slot].p;
+  }
+
+  int scan64(const int64_t* in, int64_t* out, int64_t n, std::string* err);
+  int alloc(std::string* err);
+  int add(const StoreArgs& in, int64_t n_reports, otr_tile_add_result* out, std::string* err);
+  void add_result(otr_tile_add_result* out, int64_t n_reports, int64_t n_valid, int64_t added) const;
+  int finish(float* device_ms, std::string* err);
+};
+
+void tile_store_destroy(TileStore* s) {
+  if (!s) return;
+  if (s->stream) (void)hipStreamSynchronize(s->stream);
+  if (s->rows) (void)hipFree(s->rows);
+  if (s->counters) (void)hipFree(s->counters);
+  for (auto& x : s->b)
+    if (x.p) (void)hipFree(x.p);
+  if (s->ev_init)
+    for (auto& e : s->ev) (void)hipEventDestroy(e);
+  delete s;
+}
+
+int TileStore::scan64(const int64_t* in, int64_t* out, int64_t n, std::string* err) {
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, in, out, (int)n, stream));
+  void* tmp = buf<char>(T_TMP, tb);
+  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, in, out, (int)n, stream));
+  return OTR_OK;
+}
+
+int TileStore::alloc(std::string* err) {
+  const size_t bytes = sizeof(otr_tile_row) * (size_t)cfg.max_rows;
+  if (hipMalloc((void**)&rows, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    rows = nullptr;
+    throw TstOom{"tile store rows", bytes};
+  }
+  if (hipMalloc((void**)&counters, 8 * TST_WORDS) != hipSuccess) {
+    (void)hipGetLastError();
+    counters = nullptr;
+    throw TstOom{"tile store counters", 8 * TST_WORDS};
+  }
+  for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+  ev_init = true;
+  return OTR_OK;
+}
+
+void TileStore::add_result(otr_tile_add_result* out, int64_t n_reports, int64_t n_valid, int64_t added) const {
+  memset(out, 0, sizeof(*out));
+  out->n_reports = n_reports;
+  out->n_valid = n_valid;
+  out->n_rows_added = added;
+  out->n_rows = n_rows;
+}
+
+// ev[0] was recorded at the call's start
+int TileStore::finish(float* device_ms, std::string* err) {
+  HIPCHK(hipEventRecord(ev[1], stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  HIPCHK(hipEventElapsedTime(device_ms, ev[0], ev[1]));
+  return OTR_OK;
+}
+
+// in: the windows, their order and the report arrays in HBM (ev[0] recorded).  Pass 1 counts
+// every window's rows, the scan places them, and only a total that fits is written.
+int TileStore::add(const StoreArgs& in, int64_t n_reports, otr_tile_add_result* out, std::string* err) {
+  int rc;
+  const int64_t W = in.n_windows;
+  StoreArgs a = in;
+  a.quantisation = cfg.quantisation;
+  a.row_cnt = buf<int64_t>(T_CNT, W);
+  int64_t* off = buf<int64_t>(T_ROW_OFF, (size_t)W + 1);
+  a.counters = counters;
+  a.row_off = off;
+  a.rows = rows + n_rows;
+  const unsigned blocks = tst_grid(W, kStoreWaves);
+  HIPCHK(hipMemsetAsync(counters, 0, 8 * TST_WORDS, stream));
+  HIPCHK(hipMemsetAsync(off, 0, 8, stream));
+  k_store_rows<false><<<blocks, 256, 0, stream>>>(a);
+  HIPCHK(hipGetLastError());
+  if ((rc = scan64(a.row_cnt, off + 1, W, err))) return rc;
+  int64_t total = 0;
+  unsigned long long h_cnt[TST_WORDS] = {0, 0};
+  HIPCHK(hipMemcpyAsync(&total, off + W, 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(h_cnt, counters, sizeof(h_cnt), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (h_cnt[TST_BAD_OFF]) {
+    if (err) *err = "rep_off does not start at 0 or is not ascending";
+    return OTR_BAD_REQUEST;
+  }
+  if (total < 0 || total > cfg.max_rows - n_rows) {
+    if (err)
+      *err = "the add would take the tile store beyond max_rows (" + std::to_string(n_rows) + " rows held, " +
+             (total >= (int64_t)kStoreBucketClamp ? std::string("more than ") + std::to_string(kTstMaxRows)
+                                                  : std::to_string(total)) +
+             " to add, max_rows " + std::to_string(cfg.max_rows) + "): flush first";
+    return OTR_BAD_REQUEST;
+  }
+  if (total > 0) {
+    k_store_rows<true><<<blocks, 256, 0, stream>>>(a);
+    HIPCHK(hipGetLastError());
+  }
+  float ms = 0.f;
+  if ((rc = finish(&ms, err))) return rc;
+  n_rows += total;
+  add_result(out, n_reports, (int64_t)h_cnt[TST_VALID], total);
+  out->device_ms = ms;
+  return OTR_OK;
+}
+
+// ---- the matcher's entry points -------------------------------------------------------------
+
+namespace {
+
+int bad(std::string* err, const std::string& what) {
+  if (err) *err = what;
+  return OTR_BAD_REQUEST;
+}
+
+template <class F>
+int guarded(Matcher& m, std::string* err, bool need_store, F&& f) {
+  if (need_store && !m.tst) return bad(err, "no tile store: call otr_tile_store_open first");
+  try {
+    return f();
+  } catch (const TstOom& o) {
+    if (m.stream) (void)hipStreamSynchronize(m.stream);
+    (void)hipGetLastError();
+    if (err)
+      *err = std::string("out of device memory: tile store buffer '") + o.name + "' needs " +
+             std::to_string((o.bytes >> 20) + 1) + " MiB";
+    return OTR_DEVICE_ERROR;
+  }
+}
+
+}  // namespace
+
+int Matcher::tile_store_open(const otr_tile_store_config* cfg, std::string* err) {
+  if (tst) return bad(err, "the matcher already has a tile store");
+  if (cfg->max_rows < 1 || cfg->max_rows > kTstMaxRows || cfg->quantisation < 60 || cfg->privacy < 1)
+    return bad(err, "tile store config out of range (max_rows 1 .. 1<<27, quantisation >= 60, privacy >= 1)");
+  HIPCHK(hipSetDevice(graph_state().device));
+  if (!stream) HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+  TileStore* s = new TileStore();
+  s->cfg = *cfg;
+  s->stream = stream;
+  const int rc = guarded(*this, err, false, [&] { return s->alloc(err); });
+  if (rc != OTR_OK) {
+    tile_store_destroy(s);
+    return rc;
+  }
+  tst = s;
+  return OTR_OK;
+}
+
+int Matcher::tile_store_close(std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    tile_store_destroy(tst);
+    tst = nullptr;
+    return OTR_OK;
+  });
+}
+
+int Matcher::tile_store_add_session(otr_tile_add_result* out, std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    TileStore& s = *tst;
+    int rc;
+    SessionReports sr;
+    if (!sessions_last_reports(ses, &sr))
+      return bad(err, "no session result to add: call otr_sessions_push or otr_sessions_punctuate first");
+    if (*sr.added) return bad(err, "the last session result was already added");
+    HIPCHK(hipSetDevice(graph_state().device));
+    const int64_t W = sr.n_windows;
+    if (W >= (int64_t)INT32_MAX) return bad(err, "too many windows for one add");
+    if (W == 0) {
+      *sr.added = true;
+      s.add_result(out, 0, 0, 0);
+      return OTR_OK;
+    }
+    HIPCHK(hipEventRecord(s.ev[0], stream));
+    // the forward order: a stable sort of the windows by trigger (an eviction's by rank)
+    unsigned long long* key_a = s.buf<unsigned long long>(T_KEY_A, W);
+    unsigned long long* key_b = s.buf<unsigned long long>(T_KEY_B, W);
+    int32_t* idx_a = s.buf<int32_t>(T_IDX_A, W);
+    int32_t* idx_b = s.buf<int32_t>(T_IDX_B, W);
+    k_store_order_key<<<tst_grid(W, 256), 256, 0, stream>>>(sr.trigger, W, key_a, idx_a);
+    size_t tb = 0;
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key_a, key_b, idx_a, idx_b, (int)W, 0, 64, stream));
+    void* tmp = s.buf<char>(T_TMP, tb);
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key_a, key_b, idx_a, idx_b, (int)W, 0, 64, stream));
+    StoreArgs a{};
+    a.n_windows = W;
+    a.order = idx_b;
+    a.rep_off = sr.rep_off;
+    a.id = sr.id;
+    a.next_id = sr.next_id;
+    a.t0 = sr.t0;
+    a.t1 = sr.t1;
+    a.length = sr.length;
+    a.queue = sr.queue_length;
+    if ((rc = s.add(a, sr.n_reports, out, err))) return rc;
+    *sr.added = true;
+    return OTR_OK;
+  });
+}
+
+int Matcher::tile_store_add_reports(int64_t n_windows, const int64_t* rep_off, const uint64_t* id,
+                                    const uint64_t* next_id, const double* t0, const double* t1,
+                                    const int32_t* length, const int32_t* queue_length, int memory,
+                                    otr_tile_add_result* out, std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    TileStore& s = *tst;
+    const int64_t W = n_windows;
+    if (W >= (int64_t)INT32_MAX) return bad(err, "too many windows for one add");
+    if (W <= 0) {
+      s.add_result(out, 0, 0, 0);
+      return OTR_OK;
+    }
+    if (!rep_off) return bad(err, "null argument");
+    HIPCHK(hipSetDevice(graph_state().device));
+    int64_t n_reports = 0;
+    StoreArgs a{};
+    a.n_windows = W;
+    if (memory == OTR_MEM_DEVICE) {
+      HIPCHK(hipMemcpy(&n_reports, rep_off + W, 8, hipMemcpyDeviceToHost));
+      if (n_reports < 0) return bad(err, "rep_off does not start at 0 or is not ascending");
+      if (n_reports > 0 && (!id || !next_id || !t0 || !t1 || !length || !queue_length)) return bad(err, "null argument");
+      HIPCHK(hipEventRecord(s.ev[0], stream));
+      a.rep_off = rep_off;
+      a.id = (const unsigned long long*)id;
+      a.next_id = (const unsigned long long*)next_id;
+      a.t0 = t0;
+      a.t1 = t1;
+      a.length = length;
+      a.queue = queue_length;
+    } else {
+      if (rep_off[0] != 0) return bad(err, "rep_off does not start at 0 or is not ascending");
+      for (int64_t w = 0; w < W; ++w)
+        if (rep_off[w + 1] < rep_off[w]) return bad(err, "rep_off does not start at 0 or is not ascending");
+      n_reports = rep_off[W];
+      if (n_reports > 0 && (!id || !next_id || !t0 || !t1 || !length || !queue_length)) return bad(err, "null argument");
+      const size_t nr = (size_t)n_reports;
+      int64_t* d_off = s.buf<int64_t>(T_OFF, (size_t)W + 1);
+      unsigned long long* d_id = s.buf<unsigned long long>(T_ID, nr);
+      unsigned long long* d_next = s.buf<unsigned long long>(T_NEXT, nr);
+      double* d_t0 = s.buf<double>(T_T0, nr);
+      double* d_t1 = s.buf<double>(T_T1, nr);
+      int32_t* d_len = s.buf<int32_t>(T_LEN, nr);
+      int32_t* d_queue = s.buf<int32_t>(T_QUEUE, nr);
+      HIPCHK(hipEventRecord(s.ev[0], stream));
+      HIPCHK(hipMemcpyAsync(d_off, rep_off, 8 * ((size_t)W + 1), hipMemcpyHostToDevice, stream));
+      if (nr) {
+        HIPCHK(hipMemcpyAsync(d_id, id, 8 * nr, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(d_next, next_id, 8 * nr, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(d_t0, t0, 8 * nr, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(d_t1, t1, 8 * nr, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(d_len, length, 4 * nr, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(d_queue, queue_length, 4 * nr, hipMemcpyHostToDevice, stream));
+      }
+      a.rep_off = d_off;
+      a.id = d_id;
+      a.next_id = d_next;
+      a.t0 = d_t0;
+      a.t1 = d_t1;
+      a.length = d_len;
+      a.queue = d_queue;
+    }
+    return s.add(a, n_reports, out, err);
+  });
+}
+
+int Matcher::tile_store_add_rows(const otr_tile_row* rows, int64_t n, int memory, otr_tile_add_result* out,
+                                 std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    TileStore& s = *tst;
+    if (n <= 0) {
+      s.add_result(out, 0, 0, 0);
+      return OTR_OK;
+    }
+    if (!rows) return bad(err, "null argument");
+    if (n > s.cfg.max_rows - s.n_rows)
+      return bad(err, "the add would take the tile store beyond max_rows (" + std::to_string(s.n_rows) +
+                          " rows held, " + std::to_string(n) + " to add, max_rows " +
+                          std::to_string(s.cfg.max_rows) + "): flush first");
+    HIPCHK(hipSetDevice(graph_state().device));
+    HIPCHK(hipEventRecord(s.ev[0], stream));
+    HIPCHK(hipMemcpyAsync(s.rows + s.n_rows, rows, sizeof(otr_tile_row) * (size_t)n,
+                          memory == OTR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+    float ms = 0.f;
+    int rc;
+    if ((rc = s.finish(&ms, err))) return rc;
+    s.n_rows += n;
+    s.add_result(out, 0, 0, n);
+    out->device_ms = ms;
+    return OTR_OK;
+  });
+}
+
+int Matcher::tile_store_flush(otr_tile_flush_result* out, std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    TileStore& s = *tst;
+    int rc;
+    memset(out, 0, sizeof(*out));
+    HIPCHK(hipSetDevice(graph_state().device));
+    const int64_t n = s.n_rows;
+    s.h_rows.clear();
+    s.h_file.clear();
+    s.h_unclean.clear();
+    s.h_row_off.assign(1, 0);
+    int64_t* d_row_off = s.buf<int64_t>(T_F_ROW_OFF, 1);
+    out->row_off = s.h_row_off.data();
+    if (n == 0) {
+      HIPCHK(hipMemsetAsync(d_row_off, 0, 8, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      out->d_row_off = d_row_off;
+      return OTR_OK;
+    }
+    HIPCHK(hipEventRecord(s.ev[0], stream));
+    CulledRows c;
+    if ((rc = cull_device(s.rows, n, s.cfg.privacy, OTR_TILE_RULES_STREAM, &c, err))) return rc;
+    // the files of the sorted rows, and which of them kept rows
+    const unsigned g = tst_grid(n, 256);
+    int64_t* head = s.buf<int64_t>(T_F_HEAD, n);
+    int64_t* head_incl = s.buf<int64_t>(T_F_INCL, n);
+    k_store_file_heads<<<g, 256, 0, stream>>>(c.sorted, n, head);
+    if ((rc = s.scan64(head, head_incl, n, err))) return rc;
+    int64_t nf = 0;
+    HIPCHK(hipMemcpyAsync(&nf, head_incl + (n - 1), 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (nf < 1 || nf > n) {
+      if (err) *err = "tile store file split failed";
+      return OTR_DEVICE_ERROR;
+    }
+    int64_t* start = s.buf<int64_t>(T_F_START, nf);
+    int64_t* listed = s.buf<int64_t>(T_F_LISTED, nf);
+    int64_t* listed_incl = s.buf<int64_t>(T_F_LINCL, nf);
+    k_store_file_starts<<<g, 256, 0, stream>>>(head, head_incl, n, start);
+    const unsigned gf = tst_grid(nf, 256);
+    k_store_file_listed<<<gf, 256, 0, stream>>>(start, nf, n, c.kept_incl, listed);
+    if ((rc = s.scan64(listed, listed_incl, nf, err))) return rc;
+    int64_t nl = 0;
+    HIPCHK(hipMemcpyAsync(&nl, listed_incl + (nf - 1), 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (nl < 0 || nl > nf || nl > c.n_kept || (nl == 0) != (c.n_kept == 0)) {
+      if (err) *err = "tile store file table failed";
+      return OTR_DEVICE_ERROR;
+    }
+    unsigned long long* d_file = s.buf<unsigned long long>(T_F_FILE, nl);
+    d_row_off = s.buf<int64_t>(T_F_ROW_OFF, (size_t)nl + 1);
+    int64_t* d_unclean = s.buf<int64_t>(T_F_UNCLEAN, nl);
+    k_store_file_table<<<gf, 256, 0, stream>>>(c.sorted, start, nf, n, c.kept_incl, listed, listed_incl, d_file,
+                                               d_row_off, d_unclean);
+    HIPCHK(hipGetLastError());
+    s.h_rows.resize((size_t)c.n_kept);
+    s.h_file.resize((size_t)nl);
+    s.h_unclean.resize((size_t)nl);
+    s.h_row_off.resize((size_t)nl + 1);
+    if (c.n_kept > 0)
+      HIPCHK(hipMemcpyAsync(s.h_rows.data(), c.kept, sizeof(otr_tile_row) * (size_t)c.n_kept, hipMemcpyDeviceToHost,
+                            stream));
+    if (nl > 0) {
+      HIPCHK(hipMemcpyAsync(s.h_file.data(), d_file, 8 * (size_t)nl, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipMemcpyAsync(s.h_unclean.data(), d_unclean, 8 * (size_t)nl, hipMemcpyDeviceToHost, stream));
+    }
+    HIPCHK(hipMemcpyAsync(s.h_row_off.data(), d_row_off, 8 * ((size_t)nl + 1), hipMemcpyDeviceToHost, stream));
+    if ((rc = s.finish(&out->device_ms, err))) return rc;
+    s.n_rows = 0;  // the sorted and the kept rows are copies: the buffer is free again
+    out->n_rows_in = n;
+    out->n_rows = c.n_kept;
+    out->n_files = (int32_t)nl;
+    out->n_files_empty = (int32_t)(nf - nl);
+    out->rows = s.h_rows.empty() ? nullptr : s.h_rows.data();
+    out->file = s.h_file.empty() ? nullptr : (const uint64_t*)s.h_file.data();
+    out->row_off = s.h_row_off.data();
+    out->n_unclean = s.h_unclean.empty() ? nullptr : s.h_unclean.data();
+    out->d_rows = c.kept;
+    out->d_file = (const uint64_t*)d_file;
+    out->d_row_off = d_row_off;
+    out->d_n_unclean = d_unclean;
+    return OTR_OK;
+  });
+}
+
+}  // namespace otr

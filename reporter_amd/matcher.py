@@ -368,6 +368,70 @@ class Matcher:
         self._check(self._L.otr_sessions_snapshot(self._h, ctypes.byref(r)), 'otr_sessions_snapshot')
         return _lib.snapshot_to_numpy(r)
 
+    # --- tile store (include/otr.h otr_tile_store_*) -----------------
+    def tile_store_open(self, max_rows, quantisation=3600, privacy=1):
+        """Open this matcher's tile store: the streaming path's anonymiser stage in HBM."""
+        c = _lib.TileStoreConfig()
+        c.max_rows, c.quantisation, c.privacy = int(max_rows), int(quantisation), int(privacy)
+        self._check(self._L.otr_tile_store_open(self._h, ctypes.byref(c)), 'otr_tile_store_open')
+        self._tile_quantisation = int(quantisation)
+
+    def tile_store_close(self):
+        self._check(self._L.otr_tile_store_close(self._h), 'otr_tile_store_close')
+
+    def tile_store_add_session(self):
+        """otr_tile_store_add_session: the reports of the last sessions_push / sessions_punctuate
+        into the store, in forward order.  Returns the add's counts (dict); an add past
+        max_rows raises ValueError and leaves the store as it was."""
+        r = _lib.TileAddResult()
+        self._check(self._L.otr_tile_store_add_session(self._h, ctypes.byref(r)), 'otr_tile_store_add_session')
+        return _lib.tile_add_to_dict(r)
+
+    def tile_store_add_reports(self, reports, device=False):
+        """otr_tile_store_add_reports.  reports: dict of rep_off (n_windows + 1), id, next_id, t0,
+        t1, length, queue_length: numpy arrays (a sessions_push result dict as it is), or
+        device pointers plus 'n_windows' with device=True."""
+        r = _lib.TileAddResult()
+        names = ['rep_off'] + [k for k, _, _ in _lib.SESSION_REPORT_FIELDS]
+        if device:
+            nw, mem = int(reports['n_windows']), _lib.OTR_MEM_DEVICE
+            ptrs = [reports[k] or None for k in names]
+        else:
+            types = [np.int64] + [dt for _, _, dt in _lib.SESSION_REPORT_FIELDS]
+            keep = [np.ascontiguousarray(reports[k], dt) for k, dt in zip(names, types)]
+            if len({len(a) for a in keep[1:]}) != 1 or len(keep[0]) < 1:
+                raise ValueError('tile store reports: arrays of different lengths')
+            self._keep = keep
+            nw, mem = len(keep[0]) - 1, _lib.OTR_MEM_HOST
+            ptrs = [a.ctypes.data for a in keep]
+        self._check(self._L.otr_tile_store_add_reports(self._h, nw, *ptrs, mem, ctypes.byref(r)),
+                    'otr_tile_store_add_reports')
+        return _lib.tile_add_to_dict(r)
+
+    def tile_store_add_rows(self, rows=None, device_ptr=None, n=None):
+        """otr_tile_store_add_rows: finished rows (numpy _lib.TILE_ROW, or device_ptr and n)."""
+        r = _lib.TileAddResult()
+        if device_ptr is not None:
+            rc = self._L.otr_tile_store_add_rows(self._h, device_ptr or None, int(n), _lib.OTR_MEM_DEVICE,
+                                                 ctypes.byref(r))
+        else:
+            rows = np.ascontiguousarray(rows, dtype=_lib.TILE_ROW)
+            self._keep = [rows]
+            rc = self._L.otr_tile_store_add_rows(self._h, rows.ctypes.data if len(rows) else None, len(rows),
+                                                 _lib.OTR_MEM_HOST, ctypes.byref(r))
+        self._check(rc, 'otr_tile_store_add_rows')
+        return _lib.tile_add_to_dict(r)
+
+    def tile_store_flush(self):
+        """otr_tile_store_flush: everything added since the last flush as cleaned files: numpy
+        copies of rows, file, row_off, n_unclean, the counts, the store's quantisation and the
+        device pointers d_* (matcher-owned until its next tile-store or cull call)."""
+        r = _lib.TileFlushResult()
+        self._check(self._L.otr_tile_store_flush(self._h, ctypes.byref(r)), 'otr_tile_store_flush')
+        out = _lib.tile_flush_to_numpy(r)
+        out['quantisation'] = self._tile_quantisation
+        return out
+
     def match_batch_numpy(self, traces, **kw):
         r = self.match_batch(traces, copy_out=True, **kw)
         return _lib.result_to_numpy(r)

@@ -325,6 +325,29 @@ def stream_tiles_device(matcher, traces, privacy, mode='auto', report_levels=(0,
     return rows_to_tiles(kept, quantisation, mode, source, rules=_lib.OTR_TILE_RULES_STREAM)
 
 
+# Segment.columnLayout() (Segment.java:55-57): the first line of every streaming tile file
+STREAM_COLUMN_LAYOUT = ('segment_id,next_segment_id,duration,count,length,queue_length,minimum_timestamp,'
+                        'maximum_timestamp,source,vehicle_type')
+
+
+def stream_tile_payloads(flush, mode='auto', source='reporter'):
+    """What AnonymisingProcessor.store writes (AnonymisingProcessor.java:177-183) for every file
+    of a Matcher.tile_store_flush(): {"{start}_{start+q-1}/{level}/{tile}": text}, text being
+    Segment.columnLayout() followed by the file's Segment lines (otr_tiles_format with
+    OTR_TILE_RULES_STREAM).  The bucket length is the flush's 'quantisation' (the store's)."""
+    from . import _lib
+    quantisation = int(flush['quantisation'])
+    tiles = rows_to_tiles(flush['rows'], quantisation, mode, source, rules=_lib.OTR_TILE_RULES_STREAM)
+    out = {}
+    for f in range(int(flush['n_files'])):
+        key = file_key(flush['file'][f], quantisation)
+        lines = tiles[key]
+        if len(lines) != int(flush['row_off'][f + 1]) - int(flush['row_off'][f]):
+            raise RuntimeError('stream_tile_payloads: the file table does not match the rows of ' + key)
+        out[key] = STREAM_COLUMN_LAYOUT + ''.join(lines)
+    return out
+
+
 def _exchange_by_file_owner(buf, itemsize, world, group=None):
     """All-to-all of fixed-size records whose first 8 bytes are their (hour, tile) file:
     each record goes to file_owner(file); returns the records this rank received (uint8

@@ -10,8 +10,13 @@ windows and reports back on the host), rounds per chunk, windows per round, and 
 the wall time into the matcher's batches (match_ms) and everything else (session kernels, copies,
 host).
 One warm-up replay, then `--repeats` timed ones: median, minimum and maximum are reported.
+`--tile-store` replays every chunk size a second time with a tile store open (quantisation
+3600, privacy 2): otr_tile_store_add_session after every push, inside the timed loop, and one
+flush after the final punctuate; the summed add device_ms, the flush device_ms and the rows held
+at the flush are reported beside the plain run's probes/s.
 
     python -m reporter_amd.tools.sessions_rate --traces 2000 --out profiles/sessions_c2dep.json
+    python -m reporter_amd.tools.sessions_rate --traces 2000 --tile-store --out profiles/tile_store_c2dep.json
 """
 import argparse
 import json
@@ -36,9 +41,13 @@ def stream(tr):
             'timestamp': tm[order] * 1000}
 
 
-def replay(m, pts, cuts, max_points, batch_ms):
-    """One replay: a fresh store, every chunk pushed, a final punctuate."""
+def replay(m, pts, cuts, max_points, batch_ms, tile_rows=0):
+    """One replay: a fresh store, every chunk pushed, a final punctuate.  tile_rows > 0: a tile
+    store of that many rows takes every result (add_session) and is flushed at the end."""
     m.sessions_open(int(pts['key'].max()) + 1, max_points)
+    if tile_rows:
+        m.tile_store_open(tile_rows, 3600, 2)
+    add_ms = []
     chunks = [{k: v[a:b] for k, v in pts.items()} for a, b in zip(cuts[:-1], cuts[1:])]
     rounds = windows = reports = 0
     dev_ms = match_ms = 0.0
@@ -50,10 +59,22 @@ def replay(m, pts, cuts, max_points, batch_ms):
         reports += r['n_reports']
         dev_ms += r['device_ms']
         match_ms += r['match_ms']
+        if tile_rows:
+            add_ms.append(m.tile_store_add_session()['device_ms'])
     wall = time.perf_counter() - t0
     ev = m.sessions_punctuate(int(pts['timestamp'][-1]) + 10 ** 9)
+    tile = None
+    if tile_rows:
+        add_ms.append(m.tile_store_add_session()['device_ms'])
+        t1 = time.perf_counter()
+        fl = m.tile_store_flush()
+        tile = {'adds': len(add_ms), 'add_ms': float(np.sum(add_ms)), 'add_ms_max': float(np.max(add_ms)),
+                'flush_ms': fl['device_ms'], 'flush_wall_ms': 1e3 * (time.perf_counter() - t1),
+                'rows_held': fl['n_rows_in'], 'rows_kept': fl['n_rows'], 'files': fl['n_files'],
+                'files_empty': fl['n_files_empty']}
+        m.tile_store_close()
     m.sessions_close()
-    return {'wall_s': wall, 'rounds': rounds, 'windows': windows, 'reports': reports, 'stream_ms': dev_ms, 'match_ms': match_ms,
+    return {'tile': tile, 'wall_s': wall, 'rounds': rounds, 'windows': windows, 'reports': reports, 'stream_ms': dev_ms, 'match_ms': match_ms,
             'evicted': ev['n_evicted'], 'eviction_windows': ev['n_windows'], 'chunks': len(chunks)}
 
 
@@ -64,6 +85,9 @@ def main():
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--max-points', type=int, default=128)
     ap.add_argument('--graphs', default=os.path.join(ROOT, 'build', 'graphs'))
+    ap.add_argument('--tile-store', action='store_true',
+                    help='also replay with a tile store: add_session after every push, one flush at the end')
+    ap.add_argument('--tile-rows', type=int, default=1 << 22, help='max_rows of that store')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if ROOT not in sys.path:
@@ -107,6 +131,24 @@ def main():
             'stream_ms': round(float(np.median([x['stream_ms'] for x in runs])), 1),
             'match_ms': round(float(np.median([x['match_ms'] for x in runs])), 1),
             'rounds_times_smallest_batch_ms': round(r['rounds'] * batch_ms, 1)}
+        if args.tile_store:
+            replay(m, pts, cuts, args.max_points, batch_ms, args.tile_rows)
+            truns = [replay(m, pts, cuts, args.max_points, batch_ms, args.tile_rows) for _ in range(args.repeats)]
+            trate = sorted(n / x['wall_s'] for x in truns)
+            t = truns[0]['tile']
+
+            def med(k, src=None):
+                v = sorted(x['tile'][k] if src is None else x[src] for x in truns)
+                return [round(float(np.median(v)), 3), round(float(v[0]), 3), round(float(v[-1]), 3)]
+
+            res['chunks']['%d_s' % cs]['tile_store'] = {
+                'probes_per_s': round(float(np.median(trate)), 1),
+                'probes_per_s_min_max': [round(trate[0], 1), round(trate[-1], 1)],
+                'adds': t['adds'], 'add_ms_sum_median_min_max': med('add_ms'),
+                'add_ms_largest_median_min_max': med('add_ms_max'), 'flush_ms_median_min_max': med('flush_ms'),
+                'flush_wall_ms_median_min_max': med('flush_wall_ms'),
+                'match_ms_median_min_max': med(None, 'match_ms'), 'rows_held': t['rows_held'],
+                'rows_kept': t['rows_kept'], 'files': t['files'], 'files_empty': t['files_empty']}
     line = json.dumps(res, indent=1)
     print(line)
     if args.out:
