@@ -592,6 +592,87 @@ int otr_sessions_windows(otr_matcher* m, otr_session_result* out);
 
 int otr_sessions_snapshot(otr_matcher* m, otr_session_snapshot* out);
 
+/* ---- stream formatter: raw messages → keyed points in HBM -------
+ * What KeyedFormattingProcessor.java:32-43 does with Formatter.formatSV / formatJSON: every
+ * message ends as a point (kept), is dropped (the reference certainly throws and the
+ * processor logs and goes on), or is unsupported (the reference would, or might, produce a
+ * point that cannot be reproduced here without a JVM: never approximated, counted apart).
+ * A message's status is 0 or its reason; reasons below OTR_FORMAT_UNSUPPORTED are drops.
+ * Over a message any drop beats any unsupported reading; within a class the first in the
+ * reference's evaluation order (lat, lon, time, accuracy, uuid) is reported.  The key of a
+ * point is K11's 64-bit hash of the uuid bytes. */
+#define OTR_FORMAT_SV   0   /* Formatter.formatSV   (Formatter.java:97-109)  */
+#define OTR_FORMAT_JSON 1   /* Formatter.formatJSON (Formatter.java:111-124) */
+#define OTR_FORMAT_D_FIELDS 1     /* SV: a needed field index beyond what String.split leaves */
+#define OTR_FORMAT_D_FLOAT 2      /* coordinate text not a finite decimal number */
+#define OTR_FORMAT_D_INT 3        /* time text not an integer (Long.parseLong, the pattern's pieces) */
+#define OTR_FORMAT_D_TIME 4       /* date fields out of range; JSON: a number where the pattern needs text */
+#define OTR_FORMAT_D_ACCURACY 5   /* SV: accuracy not a decimal number */
+#define OTR_FORMAT_D_JSON 6       /* not one RFC 8259 value */
+#define OTR_FORMAT_D_ROOT 7       /* the JSON value is not an object */
+#define OTR_FORMAT_D_MISSING 8    /* a needed key is missing */
+#define OTR_FORMAT_UNSUPPORTED 32
+#define OTR_FORMAT_U_PRECISION 32 /* > 19 significant digits whose rounding needs big-number arithmetic */
+#define OTR_FORMAT_U_ACCURACY 33  /* accuracy not finite or beyond ±2^24 */
+#define OTR_FORMAT_U_DEPTH 34     /* JSON nested deeper than 64 */
+#define OTR_FORMAT_U_TRAILING 35  /* non-whitespace after the JSON value */
+#define OTR_FORMAT_U_ESCAPE 36    /* a backslash in a top-level key or in a needed string */
+#define OTR_FORMAT_U_NUMBER 37    /* a number token the reference prints or reads in a way not pinned here */
+#define OTR_FORMAT_U_KIND 38      /* a needed value of a kind whose reading is not pinned here */
+#define OTR_FORMAT_U_NO_ID 39     /* the uuid hashes to OTR_NO_ID */
+
+typedef struct otr_message_format {
+  int32_t type;            /* OTR_FORMAT_* */
+  int32_t separator;       /* SV: one byte */
+  int32_t uuid_index, time_index, lat_index, lon_index, accuracy_index;   /* SV */
+  int32_t time_format;     /* OTR_TIME_EPOCH | OTR_TIME_YMDHMS ("yyyy-MM-dd HH:mm:ss", UTC) */
+  const char *uuid_key, *lat_key, *lon_key, *time_key, *accuracy_key;     /* JSON: 1..64 bytes, no '"', no '\\' */
+} otr_message_format;
+
+typedef struct otr_messages {
+  const char* text;  int64_t len;  int32_t memory;  int32_t reserved;
+  const int64_t* msg_off;   /* NULL: messages are the '\n'-separated lines of text (K11's line rule:
+                               a final fragment counts); else n_messages+1 ascending byte offsets,
+                               same memory as text */
+  int64_t n_messages;       /* with msg_off */
+  const int64_t* timestamp; /* per message, same memory as text; NULL: timestamp_all for every message */
+  int64_t timestamp_all;
+} otr_messages;
+
+/* points: the kept messages in arrival order, memory == OTR_MEM_DEVICE; d_message: per point
+ * the arrival index of its message (a session window's trigger maps back through it);
+ * d_uuid_off / d_uuid_len: per point, its uuid in the text; d_status: per message.  All of it
+ * is owned by the matcher and valid until its next formatter call (it survives an
+ * otr_sessions_push that consumes it). */
+typedef struct otr_format_result {
+  int64_t n_messages;
+  int64_t n_points;
+  int64_t n_dropped;
+  int64_t n_unsupported;
+  int64_t first_bad;          /* first message dropped or unsupported, -1 if none */
+  int32_t first_bad_reason;   /* OTR_FORMAT_D_* / OTR_FORMAT_U_* */
+  float parse_ms;             /* device time of k_format_parse (HIP events on the matcher's stream) */
+  float total_ms;             /* from the first kernel to the last (host syncs between included) */
+  int32_t reserved;
+  otr_session_points points;
+  const int64_t* d_message;
+  const int64_t* d_uuid_off;
+  const int32_t* d_uuid_len;
+  const int32_t* d_status;
+} otr_format_result;
+
+/* Text → keyed points in HBM.  OTR_BAD_REQUEST, nothing changed: a bad format struct, a key
+ * out of range, offsets that do not ascend, text or message count beyond otr_ingest's
+ * limits, or two different uuids of the chunk sharing a hash (first_bad set, reason
+ * OTR_INGEST_E_COLLISION).  Everything else is decided per message. */
+int otr_format_messages(otr_matcher* m, const otr_message_format* fmt, const otr_messages* msgs,
+                        otr_format_result* out);
+
+/* The same, then otr_sessions_push of those device points: no point crosses to the host in
+ * between.  Refusals are those of otr_sessions_push plus the formatter's own. */
+int otr_sessions_push_text(otr_matcher* m, const otr_message_format* fmt, const otr_messages* msgs,
+                           otr_format_result* fmt_out, otr_session_result* session_out);
+
 /* ---- tile store: the streaming reporter's anonymiser stage ------
  * What sits between BatchingProcessor.forward (BatchingProcessor.java:108-141) and the tile
  * files of AnonymisingProcessor.process / punctuate (AnonymisingProcessor.java:119-175,

@@ -31,6 +31,12 @@ OTR_TIME_EPOCH = 0
 OTR_TIME_YMDHMS = 1
 INGEST_REASONS = {1: 'fields', 2: 'float', 3: 'int', 4: 'time', 5: 'uuid', 6: 'precision', 7: 'collision',
                   8: 'accuracy'}
+OTR_FORMAT_SV = 0
+OTR_FORMAT_JSON = 1
+OTR_FORMAT_UNSUPPORTED = 32   # reasons below are drops (the reference throws), from here on unsupported
+FORMAT_REASONS = {1: 'fields', 2: 'float', 3: 'int', 4: 'time', 5: 'accuracy', 6: 'json', 7: 'root', 8: 'missing',
+                  32: 'precision', 33: 'accuracy range', 34: 'depth', 35: 'trailing', 36: 'escape', 37: 'number',
+                  38: 'kind', 39: 'no id'}
 OTR_NO_ID = 0xFFFFFFFFFFFFFFFF
 HIST_BINS = 8
 KMAX = 64
@@ -49,7 +55,7 @@ EXPORTS = ['otr_configure', 'otr_configure_json', 'otr_matcher_new', 'otr_matche
            'otr_sessions_push', 'otr_sessions_punctuate', 'otr_sessions_advance', 'otr_sessions_commit',
            'otr_sessions_windows', 'otr_sessions_snapshot', 'otr_tile_store_open', 'otr_tile_store_close',
            'otr_tile_store_add_session', 'otr_tile_store_add_reports', 'otr_tile_store_add_rows',
-           'otr_tile_store_flush']
+           'otr_tile_store_flush', 'otr_format_messages', 'otr_sessions_push_text']
 
 
 class ServiceSplit(ctypes.Structure):
@@ -185,6 +191,33 @@ SESSION_REPORT_FIELDS = [('id', ctypes.c_uint64, np.uint64), ('next_id', ctypes.
 SESSION_COUNTS = ['n_windows', 'n_reports', 'n_rounds', 'n_live', 'n_forced', 'n_dropped', 'n_evicted', 'n_rebuilds']
 
 
+class MessageFormat(ctypes.Structure):
+    """otr_message_format (include/otr.h): the stream formatter's SV or JSON message layout."""
+    _fields_ = [('type', ctypes.c_int32), ('separator', ctypes.c_int32), ('uuid_index', ctypes.c_int32),
+                ('time_index', ctypes.c_int32), ('lat_index', ctypes.c_int32), ('lon_index', ctypes.c_int32),
+                ('accuracy_index', ctypes.c_int32), ('time_format', ctypes.c_int32), ('uuid_key', ctypes.c_char_p),
+                ('lat_key', ctypes.c_char_p), ('lon_key', ctypes.c_char_p), ('time_key', ctypes.c_char_p),
+                ('accuracy_key', ctypes.c_char_p)]
+
+
+class Messages(ctypes.Structure):
+    """otr_messages (include/otr.h): a chunk of raw messages, host or device memory."""
+    _fields_ = [('text', ctypes.c_void_p), ('len', ctypes.c_int64), ('memory', ctypes.c_int32),
+                ('reserved', ctypes.c_int32), ('msg_off', ctypes.c_void_p), ('n_messages', ctypes.c_int64),
+                ('timestamp', ctypes.c_void_p), ('timestamp_all', ctypes.c_int64)]
+
+
+FORMAT_COUNTS = ['n_messages', 'n_points', 'n_dropped', 'n_unsupported', 'first_bad']
+
+
+class FormatResult(ctypes.Structure):
+    """otr_format_result (include/otr.h): the kept messages as keyed points in HBM."""
+    _fields_ = ([(k, ctypes.c_int64) for k in FORMAT_COUNTS] +
+                [('first_bad_reason', ctypes.c_int32), ('parse_ms', ctypes.c_float), ('total_ms', ctypes.c_float),
+                 ('reserved', ctypes.c_int32), ('points', SessionPoints), ('d_message', ctypes.c_void_p),
+                 ('d_uuid_off', ctypes.c_void_p), ('d_uuid_len', ctypes.c_void_p), ('d_status', ctypes.c_void_p)])
+
+
 class SessionResult(ctypes.Structure):
     """otr_session_result (include/otr.h): the windows of a session call and their reports."""
     _fields_ = ([('n_windows', ctypes.c_int64), ('n_reports', ctypes.c_int64)] +
@@ -257,6 +290,44 @@ def tile_flush_to_numpy(r):
     out['n_unclean'] = _copy(r.n_unclean, nf, np.int64)
     for k in TILE_FLUSH_FIELDS:
         out['d_' + k] = int(getattr(r, 'd_' + k) or 0)
+    return out
+
+
+def device_to_numpy(ptr, n, dt):
+    """n records of dtype dt at the device address ptr, copied to the host (through the HIP
+    runtime libotr links; the producing call has drained its stream)."""
+    out = np.zeros(max(int(n), 0), dt)
+    if len(out) and ptr:
+        L = lib()
+        L.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        rc = L.hipMemcpy(out.ctypes.data, ptr, out.nbytes, 2)  # hipMemcpyDeviceToHost
+        if rc != 0:
+            raise RuntimeError('hipMemcpy failed (%d)' % rc)
+    return out
+
+
+# the per-point arrays of otr_format_result beside its points, and the per-message one
+FORMAT_POINT_FIELDS = [('d_message', 'message', np.int64), ('d_uuid_off', 'uuid_off', np.int64),
+                       ('d_uuid_len', 'uuid_len', np.int32)]
+
+
+def format_result_to_numpy(r, arrays=True):
+    """An otr_format_result as host copies: counts, times, the points (key, lat, lon, accuracy,
+    time, timestamp), message, uuid_off, uuid_len per point and status per message; 'device'
+    holds the result struct, its arrays in HBM (valid until the matcher's next formatter call).
+    arrays=False: counts, times and 'device' only, nothing copied."""
+    out = {k: int(getattr(r, k)) for k in FORMAT_COUNTS}
+    out['first_bad_reason'] = int(r.first_bad_reason)
+    out['parse_ms'], out['total_ms'] = float(r.parse_ms), float(r.total_ms)
+    out['device'] = r
+    if not arrays:
+        return out
+    n = int(r.n_points)
+    for k, dt in SESSION_POINT_FIELDS:
+        out[k] = device_to_numpy(getattr(r.points, k), n, dt)
+    for src, k, dt in FORMAT_POINT_FIELDS:
+        out[k] = device_to_numpy(getattr(r, src), n, dt)
+    out['status'] = device_to_numpy(r.d_status, int(r.n_messages), np.int32)
     return out
 
 
@@ -342,6 +413,10 @@ def lib():
         L.otr_tile_store_add_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                               P(TileAddResult)]
         L.otr_tile_store_flush.argtypes = [ctypes.c_void_p, P(TileFlushResult)]
+    if hasattr(L, 'otr_format_messages'):
+        L.otr_format_messages.argtypes = [ctypes.c_void_p, P(MessageFormat), P(Messages), P(FormatResult)]
+        L.otr_sessions_push_text.argtypes = [ctypes.c_void_p, P(MessageFormat), P(Messages), P(FormatResult),
+                                             P(SessionResult)]
     L.otr_graph_info.argtypes = [P(ctypes.c_int64), P(ctypes.c_int64), P(ctypes.c_int64)]
     L.otr_matcher_stream.argtypes = [ctypes.c_void_p]
     L.otr_matcher_stream.restype = ctypes.c_void_p

@@ -145,6 +145,19 @@ def build_parsecheck(force=False):
     return lib
 
 
+def build_formatcheck(force=False):
+    """tools/libformatcheck.so: host build of the stream formatter's per-message functions
+    (CPU tests only)."""
+    src = os.path.join(PKG, 'tools', 'formatcheck.cpp')
+    lib = os.path.join(PKG, 'tools', 'libformatcheck.so')
+    deps = [src] + [os.path.join(CSRC, f) for f in ('otr_formatter.h', 'otr_ingest.h', 'otr_pow5.h')]
+    deps.append(os.path.join(ROOT, 'include', 'otr.h'))
+    if force or not _newer(lib, deps):
+        _run([HIPCC, '-x', 'hip', '--cuda-host-only', '-O2', '-std=c++17', '-fPIC', '-shared',
+              '-I' + os.path.join(ROOT, 'include'), '-o', lib, src])
+    return lib
+
+
 def build_mincheck(force=False):
     """tools/libmincheck.so: host build of the node tables' IN-gap codes (CPU tests only)."""
     src = os.path.join(PKG, 'tools', 'mincheck.cpp')
@@ -161,6 +174,7 @@ def build_all(force=False):
     from concurrent.futures import ThreadPoolExecutor
     build_gen(force)
     build_parsecheck(force)
+    build_formatcheck(force)
     build_mincheck(force)
     build_oracle(force)
     build_calib(force)

@@ -494,6 +494,27 @@ int otr_sessions_snapshot(otr_matcher* m, otr_session_snapshot* out) {
   OTR_SESSIONS_CALL(!m || !out, sessions_snapshot(out, &err));
 }
 
+// the stream formatter (K16): KeyedFormattingProcessor.java:32-43 over Formatter.java:97-124
+int otr_format_messages(otr_matcher* m, const otr_message_format* fmt, const otr_messages* msgs,
+                        otr_format_result* out) {
+  OTR_SESSIONS_CALL(!m || !fmt || !msgs || !out, format_messages(fmt, msgs, out, &err));
+}
+
+int otr_sessions_push_text(otr_matcher* m, const otr_message_format* fmt, const otr_messages* msgs,
+                           otr_format_result* fmt_out, otr_session_result* session_out) {
+  if (!m || !fmt || !msgs || !fmt_out || !session_out) {
+    g_last_error = "null argument";
+    return OTR_BAD_REQUEST;
+  }
+  std::string err;
+  int rc = OTR_OK;
+  if (m->m.ses) rc = m->m.format_messages(fmt, msgs, fmt_out, &err);  // (no store: the push's own refusal)
+  else memset(fmt_out, 0, sizeof(*fmt_out));
+  if (rc == OTR_OK) rc = m->m.sessions_push(&fmt_out->points, session_out, &err);
+  if (rc != OTR_OK) g_last_error = err;
+  return rc;
+}
+
 // the tile store (K15): BatchingProcessor.forward → AnonymisingProcessor.process / punctuate
 // (BatchingProcessor.java:108-141, AnonymisingProcessor.java:119-175, 222-266), in HBM
 int otr_tile_store_open(otr_matcher* m, const otr_tile_store_config* cfg) {

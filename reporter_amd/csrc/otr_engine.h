@@ -179,6 +179,11 @@ struct Matcher {
   int copy_out(void* dst, const void* src, size_t bytes, int dst_memory, std::string* err);
   int ingest(const char* text, int64_t len, int memory, const otr_ingest_format* fmt, otr_ingest_result* out,
              std::string* err);
+  // the stream formatter (K16, otr_formatter.h): raw messages → keyed points in HBM
+  int format_messages(const otr_message_format* fmt, const otr_messages* msgs, otr_format_result* out,
+                      std::string* err);
+  int format_messages_impl(const otr_message_format* fmt, const otr_messages* msgs, otr_format_result* out,
+                           std::string* err);
   // the session store (K14, otr_sessions.hip)
   int sessions_open(const otr_session_config* cfg, std::string* err);
   int sessions_close(std::string* err);

@@ -15,6 +15,7 @@
 #include "otr_edge.h"
 #include "otr_edge1.h"
 #include "otr_ingest.h"
+#include "otr_formatter.h"
 #include "otr_launch.h"
 #include "otr_points.h"
 #include "otr_traversals.h"
@@ -423,6 +424,8 @@ enum Slot {
   S_PT_KIND, S_PT_EDGE, S_PT_FRAC, S_PT_LAT, S_PT_LON, S_PT_DIST, S_PT_STATE, S_PT_POS, S_PT_STATUS,
   S_TR_CNT, S_TR_OFF, S_TR_EDGE, S_TR_WAY, S_TR_SEG, S_TR_FIRST, S_TR_F0, S_TR_F1, S_TR_S0, S_TR_S1, S_TR_T0, S_TR_T1,
   S_TR_KEEP, S_TR_KEEP_OFF, S_TR_ENTRIES, S_TR_TMP,
+  S_FM_KEYS, S_FM_OFF, S_FM_TSIN, S_FM_WRONG, S_FM_STATUS, S_FM_P_LAT, S_FM_P_LON, S_FM_P_ACC, S_FM_FLAG,
+  S_FM_KEY, S_FM_LAT, S_FM_LON, S_FM_ACC, S_FM_TIME, S_FM_TS, S_FM_MSG, S_FM_UOFF, S_FM_ULEN,
   S_NUM
 };
 
@@ -3031,6 +3034,21 @@ int Matcher::hist_reduce_impl(const void* in, int64_t n, int memory, int rows_in
 }
 
 // ---- K11 ingest (include/otr.h otr_ingest) ----------------------------------------------
+// The uuid grouping stage, shared by K11 and the stream formatter (K16): the M kept lines
+// (kidx, ascending) sorted by (hash, line), the stable sort keeping line order within a
+// hash, then group heads with a byte compare of every equal-hash neighbour: a collision
+// lands in *bad as (line << 8 | OTR_INGEST_E_COLLISION).
+static int uuid_group_heads(hipStream_t stream, const uint64_t* hash, const int32_t* kidx, int64_t M,
+                            const int64_t* uoff, const int32_t* ulen, const uint8_t* d_text, void* tmp, size_t tb_sort,
+                            uint64_t* key_a, uint64_t* key_b, int32_t* val_b, int64_t* head, unsigned long long* bad,
+                            std::string* err) {
+  k_gather_by<uint64_t><<<grid_for(M, 256), 256, 0, stream>>>(hash, kidx, M, key_a);
+  size_t tb = tb_sort;
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key_a, key_b, kidx, val_b, (int)M, 0, 64, stream));
+  k_group_heads<<<grid_for(M, 256), 256, 0, stream>>>(key_b, val_b, M, uoff, ulen, d_text, head, bad);
+  return OTR_OK;
+}
+
 int Matcher::ingest(const char* text, int64_t len, int memory, const otr_ingest_format* fmt, otr_ingest_result* out,
                     std::string* err) {
   try {
@@ -3178,10 +3196,9 @@ int Matcher::ingest_impl(const char* text, int64_t len, int memory, const otr_in
   if (!key_a || !key_b || !val_a || !val_b || !head || !gid || !gfirst || !gkey)
     return fail("device allocation failed (ingest)");
   // 1. group by uuid: sort (hash, line) — the stable sort keeps line order within a hash
-  k_gather_by<uint64_t><<<grid_for(M, 256), 256, 0, stream>>>(L.hash, kidx, M, key_a);
-  tb = tb_sort;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key_a, key_b, kidx, val_b, nM, 0, 64, stream));
-  k_group_heads<<<grid_for(M, 256), 256, 0, stream>>>(key_b, val_b, M, L.uoff, L.ulen, d_text, head, bad);
+  int rc_groups = uuid_group_heads(stream, L.hash, kidx, M, L.uoff, L.ulen, d_text, tmp, tb_sort, key_a, key_b, val_b,
+                                   head, bad, err);
+  if (rc_groups != OTR_OK) return rc_groups;
   tb = tb_scan;
   HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, head, gid, nM, stream));
   k_group_first<<<grid_for(M, 256), 256, 0, stream>>>(head, gid, val_b, M, gfirst);
@@ -3265,6 +3282,242 @@ int Matcher::ingest_impl(const char* text, int64_t len, int memory, const otr_in
   b.mode = o.mode;
   out->d_trace_uuid_off = o.uoff;
   out->d_trace_uuid_len = o.ulen;
+  return OTR_OK;
+}
+
+// ---- K16 stream formatter (include/otr.h otr_format_messages) ---------------------------
+int Matcher::format_messages(const otr_message_format* fmt, const otr_messages* msgs, otr_format_result* out,
+                             std::string* err) {
+  try {
+    return format_messages_impl(fmt, msgs, out, err);
+  } catch (const DeviceOom& o) {
+    return oom_error(stream, o, err);
+  }
+}
+
+int Matcher::format_messages_impl(const otr_message_format* fmt, const otr_messages* msgs, otr_format_result* out,
+                                  std::string* err) {
+  GraphState& gs = graph_state();
+  HIPCHK(hipSetDevice(gs.device));
+  if (!stream) HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+  memset(out, 0, sizeof(*out));
+  out->first_bad = -1;
+  out->points.memory = OTR_MEM_DEVICE;
+  auto refuse = [&](const char* what) {
+    if (err) *err = what;
+    return OTR_BAD_REQUEST;
+  };
+  // the format
+  MsgFmt f{};
+  f.type = fmt->type;
+  f.sep = fmt->separator;
+  f.tfmt = fmt->time_format;
+  f.idx[FM_UUID] = fmt->uuid_index;
+  f.idx[FM_TIME] = fmt->time_index;
+  f.idx[FM_LAT] = fmt->lat_index;
+  f.idx[FM_LON] = fmt->lon_index;
+  f.idx[FM_ACC] = fmt->accuracy_index;
+  if ((f.type != OTR_FORMAT_SV && f.type != OTR_FORMAT_JSON) ||
+      (f.tfmt != OTR_TIME_EPOCH && f.tfmt != OTR_TIME_YMDHMS))
+    return refuse("bad message format");
+  uint8_t h_keys[5 * 64] = {0};
+  if (f.type == OTR_FORMAT_SV) {
+    if (f.sep < 1 || f.sep > 255) return refuse("bad message format: separator");
+    for (int k = 0; k < 5; ++k)
+      if (f.idx[k] < 0 || f.idx[k] > 4096) return refuse("bad message field index");
+  } else {
+    const char* keys[5];
+    keys[FM_UUID] = fmt->uuid_key;
+    keys[FM_TIME] = fmt->time_key;
+    keys[FM_LAT] = fmt->lat_key;
+    keys[FM_LON] = fmt->lon_key;
+    keys[FM_ACC] = fmt->accuracy_key;
+    for (int k = 0; k < 5; ++k) {
+      if (!keys[k]) return refuse("bad message format: null key");
+      const size_t n = strnlen(keys[k], 65);
+      if (n < 1 || n > 64 || memchr(keys[k], '"', n) || memchr(keys[k], '\\', n))
+        return refuse("bad message key: 1..64 bytes, no quote, no backslash");
+      f.klen[k] = (int)n;
+      memcpy(h_keys + 64 * k, keys[k], n);
+    }
+  }
+  // the messages
+  const int64_t len = msgs->len;
+  const bool given = msgs->msg_off != nullptr;
+  if (len < 0 || (len > 0 && !msgs->text) || (given && msgs->n_messages < 0)) return refuse("bad messages");
+  if (len >= ((int64_t)1 << 40)) return refuse("message text too large");
+  if (given && msgs->n_messages >= INT32_MAX) return refuse("too many messages for one call");
+  const hipMemcpyKind kind = msgs->memory == OTR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  auto fail = [&](const char* what) {
+    if (err) *err = what;
+    return OTR_DEVICE_ERROR;
+  };
+  const int64_t n_chunks = std::max<int64_t>((len + 15) / 16, 1);
+  if (n_chunks >= INT32_MAX) return refuse("message text too large");
+  uint8_t* d_text = need<uint8_t>(S_IN_TEXT, 16 * n_chunks);
+  unsigned long long* bad = need<unsigned long long>(S_IN_BAD, 1);
+  uint8_t* d_keys = need<uint8_t>(S_FM_KEYS, sizeof(h_keys));
+  if (!d_text || !bad || !d_keys) return fail("device allocation failed (formatter)");
+  f.keys = d_keys;
+  HIPCHK(hipMemsetAsync(d_text + 16 * (n_chunks - 1), 0, 16, stream));
+  if (len > 0) HIPCHK(hipMemcpyAsync(d_text, msgs->text, len, kind, stream));
+  HIPCHK(hipMemcpyAsync(d_keys, h_keys, sizeof(h_keys), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemsetAsync(bad, 0xFF, 8, stream));
+  if (!ev_init) {
+    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+    ev_init = true;
+  }
+  HIPCHK(hipEventRecord(ev[20], stream));
+  // message bounds: the given offsets, or K11's newline index
+  int64_t n = 0, n_nl = 0;
+  const int64_t* d_off = nullptr;
+  const int64_t* nl = nullptr;
+  size_t tb_scan = 0;
+  void* tmp = nullptr;
+  if (given) {
+    n = msgs->n_messages;
+    int64_t* off = need<int64_t>(S_FM_OFF, n + 1);
+    int32_t* wrong = need<int32_t>(S_FM_WRONG, 1);
+    if (!off || !wrong) return fail("device allocation failed (formatter)");
+    HIPCHK(hipMemcpyAsync(off, msgs->msg_off, 8 * (n + 1), kind, stream));
+    HIPCHK(hipMemsetAsync(wrong, 0, 4, stream));
+    k_format_check_off<<<grid_for(n + 1, 256), 256, 0, stream>>>(off, n, len, wrong);
+    int32_t h_wrong = 0;
+    HIPCHK(hipMemcpyAsync(&h_wrong, wrong, 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (h_wrong) return refuse("message offsets must ascend from >= 0 to <= len");
+    d_off = off;
+  } else if (len > 0) {
+    int64_t* cnt = need<int64_t>(S_IN_CNT, n_chunks);
+    int64_t* cscan = need<int64_t>(S_IN_CSCAN, n_chunks);
+    if (!cnt || !cscan) return fail("device allocation failed (formatter)");
+    HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb_scan, cnt, cscan, (int)n_chunks, stream));
+    tmp = need<char>(S_IN_TMP, tb_scan);
+    if (!tmp) return fail("device allocation failed (formatter)");
+    k_nl_count<<<grid_for(n_chunks, 256), 256, 0, stream>>>(reinterpret_cast<const uint4*>(d_text), n_chunks, cnt);
+    size_t tb = tb_scan;
+    HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, cnt, cscan, (int)n_chunks, stream));
+    uint8_t last = 0;
+    HIPCHK(hipMemcpyAsync(&n_nl, cscan + (n_chunks - 1), 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&last, d_text + (len - 1), 1, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    n = n_nl + (last != '\n' ? 1 : 0);  // a final fragment without '\n' is a message too
+    if (n >= INT32_MAX) return refuse("too many messages for one call");
+    int64_t* nlw = need<int64_t>(S_IN_NL, std::max<int64_t>(n_nl, 1));
+    if (!nlw) return fail("device allocation failed (formatter)");
+    if (n_nl) k_nl_write<<<grid_for(n_chunks, 256), 256, 0, stream>>>(reinterpret_cast<const uint4*>(d_text), n_chunks,
+                                                                      cscan, nlw);
+    nl = nlw;
+  }
+  out->n_messages = n;
+  if (n == 0) return OTR_OK;
+  const int64_t* ts_in = nullptr;
+  if (msgs->timestamp) {
+    if (kind == hipMemcpyHostToDevice) {
+      int64_t* t = need<int64_t>(S_FM_TSIN, n);
+      if (!t) return fail("device allocation failed (formatter)");
+      HIPCHK(hipMemcpyAsync(t, msgs->timestamp, 8 * n, kind, stream));
+      ts_in = t;
+    } else {
+      ts_in = msgs->timestamp;
+    }
+  }
+  FormatMsgs M{};
+  M.text = d_text;
+  M.len = len;
+  M.nl = nl;
+  M.n_nl = n_nl;
+  M.off = d_off;
+  M.n = n;
+  M.status = need<int32_t>(S_FM_STATUS, n);
+  M.hash = need<uint64_t>(S_IN_HASH, n);
+  M.uoff = need<int64_t>(S_IN_UOFF, n);
+  M.ulen = need<int32_t>(S_IN_ULEN, n);
+  M.time = need<int64_t>(S_IN_TIME, n);
+  M.lat = need<float>(S_FM_P_LAT, n);
+  M.lon = need<float>(S_FM_P_LON, n);
+  M.acc = need<int32_t>(S_FM_P_ACC, n);
+  M.flag = need<int64_t>(S_FM_FLAG, n);
+  M.bad = bad;
+  int64_t* scan = need<int64_t>(S_IN_KPOS, n);
+  if (!M.status || !M.hash || !M.uoff || !M.ulen || !M.time || !M.lat || !M.lon || !M.acc || !M.flag || !scan)
+    return fail("device allocation failed (formatter)");
+  const int nI = (int)n;
+  size_t tb_sort = 0;
+  HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb_scan, M.flag, scan, nI, stream));
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                            (const int32_t*)nullptr, (int32_t*)nullptr, nI, 0, 64, stream));
+  tmp = need<char>(S_IN_TMP, std::max(tb_scan, tb_sort));
+  if (!tmp) return fail("device allocation failed (formatter)");
+  // parse → flag → scan → emit
+  HIPCHK(hipEventRecord(ev[21], stream));
+  k_format_parse<<<grid_for(n, 256), 256, 0, stream>>>(M, f);
+  HIPCHK(hipEventRecord(ev[22], stream));
+  size_t tb = tb_scan;
+  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, M.flag, scan, nI, stream));
+  int64_t total = 0;
+  unsigned long long hbad = ~0ull;
+  HIPCHK(hipMemcpyAsync(&total, scan + (n - 1), 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(&hbad, bad, 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  const int64_t P = total & 0xFFFFFFFFll, n_drop = total >> 32;
+  const int64_t first_bad = hbad == ~0ull ? -1 : (int64_t)(hbad >> 8);
+  const int32_t first_reason = hbad == ~0ull ? 0 : (int32_t)(hbad & 0xFF);
+  const int64_t nP = std::max<int64_t>(P, 1);
+  FormatOut o{};
+  o.key = need<unsigned long long>(S_FM_KEY, nP);
+  o.lat = need<float>(S_FM_LAT, nP);
+  o.lon = need<float>(S_FM_LON, nP);
+  o.acc = need<int32_t>(S_FM_ACC, nP);
+  o.time = need<int64_t>(S_FM_TIME, nP);
+  o.ts = need<int64_t>(S_FM_TS, nP);
+  o.msg = need<int64_t>(S_FM_MSG, nP);
+  o.uoff = need<int64_t>(S_FM_UOFF, nP);
+  o.ulen = need<int32_t>(S_FM_ULEN, nP);
+  o.kidx = need<int32_t>(S_IN_KIDX, nP);
+  if (!o.key || !o.lat || !o.lon || !o.acc || !o.time || !o.ts || !o.msg || !o.uoff || !o.ulen || !o.kidx)
+    return fail("device allocation failed (formatter)");
+  if (P > 0) {
+    k_format_emit<<<grid_for(n, 256), 256, 0, stream>>>(M, scan, ts_in, msgs->timestamp_all, o);
+    // two different uuids of the chunk under one hash: K11's stage, K11's refusal
+    uint64_t* key_a = need<uint64_t>(S_IN_KEY_A, P);
+    uint64_t* key_b = need<uint64_t>(S_IN_KEY_B, P);
+    int32_t* val_b = need<int32_t>(S_IN_VAL_B, P);
+    int64_t* head = need<int64_t>(S_IN_HEAD, P);
+    if (!key_a || !key_b || !val_b || !head) return fail("device allocation failed (formatter)");
+    HIPCHK(hipMemsetAsync(bad, 0xFF, 8, stream));
+    const int rc = uuid_group_heads(stream, M.hash, o.kidx, P, M.uoff, M.ulen, d_text, tmp, tb_sort, key_a, key_b,
+                                    val_b, head, bad, err);
+    if (rc != OTR_OK) return rc;
+    HIPCHK(hipMemcpyAsync(&hbad, bad, 8, hipMemcpyDeviceToHost, stream));
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ev[23], stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (P > 0 && hbad != ~0ull) {
+    out->first_bad = (int64_t)(hbad >> 8);
+    out->first_bad_reason = (int32_t)(hbad & 0xFF);
+    if (err) *err = "uuid hash collision at message " + std::to_string(out->first_bad);
+    return OTR_BAD_REQUEST;
+  }
+  HIPCHK(hipEventElapsedTime(&out->parse_ms, ev[21], ev[22]));
+  HIPCHK(hipEventElapsedTime(&out->total_ms, ev[20], ev[23]));
+  out->n_points = P;
+  out->n_dropped = n_drop;
+  out->n_unsupported = n - P - n_drop;
+  out->first_bad = first_bad;
+  out->first_bad_reason = first_reason;
+  out->points.n = P;
+  out->points.key = (const uint64_t*)o.key;
+  out->points.lat = o.lat;
+  out->points.lon = o.lon;
+  out->points.accuracy = o.acc;
+  out->points.time = o.time;
+  out->points.timestamp = o.ts;
+  out->d_message = o.msg;
+  out->d_uuid_off = o.uoff;
+  out->d_uuid_len = o.ulen;
+  out->d_status = M.status;
   return OTR_OK;
 }
 

@@ -73,6 +73,62 @@ def graph_info():
     return a.value, b.value, c.value
 
 
+JAVA_TIME_PATTERN = 'yyyy-MM-dd HH:mm:ss'
+
+
+def formatter_from_spec(spec):
+    """The reference's --formatter strings (Formatter.GetFormatter, Formatter.java:36-51) as a
+    format dict for Matcher.format_messages: the first character separates the arguments,
+    'sv' takes separator, uuid, lat, lon, time and accuracy indices and an optional time
+    pattern, 'json' the five keys in that order and an optional pattern.  The separator regex
+    is accepted only as one literal byte, optionally backslash-escaped; the only pattern is
+    'yyyy-MM-dd HH:mm:ss'.  Anything else raises ValueError naming it."""
+    if not isinstance(spec, str) or len(spec) < 2:
+        raise ValueError('formatter spec %r: too short' % (spec,))
+    if spec[0] in '.$|()[]{}^?*+\\':
+        raise ValueError('formatter spec %r: the argument separator %r is a regex, not a literal' % (spec, spec[0]))
+    args = spec[1:].split(spec[0])
+    while args and args[-1] == '':   # String.split drops trailing empty strings
+        args.pop()
+
+    def pattern(p):
+        if p is None:
+            return _lib.OTR_TIME_EPOCH
+        if p != JAVA_TIME_PATTERN:
+            raise ValueError('formatter spec %r: unsupported time pattern %r' % (spec, p))
+        return _lib.OTR_TIME_YMDHMS
+
+    if args and args[0] == 'sv':
+        if len(args) < 7:
+            raise ValueError('formatter spec %r: sv needs a separator and five indices' % (spec,))
+        sep = args[1]
+        if len(sep) == 2 and sep[0] == '\\' and not sep[1].isalnum():
+            sep = sep[1]
+        if len(sep) != 1 or ord(sep) > 255 or ord(sep) < 1 or (sep in '.$|()[{^?*+\\' and len(args[1]) == 1):
+            raise ValueError('formatter spec %r: separator %r is not one literal byte' % (spec, args[1]))
+        try:
+            idx = [int(a) for a in args[2:7]]
+        except ValueError:
+            raise ValueError('formatter spec %r: an index is not an integer' % (spec,))
+        if min(idx) < 0:
+            raise ValueError('formatter spec %r: negative index' % (spec,))
+        return {'type': 'sv', 'separator': sep, 'uuid_index': idx[0], 'lat_index': idx[1], 'lon_index': idx[2],
+                'time_index': idx[3], 'accuracy_index': idx[4],
+                'time_format': pattern(args[7] if len(args) > 7 else None)}
+    if args and args[0] == 'json':
+        if len(args) < 6:
+            raise ValueError('formatter spec %r: json needs five keys' % (spec,))
+        keys = args[1:6]
+        for k in keys:
+            b = k.encode()
+            if not 1 <= len(b) <= 64 or b'"' in b or b'\\' in b:
+                raise ValueError('formatter spec %r: key %r is not 1..64 bytes without quote or backslash'
+                                 % (spec, k))
+        return {'type': 'json', 'uuid_key': keys[0], 'lat_key': keys[1], 'lon_key': keys[2], 'time_key': keys[3],
+                'accuracy_key': keys[4], 'time_format': pattern(args[6] if len(args) > 6 else None)}
+    raise ValueError('formatter spec %r: unsupported raw format parser' % (spec,))
+
+
 class IngestedBatch:
     """The traces otr_ingest left in HBM, in the shape match_batch takes."""
 
@@ -335,6 +391,79 @@ class Matcher:
         p, r = self._session_points(points, device), _lib.SessionResult()
         self._check(self._L.otr_sessions_push(self._h, ctypes.byref(p), ctypes.byref(r)), 'otr_sessions_push')
         return _lib.session_result_to_numpy(r)
+
+    # --- stream formatter (include/otr.h otr_format_messages) ---------
+    def _message_args(self, text, fmt, msg_off, timestamp, device_ptr, nbytes):
+        """(otr_message_format, otr_messages) of a format dict (formatter_from_spec) and a chunk:
+        text as bytes with numpy msg_off / timestamp, or device_ptr + nbytes with msg_off and
+        timestamp as (device address, count) pairs; an int timestamp is every message's."""
+        f = _lib.MessageFormat()
+        f.type = {'sv': _lib.OTR_FORMAT_SV, 'json': _lib.OTR_FORMAT_JSON}[fmt['type']]
+        f.time_format = int(fmt.get('time_format', _lib.OTR_TIME_EPOCH))
+        keep = []
+        if fmt['type'] == 'sv':
+            sep = fmt['separator']
+            f.separator = ord(sep) if isinstance(sep, (str, bytes)) else int(sep)
+            for k in ('uuid_index', 'time_index', 'lat_index', 'lon_index', 'accuracy_index'):
+                setattr(f, k, int(fmt[k]))
+        else:
+            for k in ('uuid_key', 'lat_key', 'lon_key', 'time_key', 'accuracy_key'):
+                v = fmt[k]
+                if v is not None:
+                    v = v.encode() if isinstance(v, str) else bytes(v)
+                    keep.append(v)
+                setattr(f, k, v)
+        m = _lib.Messages()
+        if device_ptr is not None:
+            m.text, m.len, m.memory = device_ptr or None, int(nbytes), _lib.OTR_MEM_DEVICE
+            if msg_off is not None:
+                m.msg_off, m.n_messages = int(msg_off[0]), int(msg_off[1])
+            if isinstance(timestamp, (int, np.integer)):
+                m.timestamp_all = int(timestamp)
+            else:
+                m.timestamp = int(timestamp[0])   # (address, count)
+        else:
+            keep.append(text)
+            m.text = ctypes.cast(ctypes.c_char_p(text), ctypes.c_void_p)
+            m.len, m.memory = len(text), _lib.OTR_MEM_HOST
+            if msg_off is not None:
+                off = np.ascontiguousarray(msg_off, np.int64)
+                if len(off) < 1:
+                    raise ValueError('msg_off needs n_messages + 1 offsets')
+                keep.append(off)
+                m.msg_off, m.n_messages = off.ctypes.data, len(off) - 1
+            if isinstance(timestamp, (int, np.integer)):
+                m.timestamp_all = int(timestamp)
+            else:
+                ts = np.ascontiguousarray(timestamp, np.int64)
+                keep.append(ts)
+                m.timestamp = ts.ctypes.data
+                n = int(m.n_messages) if msg_off is not None else \
+                    text.count(b'\n') + (1 if text and not text.endswith(b'\n') else 0)
+                if len(ts) != n:
+                    raise ValueError('timestamp: %d values for %d messages' % (len(ts), n))
+        self._keep = keep
+        return f, m
+
+    def format_messages(self, text, fmt, msg_off=None, timestamp=0, device_ptr=None, nbytes=None, arrays=True):
+        """otr_format_messages: raw messages → keyed points in HBM.  Returns the dict of
+        _lib.format_result_to_numpy: host copies (none with arrays=False) plus 'device', the
+        result struct whose arrays stay in HBM.  A refused chunk raises ValueError."""
+        f, m = self._message_args(text, fmt, msg_off, timestamp, device_ptr, nbytes)
+        r = _lib.FormatResult()
+        self._check(self._L.otr_format_messages(self._h, ctypes.byref(f), ctypes.byref(m), ctypes.byref(r)),
+                    'otr_format_messages')
+        return _lib.format_result_to_numpy(r, arrays)
+
+    def sessions_push_text(self, text, fmt, msg_off=None, timestamp=0, device_ptr=None, nbytes=None, arrays=True):
+        """otr_sessions_push_text: the chunk's messages formatted and pushed into the session
+        store without a point crossing to the host.  Returns (format dict, session dict); the
+        format dict's host copies are made after the push (none with arrays=False)."""
+        f, m = self._message_args(text, fmt, msg_off, timestamp, device_ptr, nbytes)
+        r, s = _lib.FormatResult(), _lib.SessionResult()
+        self._check(self._L.otr_sessions_push_text(self._h, ctypes.byref(f), ctypes.byref(m), ctypes.byref(r),
+                                                   ctypes.byref(s)), 'otr_sessions_push_text')
+        return _lib.format_result_to_numpy(r, arrays), _lib.session_result_to_numpy(s)
 
     def sessions_punctuate(self, ts):
         r = _lib.SessionResult()

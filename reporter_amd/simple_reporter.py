@@ -348,6 +348,31 @@ def stream_tile_payloads(flush, mode='auto', source='reporter'):
     return out
 
 
+def stream_text_tiles(matcher, chunks, fmt, end_ts, mode='auto', source='reporter'):
+    """The streaming reporter's whole topology with the text uploaded once per chunk and
+    nothing parsed on the host: raw messages → keyed points (KeyedFormattingProcessor) →
+    sessions (BatchingProcessor) → matches and reports → tile rows → cleaned files
+    (AnonymisingProcessor).  The matcher holds an open session store and tile store.  chunks:
+    an iterable of (text, msg_off or None, timestamp) as Matcher.sessions_push_text takes them;
+    end_ts: the stream time of the final punctuate.  Returns {'payloads': those of
+    stream_tile_payloads, 'flush': the tile store's flush, 'counts': messages, points, dropped,
+    unsupported, windows, reports}."""
+    counts = dict.fromkeys(('messages', 'points', 'dropped', 'unsupported', 'windows', 'reports'), 0)
+    for text, msg_off, timestamp in chunks:
+        f, s = matcher.sessions_push_text(text, fmt, msg_off=msg_off, timestamp=timestamp, arrays=False)
+        matcher.tile_store_add_session()
+        for k in ('messages', 'points', 'dropped', 'unsupported'):
+            counts[k] += f['n_' + k]
+        counts['windows'] += s['n_windows']
+        counts['reports'] += s['n_reports']
+    s = matcher.sessions_punctuate(end_ts)
+    matcher.tile_store_add_session()
+    counts['windows'] += s['n_windows']
+    counts['reports'] += s['n_reports']
+    flush = matcher.tile_store_flush()
+    return {'payloads': stream_tile_payloads(flush, mode, source), 'flush': flush, 'counts': counts}
+
+
 def _exchange_by_file_owner(buf, itemsize, world, group=None):
     """All-to-all of fixed-size records whose first 8 bytes are their (hour, tile) file:
     each record goes to file_owner(file); returns the records this rank received (uint8

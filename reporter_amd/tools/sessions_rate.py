@@ -15,7 +15,16 @@ One warm-up replay, then `--repeats` timed ones: median, minimum and maximum are
 flush after the final punctuate; the summed add device_ms, the flush device_ms and the rows held
 at the flush are reported beside the plain run's probes/s.
 
+`--text sv|json` renders the stream as raw messages ("uuid,lat,lon,time,accuracy" lines, or the
+objects of `@json@id@latitude@longitude@timestamp@accuracy`; floats as '%.9g') and feeds every chunk
+through otr_sessions_push_text instead: the text is the only input, no point is parsed on the
+host.  The formatter's parse_ms and total_ms, summed over the pushes, are reported beside the
+push's times; and the whole stream is formatted alone as one text (otr_format_messages: warm-up,
+then `--repeats` steps) for its messages/s and input GB/s, for SV next to K11's parse_ms from
+otr_ingest(OTR_INGEST_JAVA_SV) on the same text.  `--graph city` replays the small city graph.
+
     python -m reporter_amd.tools.sessions_rate --traces 2000 --out profiles/sessions_c2dep.json
+    python -m reporter_amd.tools.sessions_rate --traces 2000 --text json --out profiles/formatter_c2dep_json.json
     python -m reporter_amd.tools.sessions_rate --traces 2000 --tile-store --out profiles/tile_store_c2dep.json
 """
 import argparse
@@ -41,19 +50,75 @@ def stream(tr):
             'timestamp': tm[order] * 1000}
 
 
-def replay(m, pts, cuts, max_points, batch_ms, tile_rows=0):
+TEXT_FORMATS = {'sv': {'type': 'sv', 'separator': ',', 'uuid_index': 0, 'lat_index': 1, 'lon_index': 2,
+                       'time_index': 3, 'accuracy_index': 4, 'time_format': 0},
+                'json': {'type': 'json', 'uuid_key': 'id', 'lat_key': 'latitude', 'lon_key': 'longitude',
+                         'time_key': 'timestamp', 'accuracy_key': 'accuracy', 'time_format': 0}}
+
+
+def render(pts, kind):
+    """The stream as one message per point (bytes, no newline)."""
+    shape = ('veh-%d,%.9g,%.9g,%d,%d' if kind == 'sv' else
+             '{"id":"veh-%d","latitude":%.9g,"longitude":%.9g,"timestamp":%d,"accuracy":%d}')
+    return [(shape % (k, la, lo, t, a)).encode() for k, la, lo, t, a in zip(
+        pts['key'].tolist(), pts['lat'].astype(np.float64).tolist(), pts['lon'].astype(np.float64).tolist(),
+        pts['time'].tolist(), pts['accuracy'].tolist())]
+
+
+def text_chunks(msgs, pts, cuts):
+    """(text, offsets, timestamps) per chunk, as Matcher.sessions_push_text takes them."""
+    out = []
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        off = np.concatenate([[0], np.cumsum([len(x) for x in msgs[a:b]])]).astype(np.int64)
+        out.append((b''.join(msgs[a:b]), off, pts['timestamp'][a:b]))
+    return out
+
+
+def formatter_rates(m, msgs, kind, repeats):
+    """otr_format_messages on the whole stream as one newline-separated text: a warm-up, then
+    `repeats` steps; for SV also K11's parse on the same text."""
+    text = b'\n'.join(msgs) + b'\n'
+    fmt = TEXT_FORMATS[kind]
+    m.format_messages(text, fmt, arrays=False)
+    runs = [m.format_messages(text, fmt, arrays=False) for _ in range(repeats)]
+    assert runs[0]['n_points'] == len(msgs), (runs[0]['n_points'], len(msgs))
+    parse = sorted(r['parse_ms'] for r in runs)
+    total = sorted(r['total_ms'] for r in runs)
+    med = float(np.median(parse))
+    out = {'messages': len(msgs), 'bytes': len(text), 'bytes_per_message': round(len(text) / len(msgs), 1),
+           'parse_ms_median_min_max': [round(med, 4), round(parse[0], 4), round(parse[-1], 4)],
+           'total_ms_median_min_max': [round(float(np.median(total)), 4), round(total[0], 4), round(total[-1], 4)],
+           'parse_messages_per_s': round(len(msgs) / (1e-3 * med), 1), 'parse_GB_per_s': round(len(text) / (1e6 * med), 3),
+           'total_messages_per_s': round(len(msgs) / (1e-3 * float(np.median(total))), 1)}
+    if kind == 'sv':
+        from reporter_amd import _lib
+        kw = dict(rules=_lib.OTR_INGEST_JAVA_SV, separator=',', uuid_index=0, lat_index=1, lon_index=2, time_index=3,
+                  accuracy_index=4, time_format=_lib.OTR_TIME_EPOCH, inactivity=120)
+        m.ingest(text, **kw)
+        k11 = sorted(m.ingest(text, **kw)[0].parse_ms for _ in range(repeats))
+        out['k11_parse_ms_median_min_max'] = [round(float(np.median(k11)), 4), round(k11[0], 4), round(k11[-1], 4)]
+    return out
+
+
+def replay(m, pts, cuts, max_points, batch_ms, tile_rows=0, text=None):
     """One replay: a fresh store, every chunk pushed, a final punctuate.  tile_rows > 0: a tile
-    store of that many rows takes every result (add_session) and is flushed at the end."""
+    store of that many rows takes every result (add_session) and is flushed at the end.
+    text: (kind, chunks of text_chunks): every chunk goes through sessions_push_text."""
     m.sessions_open(int(pts['key'].max()) + 1, max_points)
     if tile_rows:
         m.tile_store_open(tile_rows, 3600, 2)
     add_ms = []
-    chunks = [{k: v[a:b] for k, v in pts.items()} for a, b in zip(cuts[:-1], cuts[1:])]
+    chunks = text[1] if text else [{k: v[a:b] for k, v in pts.items()} for a, b in zip(cuts[:-1], cuts[1:])]
     rounds = windows = reports = 0
-    dev_ms = match_ms = 0.0
+    dev_ms = match_ms = parse_ms = format_ms = 0.0
     t0 = time.perf_counter()
     for c in chunks:
-        r = m.sessions_push(c)
+        if text:
+            f, r = m.sessions_push_text(c[0], TEXT_FORMATS[text[0]], msg_off=c[1], timestamp=c[2], arrays=False)
+            parse_ms += f['parse_ms']
+            format_ms += f['total_ms']
+        else:
+            r = m.sessions_push(c)
         rounds += r['n_rounds']
         windows += r['n_windows']
         reports += r['n_reports']
@@ -74,7 +139,7 @@ def replay(m, pts, cuts, max_points, batch_ms, tile_rows=0):
                 'files_empty': fl['n_files_empty']}
         m.tile_store_close()
     m.sessions_close()
-    return {'tile': tile, 'wall_s': wall, 'rounds': rounds, 'windows': windows, 'reports': reports, 'stream_ms': dev_ms, 'match_ms': match_ms,
+    return {'tile': tile, 'wall_s': wall, 'parse_ms': parse_ms, 'format_ms': format_ms, 'rounds': rounds, 'windows': windows, 'reports': reports, 'stream_ms': dev_ms, 'match_ms': match_ms,
             'evicted': ev['n_evicted'], 'eviction_windows': ev['n_windows'], 'chunks': len(chunks)}
 
 
@@ -88,13 +153,18 @@ def main():
     ap.add_argument('--tile-store', action='store_true',
                     help='also replay with a tile store: add_session after every push, one flush at the end')
     ap.add_argument('--tile-rows', type=int, default=1 << 22, help='max_rows of that store')
+    ap.add_argument('--text', choices=['sv', 'json'], default=None,
+                    help='render the stream as messages and push them through otr_sessions_push_text')
+    ap.add_argument('--graph', choices=['metro', 'city'], default='metro')
+    ap.add_argument('--format-traces', type=int, default=0,
+                    help='with --text: traces of the stream formatted alone (default: --traces)')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if ROOT not in sys.path:
         sys.path.insert(0, ROOT)
     from reporter_amd import matcher as M
     from reporter_amd.tools import gen
-    gpath = gen.graph_path('metro', args.graphs)
+    gpath = gen.graph_path(args.graph, args.graphs)
     tr = gen.make_traces(gpath, args.traces, 100, 15, 10.0, 2, 0.0, 0.0, None, t_begin=T_BEGIN, t_spread=1800)
     M.configure(M.default_config(gpath))
     m = M.Matcher()
@@ -109,16 +179,27 @@ def main():
         m.match_batch(one, copy_out=False, copy_reports=True)
         tb.append(1e3 * (time.perf_counter() - t0))
     batch_ms = float(np.median(tb))
-    res = {'workload': 'c2dep: metro graph, %d traces x 100 probes @15 s, sigma 10 m, deployed configuration' % args.traces,
+    msgs = render(pts, args.text) if args.text else None
+    res = {'workload': 'c2dep: %s graph, %d traces x 100 probes @15 s, sigma 10 m, deployed configuration' % (args.graph, args.traces),
            'probes': n, 'gates': '500 m, 10 points, 60 s; session_gap 60000; max_points %d' % args.max_points,
            'method': 'arrays on the host -> otr_sessions_push per chunk -> windows and reports on the host; '
                      '1 warm-up replay, %d timed; median [min, max]' % args.repeats,
            'smallest_batch_ms': round(batch_ms, 3), 'chunks': {}}
+    if args.text:
+        res['text'] = args.text
+        res['method'] = res['method'].replace('arrays on the host -> otr_sessions_push',
+                                              'message text on the host -> otr_sessions_push_text')
+        alone = msgs
+        if args.format_traces > args.traces:
+            alone = render(stream(gen.make_traces(gpath, args.format_traces, 100, 15, 10.0, 2, 0.0, 0.0, None,
+                                                  t_begin=T_BEGIN, t_spread=1800)), args.text)
+        res['formatter'] = formatter_rates(m, alone, args.text, max(args.repeats, 5))
     for cs in args.chunk_s:
         sec = (pts['time'] - pts['time'][0]) // cs
         cuts = [0] + (np.flatnonzero(np.diff(sec)) + 1).tolist() + [n]
-        replay(m, pts, cuts, args.max_points, batch_ms)
-        runs = [replay(m, pts, cuts, args.max_points, batch_ms) for _ in range(args.repeats)]
+        text = (args.text, text_chunks(msgs, pts, cuts)) if args.text else None
+        replay(m, pts, cuts, args.max_points, batch_ms, text=text)
+        runs = [replay(m, pts, cuts, args.max_points, batch_ms, text=text) for _ in range(args.repeats)]
         rate = sorted(n / r['wall_s'] for r in runs)
         r = runs[0]
         wall = float(np.median([x['wall_s'] for x in runs]))
@@ -131,9 +212,13 @@ def main():
             'stream_ms': round(float(np.median([x['stream_ms'] for x in runs])), 1),
             'match_ms': round(float(np.median([x['match_ms'] for x in runs])), 1),
             'rounds_times_smallest_batch_ms': round(r['rounds'] * batch_ms, 1)}
+        if args.text:
+            res['chunks']['%d_s' % cs].update(
+                format_parse_ms=round(float(np.median([x['parse_ms'] for x in runs])), 2),
+                format_total_ms=round(float(np.median([x['format_ms'] for x in runs])), 2))
         if args.tile_store:
-            replay(m, pts, cuts, args.max_points, batch_ms, args.tile_rows)
-            truns = [replay(m, pts, cuts, args.max_points, batch_ms, args.tile_rows) for _ in range(args.repeats)]
+            replay(m, pts, cuts, args.max_points, batch_ms, args.tile_rows, text)
+            truns = [replay(m, pts, cuts, args.max_points, batch_ms, args.tile_rows, text) for _ in range(args.repeats)]
             trate = sorted(n / x['wall_s'] for x in truns)
             t = truns[0]['tile']
 
