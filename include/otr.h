@@ -592,6 +592,66 @@ int otr_sessions_windows(otr_matcher* m, otr_session_result* out);
 
 int otr_sessions_snapshot(otr_matcher* m, otr_session_snapshot* out);
 
+/* ---- restore, export and move -----------------------------------
+ * Sessions as the values Batch.Serder writes (Batch.java:110-116, Point.java:50-55), big-endian:
+ * int32 count, float max_separation, int64 last_update, then count x (float lat, float lon,
+ * int32 accuracy, int64 time): 16 + 20*count bytes.  Record i is bytes[rec_off[i] .. rec_off[i+1]);
+ * bytes may start at any address and records at any offset.  key[i] is the 64-bit key of the
+ * record's uuid: otr_uuid_key over the changelog key's UTF-8 bytes. */
+typedef struct otr_session_records {
+  int64_t n_records;  int64_t n_bytes;
+  int32_t memory;     int32_t reserved;        /* OTR_MEM_HOST / OTR_MEM_DEVICE (input) */
+  const uint64_t* key;  const int64_t* rec_off;  const uint8_t* bytes;
+  /* export only: the same three arrays in HBM */
+  const uint64_t* d_key;  const int64_t* d_rec_off;  const uint8_t* d_bytes;
+} otr_session_records;
+
+/* Why a restore is refused; where a session has several reasons the lowest value is reported. */
+#define OTR_RESTORE_E_LAYOUT 1     /* snapshot: point_off[0] != 0, not non-decreasing, or its last value is not
+                                      n_points.  Records: offsets not non-decreasing or beyond n_bytes, a record
+                                      shorter than 16 bytes or not 16 + 20*count long (64-bit; count < 0 too) */
+#define OTR_RESTORE_E_KEY 2        /* the key is OTR_NO_ID */
+#define OTR_RESTORE_E_COUNT 3      /* count outside 1 .. max_points - 1 */
+#define OTR_RESTORE_E_DUPLICATE 4  /* not the first occurrence of its key in the input */
+#define OTR_RESTORE_E_LIVE 5       /* the key has a live session in the store */
+#define OTR_RESTORE_E_FULL 6       /* live + given > max_sessions (bad_session -1) */
+
+typedef struct otr_session_restore_result {
+  int64_t n_sessions, n_points;   /* restored by this call */
+  int64_t bad_session;            /* lowest refused index, -1: none (or the refusal is of the whole input) */
+  int32_t bad_reason;             /* OTR_RESTORE_E_*, 0 when restored */
+  int32_t n_live;                 /* after the call */
+  float device_ms;  int32_t reserved;
+} otr_session_restore_result;
+
+/* Merges the given sessions into the open store (it does not replace it).  max_sep and
+ * last_update are taken as stored, by bits, never recomputed (what the deserialiser does).
+ * All or nothing: on any refusal the call returns OTR_BAD_REQUEST with bad_session / bad_reason
+ * filled and the store untouched.  bad_session is the lowest index with any per-session reason;
+ * OTR_RESTORE_E_FULL is reported only when no session has one.  A count of 0 is refused because
+ * the reference never stores an empty Batch (BatchingProcessor.java:77), a count of max_points
+ * because a live session never holds that many after a call.  A key that was deleted from
+ * the store earlier is restorable.  Refused too (bad_session -1, bad_reason 0): no store, or an
+ * advance / commit sequence or a chunk open.  memory: where the snapshot's arrays are. */
+int otr_sessions_restore(otr_matcher* m, const otr_session_snapshot* snap, int32_t memory,
+                         otr_session_restore_result* out);
+int otr_sessions_restore_records(otr_matcher* m, const otr_session_records* recs, otr_session_restore_result* out);
+
+/* Every live session in ascending key order as records, in host memory and in HBM (memory is
+ * set to OTR_MEM_HOST).  The arrays are owned by the matcher and valid until its next session
+ * call. */
+int otr_sessions_export_records(otr_matcher* m, otr_session_records* out);
+
+/* The sessions with key % n_parts == part, in ascending key order and the layout of the
+ * snapshot.  The keys are K11's mixed 64-bit hash already, so the remainder spreads them evenly:
+ * this is the shard rule of the uuid-sharded layout.  remove != 0 also deletes them
+ * exactly as an eviction does (no report is made).  n_parts 1, part 0, remove 0 is the snapshot.
+ * Refused while an advance / commit sequence or a chunk is open. */
+int otr_sessions_take(otr_matcher* m, int32_t n_parts, int32_t part, int32_t remove, otr_session_snapshot* out);
+
+/* K11's 64-bit hash of a uuid's bytes, on the host: the key of a changelog record. */
+uint64_t otr_uuid_key(const char* uuid, int64_t len);
+
 /* ---- stream formatter: raw messages → keyed points in HBM -------
  * What KeyedFormattingProcessor.java:32-43 does with Formatter.formatSV / formatJSON: every
  * message ends as a point (kept), is dropped (the reference certainly throws and the

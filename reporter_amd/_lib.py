@@ -38,6 +38,9 @@ FORMAT_REASONS = {1: 'fields', 2: 'float', 3: 'int', 4: 'time', 5: 'accuracy', 6
                   32: 'precision', 33: 'accuracy range', 34: 'depth', 35: 'trailing', 36: 'escape', 37: 'number',
                   38: 'kind', 39: 'no id'}
 OTR_NO_ID = 0xFFFFFFFFFFFFFFFF
+OTR_RESTORE_E_LAYOUT, OTR_RESTORE_E_KEY, OTR_RESTORE_E_COUNT = 1, 2, 3
+OTR_RESTORE_E_DUPLICATE, OTR_RESTORE_E_LIVE, OTR_RESTORE_E_FULL = 4, 5, 6
+RESTORE_REASONS = {1: 'layout', 2: 'key', 3: 'count', 4: 'duplicate', 5: 'live', 6: 'full'}
 HIST_BINS = 8
 KMAX = 64
 STAGES = ['states', 'candidates', 'link', 'route', 'route_big', 'viterbi', 'paths', 'paths_big', 'segments',
@@ -55,7 +58,8 @@ EXPORTS = ['otr_configure', 'otr_configure_json', 'otr_matcher_new', 'otr_matche
            'otr_sessions_push', 'otr_sessions_punctuate', 'otr_sessions_advance', 'otr_sessions_commit',
            'otr_sessions_windows', 'otr_sessions_snapshot', 'otr_tile_store_open', 'otr_tile_store_close',
            'otr_tile_store_add_session', 'otr_tile_store_add_reports', 'otr_tile_store_add_rows',
-           'otr_tile_store_flush', 'otr_format_messages', 'otr_sessions_push_text']
+           'otr_tile_store_flush', 'otr_format_messages', 'otr_sessions_push_text', 'otr_sessions_restore',
+           'otr_sessions_restore_records', 'otr_sessions_export_records', 'otr_sessions_take', 'otr_uuid_key']
 
 
 class ServiceSplit(ctypes.Structure):
@@ -239,6 +243,21 @@ class SessionSnapshot(ctypes.Structure):
                 [(k, P(ct)) for k, ct, _ in SNAPSHOT_FIELDS])
 
 
+class SessionRecords(ctypes.Structure):
+    """otr_session_records (include/otr.h): sessions as the byte values Batch.Serder writes."""
+    _fields_ = [('n_records', ctypes.c_int64), ('n_bytes', ctypes.c_int64), ('memory', ctypes.c_int32),
+                ('reserved', ctypes.c_int32), ('key', ctypes.c_void_p), ('rec_off', ctypes.c_void_p),
+                ('bytes', ctypes.c_void_p), ('d_key', ctypes.c_void_p), ('d_rec_off', ctypes.c_void_p),
+                ('d_bytes', ctypes.c_void_p)]
+
+
+class SessionRestoreResult(ctypes.Structure):
+    """otr_session_restore_result (include/otr.h): what a restore did, or why it was refused."""
+    _fields_ = [('n_sessions', ctypes.c_int64), ('n_points', ctypes.c_int64), ('bad_session', ctypes.c_int64),
+                ('bad_reason', ctypes.c_int32), ('n_live', ctypes.c_int32), ('device_ms', ctypes.c_float),
+                ('reserved', ctypes.c_int32)]
+
+
 class TileStoreConfig(ctypes.Structure):
     """otr_tile_store_config (include/otr.h)."""
     _fields_ = [('max_rows', ctypes.c_int64), ('quantisation', ctypes.c_int32), ('privacy', ctypes.c_int32)]
@@ -351,6 +370,20 @@ def snapshot_to_numpy(r):
             for k, _, dt in SNAPSHOT_FIELDS}
 
 
+def records_to_numpy(r):
+    """An exported otr_session_records as host copies (key, rec_off, bytes); 'device' holds the
+    struct, whose d_* arrays stay in HBM until the matcher's next session call."""
+    n, nb = int(r.n_records), int(r.n_bytes)
+
+    def arr(ptr, count, dt):
+        if not ptr or count == 0:
+            return np.zeros(count, dt)
+        return np.ctypeslib.as_array(ctypes.cast(ptr, P(np.ctypeslib.as_ctypes_type(dt))), shape=(count,)).copy()
+    off = arr(r.rec_off, n + 1, np.int64)
+    return {'key': arr(r.key, n, np.uint64), 'rec_off': off if len(off) else np.zeros(1, np.int64),
+            'bytes': arr(r.bytes, nb, np.uint8), 'device': r}
+
+
 # otr_hist_entry (include/otr.h), 32 bytes
 HIST_ENTRY = np.dtype([('file', '<u8'), ('id', '<u8'), ('next_id', '<u8'), ('speed_bin', '<u4'), ('count', '<u4')])
 
@@ -404,6 +437,15 @@ def lib():
         L.otr_sessions_commit.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
         L.otr_sessions_windows.argtypes = [ctypes.c_void_p, P(SessionResult)]
         L.otr_sessions_snapshot.argtypes = [ctypes.c_void_p, P(SessionSnapshot)]
+    if hasattr(L, 'otr_sessions_restore'):
+        L.otr_sessions_restore.argtypes = [ctypes.c_void_p, P(SessionSnapshot), ctypes.c_int32,
+                                           P(SessionRestoreResult)]
+        L.otr_sessions_restore_records.argtypes = [ctypes.c_void_p, P(SessionRecords), P(SessionRestoreResult)]
+        L.otr_sessions_export_records.argtypes = [ctypes.c_void_p, P(SessionRecords)]
+        L.otr_sessions_take.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                        P(SessionSnapshot)]
+        L.otr_uuid_key.argtypes = [ctypes.c_char_p, ctypes.c_int64]
+        L.otr_uuid_key.restype = ctypes.c_uint64
     if hasattr(L, 'otr_tile_store_open'):  # (an A/B build of an earlier round may lack them)
         L.otr_tile_store_open.argtypes = [ctypes.c_void_p, P(TileStoreConfig)]
         L.otr_tile_store_close.argtypes = [ctypes.c_void_p]

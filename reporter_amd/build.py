@@ -158,6 +158,20 @@ def build_formatcheck(force=False):
     return lib
 
 
+def build_recordcheck(force=False, sanitize=False, out=None):
+    """tools/recordcheck: the session records' per-record rules as a stand-alone host program
+    (CPU tests only).  sanitize=True: built with AddressSanitizer and UndefinedBehaviorSanitizer
+    (any report is fatal), to `out` or tools/recordcheck_san."""
+    src = os.path.join(PKG, 'tools', 'recordcheck.cpp')
+    exe = out or os.path.join(PKG, 'tools', 'recordcheck_san' if sanitize else 'recordcheck')
+    deps = [src, os.path.join(CSRC, 'otr_session_records.h')]
+    if force or not _newer(exe, deps):
+        flags = ['-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
+                 '-fno-omit-frame-pointer'] if sanitize else ['-O2']
+        _run(['g++', '-std=c++17', '-Wall'] + flags + ['-o', exe, src])
+    return exe
+
+
 def build_mincheck(force=False):
     """tools/libmincheck.so: host build of the node tables' IN-gap codes (CPU tests only)."""
     src = os.path.join(PKG, 'tools', 'mincheck.cpp')
@@ -176,6 +190,7 @@ def build_all(force=False):
     build_parsecheck(force)
     build_formatcheck(force)
     build_mincheck(force)
+    build_recordcheck(force)
     build_oracle(force)
     build_calib(force)
     with ThreadPoolExecutor(max_workers=3) as ex:

@@ -494,6 +494,26 @@ int otr_sessions_snapshot(otr_matcher* m, otr_session_snapshot* out) {
   OTR_SESSIONS_CALL(!m || !out, sessions_snapshot(out, &err));
 }
 
+// restore, export and move (K17): Batch.Serder's values in and out (Batch.java:92-146)
+int otr_sessions_restore(otr_matcher* m, const otr_session_snapshot* snap, int32_t memory,
+                         otr_session_restore_result* out) {
+  OTR_SESSIONS_CALL(!m || !snap || !out, sessions_restore(snap, memory, out, &err));
+}
+
+int otr_sessions_restore_records(otr_matcher* m, const otr_session_records* recs, otr_session_restore_result* out) {
+  OTR_SESSIONS_CALL(!m || !recs || !out, sessions_restore_records(recs, out, &err));
+}
+
+int otr_sessions_export_records(otr_matcher* m, otr_session_records* out) {
+  OTR_SESSIONS_CALL(!m || !out, sessions_export_records(out, &err));
+}
+
+int otr_sessions_take(otr_matcher* m, int32_t n_parts, int32_t part, int32_t remove, otr_session_snapshot* out) {
+  OTR_SESSIONS_CALL(!m || !out, sessions_take(n_parts, part, remove, out, &err));
+}
+
+uint64_t otr_uuid_key(const char* uuid, int64_t len) { return otr::uuid_key_host(uuid, uuid ? len : 0); }
+
 // the stream formatter (K16): KeyedFormattingProcessor.java:32-43 over Formatter.java:97-124
 int otr_format_messages(otr_matcher* m, const otr_message_format* fmt, const otr_messages* msgs,
                         otr_format_result* out) {

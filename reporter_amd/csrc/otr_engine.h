@@ -81,6 +81,8 @@ struct GSlab {
 // (oracle orc_turn_table: the same operations)
 void turn_table(double factor, int32_t* tab181);
 
+uint64_t uuid_key_host(const char* uuid, int64_t len);  // K11's uuid_hash over host bytes
+
 struct SessionStore;                    // otr_sessions.hip (K14)
 void sessions_destroy(SessionStore* s);  // frees the store's device memory
 
@@ -193,6 +195,12 @@ struct Matcher {
   int sessions_commit(const int32_t* shape_used, const int32_t* status, int memory, std::string* err);
   int sessions_windows(otr_session_result* out, std::string* err);
   int sessions_snapshot(otr_session_snapshot* out, std::string* err);
+  // restore, export and move (K17)
+  int sessions_restore(const otr_session_snapshot* snap, int memory, otr_session_restore_result* out,
+                       std::string* err);
+  int sessions_restore_records(const otr_session_records* recs, otr_session_restore_result* out, std::string* err);
+  int sessions_export_records(otr_session_records* out, std::string* err);
+  int sessions_take(int n_parts, int part, int remove, otr_session_snapshot* out, std::string* err);
   // the tile store (K15, otr_tilestore.hip)
   int tile_store_open(const otr_tile_store_config* cfg, std::string* err);
   int tile_store_close(std::string* err);

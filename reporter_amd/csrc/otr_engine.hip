@@ -3521,4 +3521,9 @@ int Matcher::format_messages_impl(const otr_message_format* fmt, const otr_messa
   return OTR_OK;
 }
 
+// K11's uuid_hash on the host: the key of a changelog record (otr_uuid_key)
+uint64_t uuid_key_host(const char* uuid, int64_t len) {
+  return uuid_hash(reinterpret_cast<const uint8_t*>(uuid), 0, len > 0 ? len : 0);
+}
+
 }  // namespace otr

@@ -9,6 +9,7 @@
 
 #include "../../include/otr.h"
 #include "otr_device.h"
+#include "otr_session_records.h"
 
 namespace otr {
 
@@ -391,6 +392,157 @@ __global__ void k_ses_evict_windows(int32_t n_list, const int32_t* list, const u
   win_trig[w] = -1 - (int64_t)g;
   win_n[w] = cnt_n[g];
   win_key[w] = key[g];
+}
+
+// ---- K17: restore, export and move (include/otr.h otr_sessions_restore ...) ----------------
+
+// sessions given to a restore: SoA (off counts points, `total` is n_points) or records (off
+// counts bytes, `total` is n_bytes)
+struct SesGiven {
+  int64_t n, total;
+  const unsigned long long* key;
+  const int64_t* off;  // [n + 1]
+  const float *max_sep, *lat, *lon;
+  const int64_t *last, *time;
+  const int32_t* acc;
+  const uint8_t* bytes;
+};
+
+constexpr unsigned long long kSesNoBad = ~0ull;
+constexpr int32_t kSesNoLane = 0x7F7F7F7F;  // the scratch array's fill: above every lane index
+
+__device__ inline void ses_refuse(unsigned long long* bad, int64_t i, int32_t reason) {
+  atomicMin(bad, ((unsigned long long)i << 8) | (unsigned long long)reason);
+}
+
+// one lane per given session: layout, key and count, then the table walk of k_ses_insert.  A
+// live key is refused; so is every occurrence of a key but its first.  The lanes of one key
+// end at one entry and leave the lowest of their indices in first[entry]: a lane that finds a
+// lower one there refuses itself, a lane that replaces a higher one refuses that one, so
+// every occurrence but the first is refused whichever lane claimed the entry, and no lane
+// waits.  bad: the lowest (index << 8 | reason), reasons in the order of their precedence.
+template <bool REC>
+__global__ void k_ses_restore_check(SesTable t, SesGiven g, int32_t max_points, int32_t* first, int32_t* lane_entry,
+                                    int32_t* is_new, unsigned long long* bad, int32_t* cnt) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= g.n) return;
+  lane_entry[i] = -1;
+  is_new[i] = 0;
+  const int64_t b = g.off[i], e = g.off[i + 1];
+  int64_t count;
+  bool layout;
+  if (REC) {
+    int32_t c32;
+    layout = rec_layout_ok(g.bytes, g.total, b, e, &c32);
+    count = c32;
+  } else {
+    layout = !(e < b || (i == 0 && b != 0) || (i == g.n - 1 && e != g.total));
+    count = e - b;
+  }
+  const unsigned long long key = g.key[i];
+  if (!layout) return ses_refuse(bad, i, OTR_RESTORE_E_LAYOUT);
+  if (key == kSesEmpty) return ses_refuse(bad, i, OTR_RESTORE_E_KEY);
+  if (count < 1 || count > (int64_t)max_points - 1) return ses_refuse(bad, i, OTR_RESTORE_E_COUNT);
+  uint32_t q = ses_hash(key, t.cap);
+  for (uint32_t probe = 0; probe < t.cap; ++probe) {
+    unsigned long long k = t.key[q];
+    bool mine = false;
+    if (k == kSesEmpty) {
+      k = atomicCAS(&t.key[q], kSesEmpty, key);
+      mine = k == kSesEmpty;
+    }
+    if (mine || k == key) {
+      const int32_t slot = mine ? kSesNew : t.slot[q];
+      if (slot >= 0) return ses_refuse(bad, i, OTR_RESTORE_E_LIVE);
+      if (slot == kSesNew) {  // claimed in this call, by this lane or by another of its key
+        lane_entry[i] = (int32_t)q;
+        is_new[i] = mine ? 1 : 0;
+        const int32_t old = atomicMin(&first[q], (int32_t)i);
+        if (old < (int32_t)i) ses_refuse(bad, i, OTR_RESTORE_E_DUPLICATE);
+        else if (old != kSesNoLane) ses_refuse(bad, old, OTR_RESTORE_E_DUPLICATE);
+        return;
+      }
+      // (a dead entry of this key: the walk goes on to a new one)
+    }
+    q = q + 1 == t.cap ? 0 : q + 1;
+  }
+  atomicOr(&cnt[SES_FLAGS], kSesFlagFull);
+}
+
+// one wave per given session (none was refused, so each claimed its entry): the session from
+// the free stack by its index, the points strided over the lanes; records are decoded on the
+// way, byte by byte, so that neither the buffer nor a record needs any alignment
+template <bool REC>
+__global__ __launch_bounds__(64) void k_ses_restore_copy(SesTable t, SesStore s, SesGiven g, const int32_t* lane_entry,
+                                                         const int32_t* free_list, int32_t n_free) {
+  const int64_t i = blockIdx.x;
+  if (i >= g.n) return;
+  const int32_t slot = free_list[n_free - 1 - (int32_t)i];
+  const size_t base = (size_t)slot * (size_t)s.max_points;
+  const int64_t b = g.off[i];
+  int32_t n;
+  float ms;
+  int64_t last;
+  if (REC) {
+    rec_header_get(g.bytes + b, &n, &ms, &last);
+  } else {
+    n = (int32_t)(g.off[i + 1] - b);
+    ms = g.max_sep[i];
+    last = g.last[i];
+  }
+  for (int32_t k = threadIdx.x; k < n; k += 64) {
+    float la, lo;
+    int32_t ac;
+    int64_t tm;
+    if (REC) {
+      rec_point_get(g.bytes + b, k, &la, &lo, &ac, &tm);
+    } else {
+      la = g.lat[b + k];
+      lo = g.lon[b + k];
+      ac = g.acc[b + k];
+      tm = g.time[b + k];
+    }
+    s.lat[base + k] = la;
+    s.lon[base + k] = lo;
+    s.acc[base + k] = ac;
+    s.time[base + k] = tm;
+  }
+  if (threadIdx.x == 0) {
+    const int32_t e = lane_entry[i];
+    t.slot[e] = slot;
+    s.n[slot] = n;
+    s.max_sep[slot] = ms;
+    s.last[slot] = last;
+    s.skey[slot] = g.key[i];
+    s.entry[slot] = e;
+  }
+}
+
+// listed sessions: the length of each one's record
+__global__ void k_ses_record_len(int32_t n_list, const int32_t* list, SesStore s, int64_t* len) {
+  const int32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g < n_list) len[g] = kRecHeader + kRecPoint * (int64_t)s.n[list[g]];
+}
+
+// one wave per listed session: lane 0 writes the header, the lanes the points
+__global__ __launch_bounds__(64) void k_ses_encode(int32_t n_list, const int32_t* list, const int64_t* rec_off,
+                                                   SesStore s, uint8_t* bytes) {
+  const int32_t g = blockIdx.x;
+  if (g >= n_list) return;
+  const int32_t slot = list[g];
+  const size_t base = (size_t)slot * (size_t)s.max_points;
+  uint8_t* rec = bytes + rec_off[g];
+  const int32_t n = (int32_t)((rec_off[g + 1] - rec_off[g] - kRecHeader) / kRecPoint);
+  if (threadIdx.x == 0) rec_header_put(rec, n, s.max_sep[slot], s.last[slot]);
+  for (int32_t k = threadIdx.x; k < n; k += 64)
+    rec_point_put(rec, k, s.lat[base + k], s.lon[base + k], s.acc[base + k], s.time[base + k]);
+}
+
+// the live sessions of one part: key % n_parts == part (the keys are mixed hashes already)
+__global__ void k_ses_flag_part(SesStore s, uint32_t n_parts, uint32_t part, int32_t* flag) {
+  const int32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= s.max_sessions) return;
+  flag[slot] = (s.n[slot] > 0 && s.skey[slot] % n_parts == part) ? 1 : 0;
 }
 
 }  // namespace otr

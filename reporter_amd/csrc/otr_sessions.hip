@@ -1,6 +1,7 @@
 // otr_sessions.hip — host side of the session store (K14, otr_sessions.h): the store's
 // device memory, the passes of a chunk (insert, assign, group), the rounds (advance, gather,
-// match, commit), punctuate and the snapshot.  include/otr.h otr_sessions_* for the rules.
+// match, commit), punctuate and the snapshot; restore, export as records and take (K17).
+// include/otr.h otr_sessions_* for the rules.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -45,6 +46,7 @@ enum SesBuf {
   B_S_LAT, B_S_LON, B_S_ACC,
   B_R_KEY, B_R_TRIG, B_R_N, B_R_SU, B_R_STATUS, B_R_TRIM, B_R_OFF, B_R_ID, B_R_NEXT, B_R_T0, B_R_T1, B_R_LEN,
   B_R_QUEUE,
+  B_RS_KEY, B_RS_OFF, B_RS_SEP, B_RS_LAST, B_RS_BYTES, B_RS_BAD, B_X_LEN, B_X_OFF, B_X_BYTES,
   B_NUM
 };
 const char* const kBufName[B_NUM] = {
@@ -57,7 +59,9 @@ const char* const kBufName[B_NUM] = {
     "sorted list key", "sorted list session", "eviction report flag", "eviction report rank", "list size",
     "snapshot lat", "snapshot lon", "snapshot accuracy", "result key", "result trigger", "result size",
     "result shape_used", "result status", "result trimmed", "result report offsets", "result id", "result next id",
-    "result t0", "result t1", "result length", "result queue length"};
+    "result t0", "result t1", "result length", "result queue length", "restore key", "restore offsets",
+    "restore max_sep", "restore last_update", "restore bytes", "restore refusal", "record lengths", "record offsets",
+    "record bytes"};
 
 }  // namespace
 
@@ -100,6 +104,9 @@ struct SessionStore {
   std::vector<int64_t> s_off, s_last, s_time, all_last;
   std::vector<float> s_sep, s_lat, s_lon, all_sep;
   std::vector<int32_t> s_acc, s_slot;
+  // exported records
+  std::vector<int64_t> x_off;
+  std::vector<uint8_t> x_bytes;
 
   int32_t live() const { return cfg.max_sessions - h_cnt[SES_NFREE]; }
 
@@ -146,6 +153,10 @@ struct SessionStore {
   int result_end(otr_session_result* out, bool with_device, std::string* err);
   void fill_batch(otr_trace_batch* bt);
   int list_sessions(int stale_only, int64_t ts, std::string* err);
+  int list_flagged(std::string* err);
+  int snapshot_list(otr_session_snapshot* out, std::string* err);
+  template <bool REC>
+  int restore(SesGiven g, int memory, otr_session_restore_result* out, std::string* err);
   int release_list(const int32_t* list, int32_t n, std::string* err);
 };
 
@@ -567,11 +578,18 @@ bool sessions_last_reports(SessionStore* s, SessionReports* out) {
 // sessions (all live ones, or the stale ones at ts) in ascending key order: n_list of them
 // in B_L_KEY2 / B_L_SLOT2
 int SessionStore::list_sessions(int stale_only, int64_t ts, std::string* err) {
-  int rc;
   const int32_t ms = cfg.max_sessions;
   int32_t* flag = buf<int32_t>(B_FLAG, ms);
-  int32_t* incl = buf<int32_t>(B_FLAG_INCL, ms);
   k_ses_flag<<<ses_grid(ms, 256), 256, 0, stream>>>(st, stale_only, ts, cfg.session_gap, flag);
+  return list_flagged(err);
+}
+
+// the sessions flagged in B_FLAG, in ascending key order
+int SessionStore::list_flagged(std::string* err) {
+  int rc;
+  const int32_t ms = cfg.max_sessions;
+  int32_t* flag = (int32_t*)b[B_FLAG].p;
+  int32_t* incl = buf<int32_t>(B_FLAG_INCL, ms);
   if ((rc = scan32(flag, incl, ms, err))) return rc;
   HIPCHK(hipMemcpyAsync(&n_list, incl + (ms - 1), 4, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
@@ -586,6 +604,136 @@ int SessionStore::list_sessions(int stale_only, int64_t ts, std::string* err) {
   void* tmp = buf<char>(B_TMP, tb);
   HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key2, slot, slot2, n_list, 0, 64, stream));
   HIPCHK(hipGetLastError());
+  return OTR_OK;
+}
+
+// the sessions listed in B_L_KEY2 / B_L_SLOT2 as a snapshot in the store's host arrays
+int SessionStore::snapshot_list(otr_session_snapshot* out, std::string* err) {
+  int rc;
+  memset(out, 0, sizeof(*out));
+  const int32_t ns = n_list;
+  s_off.assign((size_t)ns + 1, 0);
+  out->point_off = s_off.data();
+  if (ns == 0) return OTR_OK;
+  const int32_t* list = (const int32_t*)b[B_L_SLOT2].p;
+  int32_t* rep = buf<int32_t>(B_L_REP, ns);
+  int64_t* cnt_n = buf<int64_t>(B_L_N, ns);
+  // (B_SUB_OFF, not the batch's offsets: an advance's empty batch stays what it is)
+  int64_t* off = buf<int64_t>(B_SUB_OFF, (size_t)ns + 1);
+  k_ses_evict_gate<<<ses_grid(ns, 256), 256, 0, stream>>>(ns, list, st, rep, cnt_n);
+  HIPCHK(hipMemsetAsync(off, 0, 8, stream));
+  if ((rc = scan64(cnt_n, off + 1, ns, err))) return rc;
+  const size_t ms = (size_t)cfg.max_sessions;
+  s_key.resize(ns);
+  s_slot.resize(ns);
+  all_sep.resize(ms);
+  all_last.resize(ms);
+  HIPCHK(hipMemcpyAsync(s_off.data(), off, 8 * ((size_t)ns + 1), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(s_key.data(), b[B_L_KEY2].p, 8 * (size_t)ns, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(s_slot.data(), list, 4 * (size_t)ns, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(all_sep.data(), st.max_sep, 4 * ms, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(all_last.data(), st.last, 8 * ms, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  const int64_t np = s_off[ns];
+  float* lat = buf<float>(B_S_LAT, np);
+  float* lon = buf<float>(B_S_LON, np);
+  int32_t* acc = buf<int32_t>(B_S_ACC, np);
+  int64_t* time = buf<int64_t>(B_G_TIME, np);
+  k_ses_gather<true><<<(unsigned)ns, 64, 0, stream>>>(ns, list, off, st, nullptr, nullptr, time, nullptr, nullptr, 0,
+                                                      lat, lon, acc);
+  HIPCHK(hipGetLastError());
+  s_lat.resize(np);
+  s_lon.resize(np);
+  s_acc.resize(np);
+  s_time.resize(np);
+  HIPCHK(hipMemcpyAsync(s_lat.data(), lat, 4 * (size_t)np, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(s_lon.data(), lon, 4 * (size_t)np, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(s_acc.data(), acc, 4 * (size_t)np, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(s_time.data(), time, 8 * (size_t)np, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  s_sep.resize(ns);
+  s_last.resize(ns);
+  for (int32_t i = 0; i < ns; ++i) {
+    s_sep[i] = all_sep[s_slot[i]];
+    s_last[i] = all_last[s_slot[i]];
+  }
+  out->n_sessions = ns;
+  out->n_points = np;
+  out->key = (uint64_t*)s_key.data();
+  out->max_sep = s_sep.data();
+  out->last_update = s_last.data();
+  out->lat = s_lat.data();
+  out->lon = s_lon.data();
+  out->accuracy = s_acc.data();
+  out->time = s_time.data();
+  return OTR_OK;
+}
+
+// K17: the given sessions (device arrays) merged into the store, all or nothing
+template <bool REC>
+int SessionStore::restore(SesGiven g, int memory, otr_session_restore_result* out, std::string* err) {
+  int rc;
+  const int64_t n = g.n;
+  out->n_live = live();
+  if (n == 0) return OTR_OK;
+  if (h_cnt[SES_DEAD] > 0 && live() + h_cnt[SES_DEAD] > cfg.max_sessions && (rc = rebuild(err))) return rc;
+  int32_t* entry = buf<int32_t>(B_ENTRY, n);
+  int32_t* fresh = buf<int32_t>(B_NEW, n);
+  unsigned long long* bad = buf<unsigned long long>(B_RS_BAD, 1);
+  int32_t* first = spare.slot;  // scratch: the spare table is only used inside a rebuild
+  HIPCHK(hipMemsetAsync(first, 0x7F, 4 * (size_t)spare.cap, stream));
+  HIPCHK(hipMemsetAsync(bad, 0xFF, 8, stream));
+  HIPCHK(hipMemsetAsync(cnt + SES_FLAGS, 0, 4, stream));
+  const unsigned grid = ses_grid(n, 256);
+  k_ses_restore_check<REC><<<grid, 256, 0, stream>>>(tab, g, cfg.max_points, first, entry, fresh, bad, cnt);
+  HIPCHK(hipGetLastError());
+  unsigned long long h_bad = kSesNoBad;
+  int32_t flags = 0;
+  HIPCHK(hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(&flags, cnt + SES_FLAGS, 4, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (flags) {
+    // more keys than the table has room for (a refusal either way): lanes that found no entry
+    // could not see each other, so the occurrences of a key are counted here
+    std::vector<unsigned long long> keys((size_t)n);
+    HIPCHK(hipMemcpyAsync(keys.data(), g.key, 8 * (size_t)n, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    std::vector<std::pair<unsigned long long, int64_t>> order((size_t)n);
+    for (int64_t i = 0; i < n; ++i) order[i] = {keys[i], i};
+    std::sort(order.begin(), order.end());
+    for (int64_t i = 1; i < n; ++i)
+      if (order[i].first == order[i - 1].first)
+        h_bad = std::min(h_bad, ((unsigned long long)order[i].second << 8) | OTR_RESTORE_E_DUPLICATE);
+  }
+  const bool full = n > (int64_t)h_cnt[SES_NFREE];
+  if (h_bad != kSesNoBad || full || flags) {
+    k_ses_rollback<<<grid, 256, 0, stream>>>(tab, n, entry, fresh);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    static const char* const why[] = {"",
+                                      "layout",
+                                      "key OTR_NO_ID is the store's empty mark",
+                                      "count outside 1 .. max_points - 1",
+                                      "duplicate key",
+                                      "the key has a live session"};
+    if (h_bad != kSesNoBad) {
+      out->bad_session = (int64_t)(h_bad >> 8);
+      out->bad_reason = (int32_t)(h_bad & 0xFF);
+      if (err) *err = "session " + std::to_string(out->bad_session) + ": " + why[out->bad_reason];
+    } else {
+      out->bad_reason = OTR_RESTORE_E_FULL;
+      if (err)
+        *err = "the restore would take the live sessions beyond max_sessions (" + std::to_string(live()) + " live, " +
+               std::to_string(n) + " given, " + std::to_string(cfg.max_sessions) + " at most)";
+    }
+    return OTR_BAD_REQUEST;
+  }
+  k_ses_restore_copy<REC><<<(unsigned)n, 64, 0, stream>>>(tab, st, g, entry, free_list, h_cnt[SES_NFREE]);
+  k_ses_add<<<1, 1, 0, stream>>>(cnt + SES_NFREE, -(int32_t)n);
+  HIPCHK(hipGetLastError());
+  h_cnt[SES_NFREE] -= (int32_t)n;
+  out->n_sessions = n;
+  out->n_live = live();
   return OTR_OK;
 }
 
@@ -773,63 +921,198 @@ int Matcher::sessions_snapshot(otr_session_snapshot* out, std::string* err) {
     int rc;
     HIPCHK(hipSetDevice(graph_state().device));
     if (s.pending) return bad(err, "the last advance has not been committed");
+    if ((rc = s.list_sessions(0, 0, err))) return rc;
+    return s.snapshot_list(out, err);
+  });
+}
+
+// ---- K17: restore, export and move ------------------------------------------------------------
+
+namespace {
+
+void restore_result_begin(otr_session_restore_result* out) {
+  memset(out, 0, sizeof(*out));
+  out->bad_session = -1;
+}
+
+}  // namespace
+
+int Matcher::sessions_restore(const otr_session_snapshot* snap, int memory, otr_session_restore_result* out,
+                              std::string* err) {
+  restore_result_begin(out);
+  return guarded(*this, err, true, [&]() -> int {
+    SessionStore& s = *ses;
+    int rc;
+    HIPCHK(hipSetDevice(graph_state().device));
+    out->n_live = s.live();
+    if (s.pending || s.chunk_open) return bad(err, "an advance / commit sequence is open");
+    const int64_t n = snap->n_sessions, np = snap->n_points;
+    if (n < 0 || np < 0 || n > (int64_t)1 << 30 || np > (int64_t)1 << 40)
+      return bad(err, "too many sessions for one restore (2^30 at most)");
+    if (n == 0) {
+      if (np == 0) return OTR_OK;
+      out->bad_reason = OTR_RESTORE_E_LAYOUT;
+      return bad(err, "layout: points without sessions");
+    }
+    if (!snap->key || !snap->point_off || !snap->max_sep || !snap->last_update ||
+        (np > 0 && (!snap->lat || !snap->lon || !snap->accuracy || !snap->time)))
+      return bad(err, "null argument");
+    SesGiven g{};
+    g.n = n;
+    g.total = np;
+    HIPCHK(hipEventRecord(s.ev[0], stream));
+    if (memory == OTR_MEM_DEVICE) {
+      g.key = (const unsigned long long*)snap->key;
+      g.off = snap->point_off;
+      g.max_sep = snap->max_sep;
+      g.last = snap->last_update;
+      g.lat = snap->lat;
+      g.lon = snap->lon;
+      g.acc = snap->accuracy;
+      g.time = snap->time;
+    } else {
+      unsigned long long* key = s.buf<unsigned long long>(B_RS_KEY, n);
+      int64_t* off = s.buf<int64_t>(B_RS_OFF, (size_t)n + 1);
+      float* sep = s.buf<float>(B_RS_SEP, n);
+      int64_t* last = s.buf<int64_t>(B_RS_LAST, n);
+      float* lat = s.buf<float>(B_LAT, np);
+      float* lon = s.buf<float>(B_LON, np);
+      int32_t* acc = s.buf<int32_t>(B_ACC, np);
+      int64_t* time = s.buf<int64_t>(B_TIME, np);
+      HIPCHK(hipMemcpyAsync(key, snap->key, 8 * (size_t)n, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(off, snap->point_off, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(sep, snap->max_sep, 4 * (size_t)n, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(last, snap->last_update, 8 * (size_t)n, hipMemcpyHostToDevice, stream));
+      if (np > 0) {
+        HIPCHK(hipMemcpyAsync(lat, snap->lat, 4 * (size_t)np, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(lon, snap->lon, 4 * (size_t)np, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(acc, snap->accuracy, 4 * (size_t)np, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(time, snap->time, 8 * (size_t)np, hipMemcpyHostToDevice, stream));
+      }
+      g.key = key;
+      g.off = off;
+      g.max_sep = sep;
+      g.last = last;
+      g.lat = lat;
+      g.lon = lon;
+      g.acc = acc;
+      g.time = time;
+    }
+    if ((rc = s.restore<false>(g, memory, out, err))) return rc;
+    out->n_points = np;
+    HIPCHK(hipEventRecord(s.ev[1], stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipEventElapsedTime(&out->device_ms, s.ev[0], s.ev[1]));
+    return OTR_OK;
+  });
+}
+
+int Matcher::sessions_restore_records(const otr_session_records* recs, otr_session_restore_result* out,
+                                      std::string* err) {
+  restore_result_begin(out);
+  return guarded(*this, err, true, [&]() -> int {
+    SessionStore& s = *ses;
+    int rc;
+    HIPCHK(hipSetDevice(graph_state().device));
+    out->n_live = s.live();
+    if (s.pending || s.chunk_open) return bad(err, "an advance / commit sequence is open");
+    const int64_t n = recs->n_records, nb = recs->n_bytes;
+    if (n < 0 || nb < 0 || n > (int64_t)1 << 30 || nb > (int64_t)1 << 44)
+      return bad(err, "too many sessions for one restore (2^30 at most)");
+    if (n == 0) return OTR_OK;
+    if (!recs->key || !recs->rec_off || (nb > 0 && !recs->bytes)) return bad(err, "null argument");
+    SesGiven g{};
+    g.n = n;
+    g.total = nb;
+    HIPCHK(hipEventRecord(s.ev[0], stream));
+    if (recs->memory == OTR_MEM_DEVICE) {
+      g.key = (const unsigned long long*)recs->key;
+      g.off = recs->rec_off;
+      g.bytes = recs->bytes;
+    } else {
+      unsigned long long* key = s.buf<unsigned long long>(B_RS_KEY, n);
+      int64_t* off = s.buf<int64_t>(B_RS_OFF, (size_t)n + 1);
+      uint8_t* bytes = s.buf<uint8_t>(B_RS_BYTES, nb);
+      HIPCHK(hipMemcpyAsync(key, recs->key, 8 * (size_t)n, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(off, recs->rec_off, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, stream));
+      if (nb > 0) HIPCHK(hipMemcpyAsync(bytes, recs->bytes, (size_t)nb, hipMemcpyHostToDevice, stream));
+      g.key = key;
+      g.off = off;
+      g.bytes = bytes;
+    }
+    if ((rc = s.restore<true>(g, recs->memory, out, err))) return rc;
+    int64_t ends[2] = {0, 0};  // every record was as long as its count says
+    HIPCHK(hipMemcpyAsync(&ends[0], g.off, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&ends[1], g.off + n, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipEventRecord(s.ev[1], stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipEventElapsedTime(&out->device_ms, s.ev[0], s.ev[1]));
+    out->n_points = (ends[1] - ends[0] - kRecHeader * n) / kRecPoint;
+    return OTR_OK;
+  });
+}
+
+int Matcher::sessions_export_records(otr_session_records* out, std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    SessionStore& s = *ses;
+    int rc;
+    HIPCHK(hipSetDevice(graph_state().device));
+    if (s.pending) return bad(err, "the last advance has not been committed");
     memset(out, 0, sizeof(*out));
+    out->memory = OTR_MEM_HOST;
     if ((rc = s.list_sessions(0, 0, err))) return rc;
     const int32_t ns = s.n_list;
-    s.s_off.assign((size_t)ns + 1, 0);
-    out->point_off = s.s_off.data();
-    if (ns == 0) return OTR_OK;
-    const int32_t* list = (const int32_t*)s.b[B_L_SLOT2].p;
-    int32_t* rep = s.buf<int32_t>(B_L_REP, ns);
-    int64_t* cnt_n = s.buf<int64_t>(B_L_N, ns);
-    // (B_SUB_OFF, not the batch's offsets: an advance's empty batch stays what it is)
-    int64_t* off = s.buf<int64_t>(B_SUB_OFF, (size_t)ns + 1);
-    k_ses_evict_gate<<<ses_grid(ns, 256), 256, 0, stream>>>(ns, list, s.st, rep, cnt_n);
+    s.x_off.assign((size_t)ns + 1, 0);
+    int64_t* off = s.buf<int64_t>(B_X_OFF, (size_t)ns + 1);
     HIPCHK(hipMemsetAsync(off, 0, 8, stream));
-    if ((rc = s.scan64(cnt_n, off + 1, ns, err))) return rc;
-    const size_t ms = (size_t)s.cfg.max_sessions;
-    s.s_key.resize(ns);
-    s.s_slot.resize(ns);
-    s.all_sep.resize(ms);
-    s.all_last.resize(ms);
-    HIPCHK(hipMemcpyAsync(s.s_off.data(), off, 8 * ((size_t)ns + 1), hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(s.s_key.data(), s.b[B_L_KEY2].p, 8 * (size_t)ns, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(s.s_slot.data(), list, 4 * (size_t)ns, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(s.all_sep.data(), s.st.max_sep, 4 * ms, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(s.all_last.data(), s.st.last, 8 * ms, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    const int64_t np = s.s_off[ns];
-    float* lat = s.buf<float>(B_S_LAT, np);
-    float* lon = s.buf<float>(B_S_LON, np);
-    int32_t* acc = s.buf<int32_t>(B_S_ACC, np);
-    int64_t* time = s.buf<int64_t>(B_G_TIME, np);
-    k_ses_gather<true><<<(unsigned)ns, 64, 0, stream>>>(ns, list, off, s.st, nullptr, nullptr, time, nullptr, nullptr,
-                                                        0, lat, lon, acc);
-    HIPCHK(hipGetLastError());
-    s.s_lat.resize(np);
-    s.s_lon.resize(np);
-    s.s_acc.resize(np);
-    s.s_time.resize(np);
-    HIPCHK(hipMemcpyAsync(s.s_lat.data(), lat, 4 * (size_t)np, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(s.s_lon.data(), lon, 4 * (size_t)np, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(s.s_acc.data(), acc, 4 * (size_t)np, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(s.s_time.data(), time, 8 * (size_t)np, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    s.s_sep.resize(ns);
-    s.s_last.resize(ns);
-    for (int32_t i = 0; i < ns; ++i) {
-      s.s_sep[i] = s.all_sep[s.s_slot[i]];
-      s.s_last[i] = s.all_last[s.s_slot[i]];
+    out->rec_off = s.x_off.data();
+    out->d_rec_off = off;
+    if (ns == 0) {
+      HIPCHK(hipStreamSynchronize(stream));
+      return OTR_OK;
     }
-    out->n_sessions = ns;
-    out->n_points = np;
-    out->key = (uint64_t*)s.s_key.data();
-    out->max_sep = s.s_sep.data();
-    out->last_update = s.s_last.data();
-    out->lat = s.s_lat.data();
-    out->lon = s.s_lon.data();
-    out->accuracy = s.s_acc.data();
-    out->time = s.s_time.data();
+    const int32_t* list = (const int32_t*)s.b[B_L_SLOT2].p;
+    int64_t* len = s.buf<int64_t>(B_X_LEN, ns);
+    k_ses_record_len<<<ses_grid(ns, 256), 256, 0, stream>>>(ns, list, s.st, len);
+    if ((rc = s.scan64(len, off + 1, ns, err))) return rc;
+    s.s_key.resize(ns);
+    HIPCHK(hipMemcpyAsync(s.x_off.data(), off, 8 * ((size_t)ns + 1), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(s.s_key.data(), s.b[B_L_KEY2].p, 8 * (size_t)ns, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    const int64_t nb = s.x_off[ns];
+    uint8_t* bytes = s.buf<uint8_t>(B_X_BYTES, nb);
+    k_ses_encode<<<(unsigned)ns, 64, 0, stream>>>(ns, list, off, s.st, bytes);
+    HIPCHK(hipGetLastError());
+    s.x_bytes.resize((size_t)nb);
+    HIPCHK(hipMemcpyAsync(s.x_bytes.data(), bytes, (size_t)nb, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    out->n_records = ns;
+    out->n_bytes = nb;
+    out->key = (const uint64_t*)s.s_key.data();
+    out->bytes = s.x_bytes.data();
+    out->d_key = (const uint64_t*)s.b[B_L_KEY2].p;
+    out->d_bytes = bytes;
+    return OTR_OK;
+  });
+}
+
+int Matcher::sessions_take(int n_parts, int part, int remove, otr_session_snapshot* out, std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    SessionStore& s = *ses;
+    int rc;
+    HIPCHK(hipSetDevice(graph_state().device));
+    if (s.pending || s.chunk_open) return bad(err, "an advance / commit sequence is open");
+    if (n_parts < 1 || part < 0 || part >= n_parts) return bad(err, "part out of range");
+    const int32_t ms = s.cfg.max_sessions;
+    int32_t* flag = s.buf<int32_t>(B_FLAG, ms);
+    k_ses_flag_part<<<ses_grid(ms, 256), 256, 0, stream>>>(s.st, (uint32_t)n_parts, (uint32_t)part, flag);
+    if ((rc = s.list_flagged(err))) return rc;
+    if ((rc = s.snapshot_list(out, err))) return rc;
+    if (remove && s.n_list > 0) {  // deleted as an eviction deletes, without a report
+      const int32_t* list = (const int32_t*)s.b[B_L_SLOT2].p;
+      k_ses_clear<<<ses_grid(s.n_list, 256), 256, 0, stream>>>(s.n_list, list, s.st);
+      if ((rc = s.release_list(list, s.n_list, err))) return rc;
+    }
     return OTR_OK;
   });
 }

@@ -73,6 +73,13 @@ def graph_info():
     return a.value, b.value, c.value
 
 
+def session_key(uuid_bytes):
+    """otr_uuid_key: the session store's key of a uuid (K11's 64-bit hash of its bytes; a str
+    is taken as UTF-8, as the changelog's String keys are)."""
+    b = uuid_bytes.encode() if isinstance(uuid_bytes, str) else bytes(uuid_bytes)
+    return int(_lib.lib().otr_uuid_key(b, len(b)))
+
+
 JAVA_TIME_PATTERN = 'yyyy-MM-dd HH:mm:ss'
 
 
@@ -495,6 +502,76 @@ class Matcher:
         accuracy, time (numpy copies)."""
         r = _lib.SessionSnapshot()
         self._check(self._L.otr_sessions_snapshot(self._h, ctypes.byref(r)), 'otr_sessions_snapshot')
+        return _lib.snapshot_to_numpy(r)
+
+    # --- restore, export and move (include/otr.h otr_sessions_restore ..., DESIGN.md §3 item 16) --
+    def _restore_check(self, rc, r, what):
+        if rc == _lib.OTR_BAD_REQUEST and r.bad_reason:
+            where = 'session %d: ' % r.bad_session if r.bad_session >= 0 else ''
+            raise ValueError('%s refused: %s%s (%s)' % (what, where, _lib.RESTORE_REASONS.get(r.bad_reason, r.bad_reason),
+                                                       _lib.last_error()))
+        self._check(rc, what)
+        return {k: getattr(r, k) for k in ('n_sessions', 'n_points', 'n_live', 'device_ms')}
+
+    def sessions_restore(self, snapshot, device=False):
+        """otr_sessions_restore: the sessions of a snapshot dict (sessions_snapshot's layout)
+        merged into the open store, all or nothing.  device=True: the dict holds device
+        pointers plus 'n_sessions' and 'n_points'.  A refusal raises ValueError carrying the
+        lowest refused index and the reason (_lib.RESTORE_REASONS)."""
+        s, r = _lib.SessionSnapshot(), _lib.SessionRestoreResult()
+        if device:
+            s.n_sessions, s.n_points = int(snapshot['n_sessions']), int(snapshot['n_points'])
+            for k, ct, _ in _lib.SNAPSHOT_FIELDS:
+                setattr(s, k, ctypes.cast(ctypes.c_void_p(int(snapshot[k]) or None), P(ct)))
+        else:
+            keep = [np.ascontiguousarray(snapshot[k], dt) for k, _, dt in _lib.SNAPSHOT_FIELDS]
+            per_session = {k: a for (k, _, _), a in zip(_lib.SNAPSHOT_FIELDS, keep)}
+            ns, npt = len(per_session['key']), len(per_session['time'])
+            if len(per_session['point_off']) != ns + 1 or any(len(per_session[k]) != ns for k in ('max_sep', 'last_update')) \
+                    or any(len(per_session[k]) != npt for k in ('lat', 'lon', 'accuracy')):
+                raise ValueError('session snapshot: arrays of different lengths')
+            self._keep = keep
+            s.n_sessions, s.n_points = ns, npt
+            for (k, ct, _), a in zip(_lib.SNAPSHOT_FIELDS, keep):
+                setattr(s, k, ctypes.cast(ctypes.c_void_p(a.ctypes.data), P(ct)))
+        rc = self._L.otr_sessions_restore(self._h, ctypes.byref(s), _lib.OTR_MEM_DEVICE if device else _lib.OTR_MEM_HOST,
+                                          ctypes.byref(r))
+        return self._restore_check(rc, r, 'otr_sessions_restore')
+
+    def sessions_restore_records(self, key, rec_off, data, device=False, n_records=None, n_bytes=None):
+        """otr_sessions_restore_records: sessions as Batch.Serder's value bytes.  key: uint64 per
+        record (session_key of the changelog key), rec_off: n + 1 byte offsets, data: the bytes
+        (bytes or uint8 array).  device=True: the three are device addresses, with n_records and
+        n_bytes; the bytes may start at any address."""
+        c, r = _lib.SessionRecords(), _lib.SessionRestoreResult()
+        if device:
+            c.n_records, c.n_bytes, c.memory = int(n_records), int(n_bytes), _lib.OTR_MEM_DEVICE
+            c.key, c.rec_off, c.bytes = int(key) or None, int(rec_off) or None, int(data) or None
+        else:
+            k = np.ascontiguousarray(key, np.uint64)
+            o = np.ascontiguousarray(rec_off, np.int64)
+            d = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
+            if len(o) != len(k) + 1:
+                raise ValueError('session records: rec_off needs n_records + 1 offsets')
+            self._keep = [k, o, d]
+            c.n_records, c.n_bytes, c.memory = len(k), len(d), _lib.OTR_MEM_HOST
+            c.key, c.rec_off, c.bytes = k.ctypes.data, o.ctypes.data, (d.ctypes.data if len(d) else None)
+        rc = self._L.otr_sessions_restore_records(self._h, ctypes.byref(c), ctypes.byref(r))
+        return self._restore_check(rc, r, 'otr_sessions_restore_records')
+
+    def sessions_export_records(self):
+        """otr_sessions_export_records: every live session in ascending key order as records:
+        numpy copies of key, rec_off and bytes, and 'device' with the same arrays in HBM."""
+        r = _lib.SessionRecords()
+        self._check(self._L.otr_sessions_export_records(self._h, ctypes.byref(r)), 'otr_sessions_export_records')
+        return _lib.records_to_numpy(r)
+
+    def sessions_take(self, n_parts, part, remove=True):
+        """otr_sessions_take: the sessions with key % n_parts == part as a snapshot dict;
+        remove=True also deletes them from the store (no report is made)."""
+        r = _lib.SessionSnapshot()
+        self._check(self._L.otr_sessions_take(self._h, int(n_parts), int(part), 1 if remove else 0, ctypes.byref(r)),
+                    'otr_sessions_take')
         return _lib.snapshot_to_numpy(r)
 
     # --- tile store (include/otr.h otr_tile_store_*, DESIGN.md §3 item 14) -----------------

@@ -373,6 +373,25 @@ def stream_text_tiles(matcher, chunks, fmt, end_ts, mode='auto', source='reporte
     return {'payloads': stream_tile_payloads(flush, mode, source), 'flush': flush, 'counts': counts}
 
 
+def save_sessions(matcher, path):
+    """The open session store's state as one .npz of (key, rec_off, bytes): every live session as
+    the value Batch.Serder writes for it (Matcher.sessions_export_records).  With load_sessions
+    this lets stream_text_tiles go on after a restart where the saved process stopped between two
+    chunks.  Returns the number of sessions saved."""
+    r = matcher.sessions_export_records()
+    with open(path, 'wb') as f:
+        np.savez(f, key=r['key'], rec_off=r['rec_off'], bytes=r['bytes'])
+    return len(r['key'])
+
+
+def load_sessions(matcher, path):
+    """The sessions of a save_sessions file merged into the matcher's open store
+    (Matcher.sessions_restore_records: all or nothing, ValueError when refused).  Returns the
+    restore's counts."""
+    with np.load(path) as z:
+        return matcher.sessions_restore_records(z['key'], z['rec_off'], z['bytes'])
+
+
 def _exchange_by_file_owner(buf, itemsize, world, group=None):
     """All-to-all of fixed-size records whose first 8 bytes are their (hour, tile) file:
     each record goes to file_owner(file); returns the records this rank received (uint8

@@ -25,7 +25,17 @@ otr_ingest(OTR_INGEST_JAVA_SV) on the same text.  `--graph city` replays the sma
 
     python -m reporter_amd.tools.sessions_rate --traces 2000 --out profiles/sessions_c2dep.json
     python -m reporter_amd.tools.sessions_rate --traces 2000 --text json --out profiles/formatter_c2dep_json.json
+
+`--restore` replays the stream in 10 s chunks to its midpoint and times, on the store as it stands
+there (one warm-up, `--repeats` timed; median [min, max] of the wall time and of the device time:
+the call's own device_ms, or HIP events on the matcher's stream around the call): the snapshot,
+the export as records, take-all with remove, the restore from the snapshot's arrays and the
+restore from the records; beside them the store's sessions, points and record bytes and one plain
+device-to-device copy of as many bytes.  With OTR_LIB naming a library built before these calls
+existed it times the snapshot alone (the comparand in profiles/sessions_restore_c2dep.json).
+
     python -m reporter_amd.tools.sessions_rate --traces 2000 --tile-store --out profiles/tile_store_c2dep.json
+    python -m reporter_amd.tools.sessions_rate --traces 2000 --restore --out profiles/sessions_restore_c2dep.json
 """
 import argparse
 import json
@@ -143,6 +153,69 @@ def replay(m, pts, cuts, max_points, batch_ms, tile_rows=0, text=None):
             'evicted': ev['n_evicted'], 'eviction_windows': ev['n_windows'], 'chunks': len(chunks)}
 
 
+def restore_rates(m, pts, max_points, repeats):
+    """The store at the stream's midpoint (10 s chunks): snapshot, export, take-all, restore from
+    the SoA and from records, each timed `repeats` times after a warm-up."""
+    import torch
+    n = len(pts['key'])
+    sec = (pts['time'] - pts['time'][0]) // 10
+    cuts = [0] + (np.flatnonzero(np.diff(sec)) + 1).tolist() + [n]
+    cuts = [c for c in cuts if c <= n // 2]
+    m.sessions_open(int(pts['key'].max()) + 1, max_points)
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        m.sessions_push({k: v[a:b] for k, v in pts.items()})
+    stream = torch.cuda.ExternalStream(m.stream)
+    times = {}
+
+    def timed(name, f, *a, **kw):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        t0 = time.perf_counter()
+        r = f(*a, **kw)
+        wall = 1e3 * (time.perf_counter() - t0)
+        e1.record(stream)
+        e1.synchronize()
+        dev = r['device_ms'] if isinstance(r, dict) and 'device_ms' in r else e0.elapsed_time(e1)
+        times.setdefault(name, []).append((wall, float(dev)))
+        return r
+
+    from reporter_amd import _lib
+    has_restore = hasattr(_lib.lib(), 'otr_sessions_restore')   # (a library from before K17: the snapshot alone)
+    for _ in range(repeats + 1):
+        snap = timed('snapshot', m.sessions_snapshot)
+        if not has_restore:
+            continue
+        rec = timed('export_records', m.sessions_export_records)
+        taken = timed('take_all', m.sessions_take, 1, 0)
+        timed('restore', m.sessions_restore, taken)
+        m.sessions_take(1, 0)
+        timed('restore_records', m.sessions_restore_records, rec['key'], rec['rec_off'], rec['bytes'])
+    out = {'points_pushed': cuts[-1], 'sessions': len(snap['key']), 'points': len(snap['time'])}
+    if has_restore:
+        nb = len(rec['bytes'])
+        out['record_bytes'] = nb
+        src = torch.zeros(max(nb, 1), dtype=torch.uint8, device='cuda')
+        dst = torch.empty_like(src)
+        cp = []
+        for _ in range(repeats + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            dst.copy_(src)
+            e1.record()
+            e1.synchronize()
+            cp.append(e0.elapsed_time(e1))
+        cp = sorted(cp[1:])
+        out['device_copy_ms_median_min_max'] = [round(float(np.median(cp)), 4), round(cp[0], 4), round(cp[-1], 4)]
+        after = m.sessions_snapshot()
+        assert all(np.array_equal(after[k], snap[k]) for k in snap), 'the store changed over the repeats'
+    for name, v in times.items():
+        wall, dev = sorted(x[0] for x in v[1:]), sorted(x[1] for x in v[1:])
+        out[name] = {'wall_ms_median_min_max': [round(float(np.median(wall)), 4), round(wall[0], 4), round(wall[-1], 4)],
+                     'device_ms_median_min_max': [round(float(np.median(dev)), 4), round(dev[0], 4), round(dev[-1], 4)]}
+    m.sessions_close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--traces', type=int, default=2000, help='traces of the c2dep workload (bench.py --json-traces)')
@@ -155,6 +228,8 @@ def main():
     ap.add_argument('--tile-rows', type=int, default=1 << 22, help='max_rows of that store')
     ap.add_argument('--text', choices=['sv', 'json'], default=None,
                     help='render the stream as messages and push them through otr_sessions_push_text')
+    ap.add_argument('--restore', action='store_true',
+                    help='time snapshot, export, take-all and the two restores on the store at the midpoint')
     ap.add_argument('--graph', choices=['metro', 'city'], default='metro')
     ap.add_argument('--format-traces', type=int, default=0,
                     help='with --text: traces of the stream formatted alone (default: --traces)')
@@ -179,6 +254,18 @@ def main():
         m.match_batch(one, copy_out=False, copy_reports=True)
         tb.append(1e3 * (time.perf_counter() - t0))
     batch_ms = float(np.median(tb))
+    if args.restore:
+        res = {'workload': 'c2dep: %s graph, %d traces x 100 probes @15 s, sigma 10 m, deployed configuration, '
+                           '10 s chunks to the midpoint' % (args.graph, args.traces),
+               'method': '1 warm-up, %d timed; median [min, max]; device_ms of the call, or HIP events on the '
+                         "matcher's stream around it" % args.repeats,
+               'restore': restore_rates(m, pts, args.max_points, args.repeats)}
+        line = json.dumps(res, indent=1)
+        print(line)
+        if args.out:
+            with open(args.out, 'w') as f:
+                f.write(line + '\n')
+        return
     msgs = render(pts, args.text) if args.text else None
     res = {'workload': 'c2dep: %s graph, %d traces x 100 probes @15 s, sigma 10 m, deployed configuration' % (args.graph, args.traces),
            'probes': n, 'gates': '500 m, 10 points, 60 s; session_gap 60000; max_points %d' % args.max_points,
