@@ -3008,7 +3008,8 @@ __global__ __launch_bounds__(256) void k_histogram(HistArgs a) {
     const uint32_t seg = a.rep_seg[co + r];
     for (int64_t bk = sp.min_bucket; bk <= sp.max_bucket; ++bk) {
       ++rows;
-      const int64_t h = (bk * a.quantisation - a.base_time) / a.quantisation;
+      // floor: a bucket that starts before the base is outside [base, base + hours * q) (otr.h)
+      const int64_t h = py2_div(bk * a.quantisation - a.base_time, a.quantisation);
       if (h >= 0 && h < a.hours && seg < a.n_segments && a.hist)
         atomicAdd(&a.hist[((size_t)h * a.n_segments + seg) * OTR_HIST_BINS + bin], 1u);
     }

@@ -3,6 +3,8 @@ traces of 0 to 200 probes in one batch, forced steps and states without candidat
 places, cut from gen.make_traces output with pure numpy.  A helper module (no tests, no
 fixtures): tests/test_trace_stage_cases_cpu.py pins what the oracle makes of every case
 (coverage), tests/test_gpu_trace_stages.py runs them through the three Viterbi variants.
+many_reports, for the output stages (k_histogram, k_tile_rows, the sort + cull): traces of up to
+236 reports, pinned by tests/test_tile_stage_cases_cpu.py and run by tests/test_gpu_tile_stages.py.
 
 The boundaries the cases sit on (otr_kernels.h): k_link and k_segments walk a trace in
 chunks of 64 states / 64 active states and carry values across chunks; k_viterbi backtracks
@@ -157,6 +159,54 @@ def ragged_city(graph_dir):
     return path, tr
 
 
+# many_reports: traces with many more reports than ragged_city's (at most 51), for the stages
+# that walk a trace's reports 64 at a time (k_histogram, k_tile_rows): prefixes of six long city
+# traces (700 probes, 15 s apart), the prefix lengths found by a search on the oracle so that
+# the report counts per trace under 'gtt' are MANY_REPORTS (pinned by
+# tests/test_tile_stage_cases_cpu.py; each length sits inside the range of lengths that give its
+# count).  (source trace, probes, reports), four traces per 256-thread block of K8 / K9: an
+# empty trace and one with probes and no report beside the longest, 64 | 65 and 128 | 129 beside
+# each other, three whole chunks (192) and the last block with three traces only.
+MANY_SEED = 77
+MANY = [(0, 0, 0), (1, 692, 236), (1, 8, 0), (2, 228, 64),
+        (0, 247, 65), (0, 6, 1), (1, 375, 128), (2, 533, 129),
+        (2, 222, 63), (1, 366, 127), (4, 680, 192), (4, 688, 194),
+        (5, 657, 200), (3, 8, 2), (3, 0, 0)]
+MANY_SRC = [m[0] for m in MANY]
+MANY_LENS = [m[1] for m in MANY]
+MANY_REPORTS = [m[2] for m in MANY]
+
+
+def many_reports(graph_dir):
+    path = gen.graph_path('city', graph_dir)
+    full = gen.make_traces(path, 6, 700, 15, 10.0, MANY_SEED, t_begin=gen.T_BEGIN, t_spread=1800)
+    return path, prefixes(full.subset(MANY_SRC), MANY_LENS)
+
+
+# The dense histogram's windows for tests/test_gpu_tile_stages.py, per (batch, quantisation):
+# (name, base - T_BEGIN, buckets).  aligned: the base every caller passes; inside: an aligned
+# base after the first reports with an end before the last ones, so rows fall outside on both
+# sides (ragged_city ends within its first hour: no such window at 3600); unaligned: a base
+# that is no multiple of the quantisation, where the bucket that starts less than one bucket
+# before the base has the floor index -1 (left out: include/otr.h "covers [base, ...)") and
+# the truncated index 0.  One bucket is n_segments x 8 counters (1.7 MB for the city graph).
+HIST_WINDOWS = {
+    ('ragged_city', 3600): [('aligned', 0, 3), ('unaligned', 1800, 2)],
+    ('ragged_city', 60): [('aligned', 0, 20), ('inside', 1200, 20), ('unaligned', 630, 20)],
+    ('many_reports', 3600): [('aligned', 0, 4), ('inside', 3600, 1), ('unaligned', 1800, 2)],
+    ('many_reports', 60): [('aligned', 0, 20), ('inside', 3600, 20), ('unaligned', 630, 20),
+                             ('unaligned_busy', 3630, 20)],
+}
+
+
+def trace_times(tr):
+    """(first, last) probe time of every trace, 0 for a trace without probes."""
+    n = np.diff(tr.offsets)
+    first = np.where(n > 0, tr.time[np.minimum(tr.offsets[:-1], len(tr.time) - 1)], 0)
+    last = np.where(n > 0, tr.time[np.maximum(tr.offsets[1:] - 1, 0)], 0)
+    return first, last
+
+
 def tiny_T(graph_dir, T):
     """ragged_city's 129-, 104- and 1-probe traces, the first T of them."""
     assert 1 <= T <= 3
@@ -194,6 +244,10 @@ CASES = {
     'wide_K': (wide_K, ('wide',)),
 }
 
+# batches of other test files (tests/test_gpu_tile_stages.py), kept out of CASES so that
+# tests/test_gpu_trace_stages.py keeps its jobs; oracle_result() knows them too
+OTHER_BATCHES = {'many_reports': many_reports}
+
 # the two fixed permutations of ragged_city for the neighbour test: the reversal, and a
 # shuffle that moves every trace to the other half of a wave or to another partner
 PERMS = {
@@ -212,7 +266,8 @@ def oracle_result(case, cfg, graph_dir):
     from oracle import pyoracle as po
     key = (case, cfg)
     if key not in _ORACLE:
-        path, tr = CASES[case][0](graph_dir)
+        build = CASES[case][0] if case in CASES else OTHER_BATCHES[case]
+        path, tr = build(graph_dir)
         t0 = time.perf_counter()
         want = po.match_batch(po.Graph(path), tr, oracle_params(cfg), threads=8)
         _ORACLE[key] = (path, tr, want, time.perf_counter() - t0)

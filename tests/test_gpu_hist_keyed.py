@@ -1,7 +1,10 @@
 """Keyed speed histogram on the GPU (otr_hist_reduce) vs the CPU
 restatement oracle/hist.py: device tile rows (K9) sort-reduced by (file, id, next_id,
 speed bin), pair cull at privacy p; entries merged across inputs (the owner's side of
-the exchange); the single-GPU end of the exchange (all entries owned by rank 0)."""
+the exchange); the single-GPU end of the exchange (all entries owned by rank 0); and the
+hand-built entry sets of tests/hist_cases.py, one for every choice of radix passes
+hist_reduce_impl makes from the data, for files of more than 1024 pairs and for the sizes around
+k_entry_range's blocks and grid."""
 import numpy as np
 import pytest
 
@@ -12,6 +15,7 @@ from reporter_amd import _lib
 from reporter_amd import matcher as M
 from reporter_amd import simple_reporter as sr
 from reporter_amd.tools import gen
+from tests import hist_cases as hc
 
 pytestmark = pytest.mark.gpu
 
@@ -90,3 +94,43 @@ def test_owner_cull_trailing_singleton_equals_reference_loop(workload):
         got = sr.hist_reduce(m, rows, len(rows), privacy=p, rows_in=True, memory='host')
         assert np.array_equal(got, oh.reduce(oh.entries_from_rows(rows), p))
         assert _pairs_from_entries(got) == _pairs_from_lines(rows, p)
+
+
+# ---- hand-built entry sets: every choice of radix passes, big files, sizes (tests/hist_cases.py,
+# pinned by tests/test_hist_cases_cpu.py) ------------------------------------------------------
+def _reduce_from_device(m, e, privacy):
+    import torch
+    src = torch.from_numpy(e.view(np.uint8).copy()).cuda()
+    out = torch.zeros(len(e) * _lib.HIST_ENTRY.itemsize, dtype=torch.uint8, device='cuda')
+    n = sr.hist_reduce(m, src.data_ptr(), len(e), privacy=privacy, out=out.data_ptr())
+    return out[:n * _lib.HIST_ENTRY.itemsize].cpu().numpy().view(_lib.HIST_ENTRY)
+
+
+@pytest.fixture(scope='module')
+def matcher(city):
+    return M.Matcher()
+
+
+@pytest.mark.parametrize('privacy', [1, 2, 3])
+@pytest.mark.parametrize('name', list(hc.FAMILIES))
+def test_family_reduce_equals_oracle(name, privacy, matcher):
+    """otr_hist_reduce on a hand-built set, from host memory and from a device buffer: the
+    entries of oracle/hist.reduce in key order, bit for bit."""
+    e = hc.entries(name)
+    want = hc.reduced(name, privacy)
+    assert len(want) > 0
+    got = sr.hist_reduce(matcher, e, len(e), privacy=privacy, memory='host')
+    assert np.array_equal(got, want)
+    assert np.array_equal(_reduce_from_device(matcher, e, privacy), want)
+
+
+@pytest.mark.parametrize('privacy', [2, 3])
+@pytest.mark.parametrize('name', ['big_1500', 'big_2500'])
+def test_big_file_cull_equals_reference_loop(name, privacy, matcher):
+    """Files of more than 1024 pairs (k_pair_file_top2's strided loop and LDS tree): the kept
+    pairs and their line counts are the reference loop's on the files' lines."""
+    from tests.test_hist_cull_cpu import _pairs_from_entries, _pairs_from_lines
+    rows, _ = hc.big_rows(name)
+    got = sr.hist_reduce(matcher, rows, len(rows), privacy=privacy, rows_in=True, memory='host')
+    assert np.array_equal(got, hc.reduced(name, privacy))
+    assert _pairs_from_entries(got) == _pairs_from_lines(rows, privacy)

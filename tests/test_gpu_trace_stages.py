@@ -133,7 +133,9 @@ def test_trace_does_not_depend_on_its_neighbours(setting, perm, runs, graph_dir)
 
 @pytest.mark.parametrize('setting', list(SETTINGS))
 def test_device_histogram(setting, runs, graph_dir):
-    """k_histogram, one wave per trace, on traces of 0 to more than 100 reports."""
+    """k_histogram, one wave per trace, on ragged_city's traces of 0 to 49 ('gtt'; 51 under
+    'deployed') reports: one stride of 64 lanes.  Traces of more reports, other quantisations
+    and other windows: tests/test_gpu_tile_stages.py."""
     from oracle.hist import histogram
     from reporter_amd import _lib
     from reporter_amd.graphfile import GraphFile
