@@ -597,7 +597,9 @@ int otr_sessions_snapshot(otr_matcher* m, otr_session_snapshot* out);
  * int32 count, float max_separation, int64 last_update, then count x (float lat, float lon,
  * int32 accuracy, int64 time): 16 + 20*count bytes.  Record i is bytes[rec_off[i] .. rec_off[i+1]);
  * bytes may start at any address and records at any offset.  key[i] is the 64-bit key of the
- * record's uuid: otr_uuid_key over the changelog key's UTF-8 bytes. */
+ * record's uuid: otr_uuid_key over the changelog key's UTF-8 bytes.  On a store with the uuid
+ * directory the changelog key of record i itself is entry i of otr_sessions_names after the
+ * export. */
 typedef struct otr_session_records {
   int64_t n_records;  int64_t n_bytes;
   int32_t memory;     int32_t reserved;        /* OTR_MEM_HOST / OTR_MEM_DEVICE (input) */
@@ -651,6 +653,74 @@ int otr_sessions_take(otr_matcher* m, int32_t n_parts, int32_t part, int32_t rem
 
 /* K11's 64-bit hash of a uuid's bytes, on the host: the key of a changelog record. */
 uint64_t otr_uuid_key(const char* uuid, int64_t len);
+
+/* ---- uuid directory: the name of every live session --------------
+ * The reference's store is KeyValueStore<String, Batch> (BatchingProcessor.java:21,47); ours is
+ * keyed by a 64-bit hash.  A store opened with otr_sessions_open_named also keeps, in HBM and per
+ * session slot, the uuid bytes of every live session (max_sessions x round_up(uuid_bytes, 16)
+ * bytes and a length each).  Every point then comes with a name: a key that is live under another
+ * name (two uuids sharing a hash) is refused instead of merged, snapshots, takes and exports list
+ * the names (a record's changelog key is entry i of that list), restores bring them back, and
+ * otr_sessions_punctuate evicts in ascending name order (unsigned bytes, a proper prefix first,
+ * ties by key; trigger = -1 - rank in that order): String order for ASCII uuids, UTF-8 byte order
+ * otherwise.  The store does not check key == otr_uuid_key(name): keying is the caller's choice,
+ * the directory demands one name per live key.  A name belongs to a live session only: once the
+ * session is deleted its key may come back under another name.  uuid_bytes: 1 .. 255, the
+ * longest name (OTR_BAD_REQUEST outside that range).  A store opened with otr_sessions_open has
+ * no directory and refuses the _named calls; a store with one refuses otr_sessions_push,
+ * otr_sessions_advance with points, otr_sessions_restore and otr_sessions_restore_records. */
+int otr_sessions_open_named(otr_matcher* m, const otr_session_config* cfg, int32_t uuid_bytes);
+
+/* One name per point or per session, in the same memory as the arrays it goes with: name i is
+ * bytes[off[i] .. off[i] + len[i]).  No byte outside [bytes, bytes + n_bytes) is read. */
+typedef struct otr_session_names {
+  const uint8_t* bytes;  int64_t n_bytes;
+  const int64_t* off;  const int32_t* len;
+} otr_session_names;
+
+/* Why a named chunk is refused.  The refusal is that of the lowest arrival index with any reason
+ * and, at that point, of the lowest value.  It comes after the chunk's own refusals (OTR_NO_ID,
+ * max_sessions) and like them leaves the store and the directory untouched. */
+#define OTR_NAME_E_LONG 1        /* len > uuid_bytes (0 is a valid length) */
+#define OTR_NAME_E_COLLISION 2   /* the key's live session has another name (length or any byte), or the
+                                    key is new in the chunk and its first-arriving point has another */
+#define OTR_NAME_E_LAYOUT 3      /* off < 0, len < 0 or off + len > n_bytes */
+
+typedef struct otr_session_name_refusal {
+  int64_t point;      /* arrival index in the chunk, -1: the last named call was not refused for a name */
+  int64_t message;    /* otr_sessions_push_text: the arrival index of the point's message; else -1 */
+  int32_t reason;     /* OTR_NAME_E_*, 0: none */
+  int32_t reserved;
+} otr_session_name_refusal;
+
+/* otr_sessions_push / otr_sessions_advance (pts non-NULL; a chunk is continued with
+ * otr_sessions_advance and NULL) on a store with a directory.  An accepted chunk stores the name
+ * of every key it created: that of the key's first-arriving point. */
+int otr_sessions_push_named(otr_matcher* m, const otr_session_points* pts, const otr_session_names* names,
+                            otr_session_result* out);
+int otr_sessions_advance_named(otr_matcher* m, const otr_session_points* pts, const otr_session_names* names,
+                               otr_trace_batch* out);
+int otr_sessions_last_refusal(otr_matcher* m, otr_session_name_refusal* out);
+
+/* The names of exactly the sessions of the matcher's last otr_sessions_snapshot, otr_sessions_take
+ * (gathered before a removal) or otr_sessions_export_records, in that listing's order: name i is
+ * bytes[off[i] .. off[i+1]).  Host and device arrays owned by the matcher, valid until its next
+ * session call; refused without a directory or without such a listing. */
+typedef struct otr_session_name_list {
+  int64_t n;  int64_t n_bytes;
+  const int64_t* off;  const uint8_t* bytes;      /* host: off has n + 1 elements */
+  const int64_t* d_off;  const uint8_t* d_bytes;  /* the same in HBM */
+} otr_session_name_list;
+int otr_sessions_names(otr_matcher* m, otr_session_name_list* out);
+
+/* otr_sessions_restore / otr_sessions_restore_records with one name per session (names in the
+ * memory of the sessions), on a store with a directory.  One more per-session reason, last in
+ * the order.  Names are stored as given. */
+#define OTR_RESTORE_E_NAME 7       /* the name's layout (as OTR_NAME_E_LAYOUT) or len > uuid_bytes */
+int otr_sessions_restore_named(otr_matcher* m, const otr_session_snapshot* snap, const otr_session_names* names,
+                               int32_t memory, otr_session_restore_result* out);
+int otr_sessions_restore_records_named(otr_matcher* m, const otr_session_records* recs,
+                                       const otr_session_names* names, otr_session_restore_result* out);
 
 /* ---- stream formatter: raw messages → keyed points in HBM -------
  * What KeyedFormattingProcessor.java:32-43 does with Formatter.formatSV / formatJSON: every

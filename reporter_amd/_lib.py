@@ -40,7 +40,11 @@ FORMAT_REASONS = {1: 'fields', 2: 'float', 3: 'int', 4: 'time', 5: 'accuracy', 6
 OTR_NO_ID = 0xFFFFFFFFFFFFFFFF
 OTR_RESTORE_E_LAYOUT, OTR_RESTORE_E_KEY, OTR_RESTORE_E_COUNT = 1, 2, 3
 OTR_RESTORE_E_DUPLICATE, OTR_RESTORE_E_LIVE, OTR_RESTORE_E_FULL = 4, 5, 6
+OTR_RESTORE_E_NAME = 7
 RESTORE_REASONS = {1: 'layout', 2: 'key', 3: 'count', 4: 'duplicate', 5: 'live', 6: 'full'}
+RESTORE_NAMED_REASONS = {**RESTORE_REASONS, 7: 'name'}   # the _named restores have one more
+OTR_NAME_E_LONG, OTR_NAME_E_COLLISION, OTR_NAME_E_LAYOUT = 1, 2, 3
+NAME_REASONS = {1: 'long', 2: 'collision', 3: 'layout'}
 HIST_BINS = 8
 KMAX = 64
 STAGES = ['states', 'candidates', 'link', 'route', 'route_big', 'viterbi', 'paths', 'paths_big', 'segments',
@@ -59,7 +63,10 @@ EXPORTS = ['otr_configure', 'otr_configure_json', 'otr_matcher_new', 'otr_matche
            'otr_sessions_windows', 'otr_sessions_snapshot', 'otr_tile_store_open', 'otr_tile_store_close',
            'otr_tile_store_add_session', 'otr_tile_store_add_reports', 'otr_tile_store_add_rows',
            'otr_tile_store_flush', 'otr_format_messages', 'otr_sessions_push_text', 'otr_sessions_restore',
-           'otr_sessions_restore_records', 'otr_sessions_export_records', 'otr_sessions_take', 'otr_uuid_key']
+           'otr_sessions_restore_records', 'otr_sessions_export_records', 'otr_sessions_take', 'otr_uuid_key',
+           'otr_sessions_open_named', 'otr_sessions_push_named', 'otr_sessions_advance_named',
+           'otr_sessions_last_refusal', 'otr_sessions_names', 'otr_sessions_restore_named',
+           'otr_sessions_restore_records_named']
 
 
 class ServiceSplit(ctypes.Structure):
@@ -258,6 +265,24 @@ class SessionRestoreResult(ctypes.Structure):
                 ('reserved', ctypes.c_int32)]
 
 
+class SessionNames(ctypes.Structure):
+    """otr_session_names (include/otr.h): one name per point or per session."""
+    _fields_ = [('bytes', ctypes.c_void_p), ('n_bytes', ctypes.c_int64), ('off', ctypes.c_void_p),
+                ('len', ctypes.c_void_p)]
+
+
+class SessionNameRefusal(ctypes.Structure):
+    """otr_session_name_refusal (include/otr.h): the last named call's name refusal."""
+    _fields_ = [('point', ctypes.c_int64), ('message', ctypes.c_int64), ('reason', ctypes.c_int32),
+                ('reserved', ctypes.c_int32)]
+
+
+class SessionNameList(ctypes.Structure):
+    """otr_session_name_list (include/otr.h): the names of the last listing, host and device."""
+    _fields_ = [('n', ctypes.c_int64), ('n_bytes', ctypes.c_int64), ('off', ctypes.c_void_p),
+                ('bytes', ctypes.c_void_p), ('d_off', ctypes.c_void_p), ('d_bytes', ctypes.c_void_p)]
+
+
 class TileStoreConfig(ctypes.Structure):
     """otr_tile_store_config (include/otr.h)."""
     _fields_ = [('max_rows', ctypes.c_int64), ('quantisation', ctypes.c_int32), ('privacy', ctypes.c_int32)]
@@ -370,6 +395,24 @@ def snapshot_to_numpy(r):
             for k, _, dt in SNAPSHOT_FIELDS}
 
 
+def pack_names(names):
+    """(bytes uint8, off int64, len int32) of a sequence of bytes objects, packed end to end."""
+    names = [bytes(x) for x in names]
+    ln = np.array([len(x) for x in names], np.int32)
+    off = np.zeros(len(names), np.int64)
+    if len(names):
+        off[1:] = np.cumsum(ln[:-1], dtype=np.int64)
+    return np.frombuffer(b''.join(names), np.uint8).copy(), off, ln
+
+
+def names_to_list(r):
+    """An otr_session_name_list as a list of bytes objects (host copies)."""
+    n = int(r.n)
+    off = _copy(r.off, n + 1, np.int64)
+    data = ctypes.string_at(r.bytes, int(r.n_bytes)) if r.bytes and r.n_bytes else b''
+    return [data[int(off[i]):int(off[i + 1])] for i in range(n)]
+
+
 def records_to_numpy(r):
     """An exported otr_session_records as host copies (key, rec_off, bytes); 'device' holds the
     struct, whose d_* arrays stay in HBM until the matcher's next session call."""
@@ -446,6 +489,16 @@ def lib():
                                         P(SessionSnapshot)]
         L.otr_uuid_key.argtypes = [ctypes.c_char_p, ctypes.c_int64]
         L.otr_uuid_key.restype = ctypes.c_uint64
+    if hasattr(L, 'otr_sessions_open_named'):
+        L.otr_sessions_open_named.argtypes = [ctypes.c_void_p, P(SessionConfig), ctypes.c_int32]
+        L.otr_sessions_push_named.argtypes = [ctypes.c_void_p, P(SessionPoints), P(SessionNames), P(SessionResult)]
+        L.otr_sessions_advance_named.argtypes = [ctypes.c_void_p, P(SessionPoints), P(SessionNames), P(TraceBatch)]
+        L.otr_sessions_last_refusal.argtypes = [ctypes.c_void_p, P(SessionNameRefusal)]
+        L.otr_sessions_names.argtypes = [ctypes.c_void_p, P(SessionNameList)]
+        L.otr_sessions_restore_named.argtypes = [ctypes.c_void_p, P(SessionSnapshot), P(SessionNames), ctypes.c_int32,
+                                                 P(SessionRestoreResult)]
+        L.otr_sessions_restore_records_named.argtypes = [ctypes.c_void_p, P(SessionRecords), P(SessionNames),
+                                                         P(SessionRestoreResult)]
     if hasattr(L, 'otr_tile_store_open'):  # (an A/B build of an earlier round may lack them)
         L.otr_tile_store_open.argtypes = [ctypes.c_void_p, P(TileStoreConfig)]
         L.otr_tile_store_close.argtypes = [ctypes.c_void_p]

@@ -172,6 +172,20 @@ def build_recordcheck(force=False, sanitize=False, out=None):
     return exe
 
 
+def build_namecheck(force=False, sanitize=False, out=None):
+    """tools/namecheck: the uuid directory's per-name rules as a stand-alone host program (CPU
+    tests only).  sanitize=True: built with AddressSanitizer and UndefinedBehaviorSanitizer (any
+    report is fatal), to `out` or tools/namecheck_san."""
+    src = os.path.join(PKG, 'tools', 'namecheck.cpp')
+    exe = out or os.path.join(PKG, 'tools', 'namecheck_san' if sanitize else 'namecheck')
+    deps = [src, os.path.join(CSRC, 'otr_session_names.h')]
+    if force or not _newer(exe, deps):
+        flags = ['-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
+                 '-fno-omit-frame-pointer'] if sanitize else ['-O2']
+        _run(['g++', '-std=c++17', '-Wall'] + flags + ['-o', exe, src])
+    return exe
+
+
 def build_mincheck(force=False):
     """tools/libmincheck.so: host build of the node tables' IN-gap codes (CPU tests only)."""
     src = os.path.join(PKG, 'tools', 'mincheck.cpp')
@@ -191,6 +205,7 @@ def build_all(force=False):
     build_formatcheck(force)
     build_mincheck(force)
     build_recordcheck(force)
+    build_namecheck(force)
     build_oracle(force)
     build_calib(force)
     with ThreadPoolExecutor(max_workers=3) as ex:

@@ -465,13 +465,13 @@ int otr_ingest(otr_matcher* m, const char* text, int64_t len, int32_t memory, co
   return rc
 
 int otr_sessions_open(otr_matcher* m, const otr_session_config* cfg) {
-  OTR_SESSIONS_CALL(!m || !cfg, sessions_open(cfg, &err));
+  OTR_SESSIONS_CALL(!m || !cfg, sessions_open(cfg, 0, &err));
 }
 
 int otr_sessions_close(otr_matcher* m) { OTR_SESSIONS_CALL(!m, sessions_close(&err)); }
 
 int otr_sessions_push(otr_matcher* m, const otr_session_points* pts, otr_session_result* out) {
-  OTR_SESSIONS_CALL(!m || !pts || !out, sessions_push(pts, out, &err));
+  OTR_SESSIONS_CALL(!m || !pts || !out, sessions_push(pts, nullptr, out, &err));
 }
 
 int otr_sessions_punctuate(otr_matcher* m, int64_t ts, otr_session_result* out) {
@@ -479,7 +479,7 @@ int otr_sessions_punctuate(otr_matcher* m, int64_t ts, otr_session_result* out) 
 }
 
 int otr_sessions_advance(otr_matcher* m, const otr_session_points* pts, otr_trace_batch* out) {
-  OTR_SESSIONS_CALL(!m || !out, sessions_advance(pts, out, &err));
+  OTR_SESSIONS_CALL(!m || !out, sessions_advance(pts, nullptr, out, &err));
 }
 
 int otr_sessions_commit(otr_matcher* m, const int32_t* shape_used, const int32_t* status, int32_t memory) {
@@ -497,11 +497,11 @@ int otr_sessions_snapshot(otr_matcher* m, otr_session_snapshot* out) {
 // restore, export and move (K17): Batch.Serder's values in and out (Batch.java:92-146)
 int otr_sessions_restore(otr_matcher* m, const otr_session_snapshot* snap, int32_t memory,
                          otr_session_restore_result* out) {
-  OTR_SESSIONS_CALL(!m || !snap || !out, sessions_restore(snap, memory, out, &err));
+  OTR_SESSIONS_CALL(!m || !snap || !out, sessions_restore(snap, nullptr, memory, out, &err));
 }
 
 int otr_sessions_restore_records(otr_matcher* m, const otr_session_records* recs, otr_session_restore_result* out) {
-  OTR_SESSIONS_CALL(!m || !recs || !out, sessions_restore_records(recs, out, &err));
+  OTR_SESSIONS_CALL(!m || !recs || !out, sessions_restore_records(recs, nullptr, out, &err));
 }
 
 int otr_sessions_export_records(otr_matcher* m, otr_session_records* out) {
@@ -513,6 +513,43 @@ int otr_sessions_take(otr_matcher* m, int32_t n_parts, int32_t part, int32_t rem
 }
 
 uint64_t otr_uuid_key(const char* uuid, int64_t len) { return otr::uuid_key_host(uuid, uuid ? len : 0); }
+
+// the uuid directory (K18): KeyValueStore<String, Batch>'s keys beside the sessions
+int otr_sessions_open_named(otr_matcher* m, const otr_session_config* cfg, int32_t uuid_bytes) {
+  if (uuid_bytes < 1 || uuid_bytes > 255) {
+    g_last_error = "uuid_bytes outside 1 .. 255";
+    return OTR_BAD_REQUEST;
+  }
+  OTR_SESSIONS_CALL(!m || !cfg, sessions_open(cfg, uuid_bytes, &err));
+}
+
+int otr_sessions_push_named(otr_matcher* m, const otr_session_points* pts, const otr_session_names* names,
+                            otr_session_result* out) {
+  OTR_SESSIONS_CALL(!m || !pts || !names || !out, sessions_push(pts, names, out, &err));
+}
+
+int otr_sessions_advance_named(otr_matcher* m, const otr_session_points* pts, const otr_session_names* names,
+                               otr_trace_batch* out) {
+  OTR_SESSIONS_CALL(!m || !pts || !names || !out, sessions_advance(pts, names, out, &err));
+}
+
+int otr_sessions_last_refusal(otr_matcher* m, otr_session_name_refusal* out) {
+  OTR_SESSIONS_CALL(!m || !out, sessions_last_refusal(out, &err));
+}
+
+int otr_sessions_names(otr_matcher* m, otr_session_name_list* out) {
+  OTR_SESSIONS_CALL(!m || !out, sessions_names(out, &err));
+}
+
+int otr_sessions_restore_named(otr_matcher* m, const otr_session_snapshot* snap, const otr_session_names* names,
+                               int32_t memory, otr_session_restore_result* out) {
+  OTR_SESSIONS_CALL(!m || !snap || !names || !out, sessions_restore(snap, names, memory, out, &err));
+}
+
+int otr_sessions_restore_records_named(otr_matcher* m, const otr_session_records* recs,
+                                       const otr_session_names* names, otr_session_restore_result* out) {
+  OTR_SESSIONS_CALL(!m || !recs || !names || !out, sessions_restore_records(recs, names, out, &err));
+}
 
 // the stream formatter (K16): KeyedFormattingProcessor.java:32-43 over Formatter.java:97-124
 int otr_format_messages(otr_matcher* m, const otr_message_format* fmt, const otr_messages* msgs,
@@ -528,9 +565,18 @@ int otr_sessions_push_text(otr_matcher* m, const otr_message_format* fmt, const 
   }
   std::string err;
   int rc = OTR_OK;
+  m->m.sessions_refusal_clear();
   if (m->m.ses) rc = m->m.format_messages(fmt, msgs, fmt_out, &err);  // (no store: the push's own refusal)
   else memset(fmt_out, 0, sizeof(*fmt_out));
-  if (rc == OTR_OK) rc = m->m.sessions_push(&fmt_out->points, session_out, &err);
+  if (rc == OTR_OK && m->m.sessions_named()) {
+    // the uuids in the formatter's device copy of the text (padded to 16 bytes, not reused before
+    // the push has read it) are the points' names
+    const otr_session_names names{m->m.fmt_text, m->m.fmt_text_len, fmt_out->d_uuid_off, fmt_out->d_uuid_len};
+    rc = m->m.sessions_push(&fmt_out->points, &names, session_out, &err);
+    if (rc != OTR_OK) m->m.sessions_refusal_message(fmt_out->d_message);
+  } else if (rc == OTR_OK) {
+    rc = m->m.sessions_push(&fmt_out->points, nullptr, session_out, &err);
+  }
   if (rc != OTR_OK) g_last_error = err;
   return rc;
 }

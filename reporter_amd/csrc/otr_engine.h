@@ -187,20 +187,35 @@ struct Matcher {
   int format_messages_impl(const otr_message_format* fmt, const otr_messages* msgs, otr_format_result* out,
                            std::string* err);
   // the session store (K14, otr_sessions.hip)
-  int sessions_open(const otr_session_config* cfg, std::string* err);
+  // (uuid_bytes > 0: with the uuid directory, K18; names: non-null on such a store only)
+  int sessions_open(const otr_session_config* cfg, int32_t uuid_bytes, std::string* err);
   int sessions_close(std::string* err);
-  int sessions_push(const otr_session_points* pts, otr_session_result* out, std::string* err);
+  int sessions_push(const otr_session_points* pts, const otr_session_names* names, otr_session_result* out,
+                    std::string* err);
   int sessions_punctuate(int64_t ts, otr_session_result* out, std::string* err);
-  int sessions_advance(const otr_session_points* pts, otr_trace_batch* out, std::string* err);
+  int sessions_advance(const otr_session_points* pts, const otr_session_names* names, otr_trace_batch* out,
+                       std::string* err);
   int sessions_commit(const int32_t* shape_used, const int32_t* status, int memory, std::string* err);
   int sessions_windows(otr_session_result* out, std::string* err);
   int sessions_snapshot(otr_session_snapshot* out, std::string* err);
   // restore, export and move (K17)
-  int sessions_restore(const otr_session_snapshot* snap, int memory, otr_session_restore_result* out,
-                       std::string* err);
-  int sessions_restore_records(const otr_session_records* recs, otr_session_restore_result* out, std::string* err);
+  int sessions_restore(const otr_session_snapshot* snap, const otr_session_names* names, int memory,
+                       otr_session_restore_result* out, std::string* err);
+  int sessions_restore_records(const otr_session_records* recs, const otr_session_names* names,
+                               otr_session_restore_result* out, std::string* err);
   int sessions_export_records(otr_session_records* out, std::string* err);
   int sessions_take(int n_parts, int part, int remove, otr_session_snapshot* out, std::string* err);
+  // the uuid directory (K18): whether the store has one, the names of the last listing, the last
+  // name refusal (and, after a refused otr_sessions_push_text, its message from d_message)
+  bool sessions_named() const;
+  int sessions_names(otr_session_name_list* out, std::string* err);
+  int sessions_last_refusal(otr_session_name_refusal* out, std::string* err);
+  void sessions_refusal_message(const int64_t* d_message);
+  void sessions_refusal_clear();
+  // the formatter's copy of the last chunk's text (S_IN_TEXT) and its length: what
+  // otr_format_result's d_uuid_off / d_uuid_len index
+  const uint8_t* fmt_text = nullptr;
+  int64_t fmt_text_len = 0;
   // the tile store (K15, otr_tilestore.hip)
   int tile_store_open(const otr_tile_store_config* cfg, std::string* err);
   int tile_store_close(std::string* err);

@@ -3514,6 +3514,8 @@ int Matcher::format_messages_impl(const otr_message_format* fmt, const otr_messa
   out->points.accuracy = o.acc;
   out->points.time = o.time;
   out->points.timestamp = o.ts;
+  fmt_text = d_text;
+  fmt_text_len = len;
   out->d_message = o.msg;
   out->d_uuid_off = o.uoff;
   out->d_uuid_len = o.ulen;

@@ -9,6 +9,7 @@
 
 #include "../../include/otr.h"
 #include "otr_device.h"
+#include "otr_session_names.h"
 #include "otr_session_records.h"
 
 namespace otr {
@@ -543,6 +544,142 @@ __global__ void k_ses_flag_part(SesStore s, uint32_t n_parts, uint32_t part, int
   const int32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
   if (slot >= s.max_sessions) return;
   flag[slot] = (s.n[slot] > 0 && s.skey[slot] % n_parts == part) ? 1 : 0;
+}
+
+// ---- K18: the uuid directory (include/otr.h otr_sessions_open_named ...) ---------------------
+// The name of every live session, by session slot (a table rebuild does not move it).  The
+// per-name rules are otr_session_names.h's.
+
+struct SesDir {
+  uint8_t* bytes;  // [max_sessions * row]: 16-byte aligned rows, zero-filled beyond the length
+  int32_t* len;    // [max_sessions]
+  int32_t row, uuid_bytes;
+};
+
+// the names that come with a chunk's points or a restore's sessions (device arrays)
+struct SesNamesIn {
+  const uint8_t* bytes;
+  int64_t n_bytes;
+  const int64_t* off;
+  const int32_t* len;
+};
+
+// after k_ses_insert: the first-arriving point of every key that is new in the chunk (K17's
+// atomicMin into a scratch word of the entry; first[] is kSesNoLane everywhere between calls)
+__global__ void k_ses_name_first(SesTable t, int64_t n, const int32_t* lane_entry, int32_t* first) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t e = lane_entry[i];
+  if (e >= 0 && t.slot[e] == kSesNew) atomicMin(&first[e], (int32_t)i);
+}
+
+// one lane per point, a kernel boundary after k_ses_name_first and before anything is
+// committed: the name's own faults, then the compare with the live session's row or with the
+// name of the key's first-arriving point.  A first arrival with a fault of its own is refused
+// at its lower index, so its name is not read.  bad: the lowest (index << 8 | reason).
+__global__ void k_ses_name_check(SesTable t, SesDir d, SesNamesIn nm, int64_t n, const int32_t* lane_entry,
+                                 const int32_t* first, unsigned long long* bad) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t e = lane_entry[i];
+  if (e < 0) return;  // (the chunk is refused for its keys)
+  const int64_t off = nm.off[i];
+  const int32_t len = nm.len[i];
+  const int32_t slot = t.slot[e];
+  const uint8_t* row = nullptr;
+  int32_t row_len = 0, flen = 0;
+  int64_t foff = 0;
+  bool has_first = false;
+  if (slot >= 0) {
+    row = d.bytes + (size_t)slot * (size_t)d.row;
+    row_len = d.len[slot];
+  } else {
+    const int32_t f = first[e];
+    if (f >= 0 && (int64_t)f < i) {
+      has_first = true;
+      foff = nm.off[f];
+      flen = nm.len[f];
+    }
+  }
+  const int32_t why = name_reason(nm.bytes, nm.n_bytes, d.uuid_bytes, off, len, row, row_len, has_first, foff, flen);
+  if (why) ses_refuse(bad, i, why);
+}
+
+// an accepted chunk, after k_ses_assign: the creator lane of every new key writes the name of
+// the key's first-arriving point into the session's row and clears the scratch word
+__global__ void k_ses_name_write(SesTable t, SesDir d, SesNamesIn nm, int64_t n, const int32_t* lane_entry,
+                                 const int32_t* is_new, int32_t* first) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || !is_new[i]) return;
+  const int32_t e = lane_entry[i];
+  const int32_t f = first[e];
+  first[e] = kSesNoLane;
+  const int32_t slot = t.slot[e];
+  if (f < 0 || (int64_t)f >= n || slot < 0) return;
+  const int32_t len = nm.len[f];
+  name_write_row(d.bytes + (size_t)slot * (size_t)d.row, d.row, nm.bytes, nm.off[f], len);
+  d.len[slot] = len;
+}
+
+// a refused chunk: the scratch words are kSesNoLane again
+__global__ void k_ses_name_unmark(int64_t n, const int32_t* lane_entry, const int32_t* is_new, int32_t* first) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && is_new[i]) first[lane_entry[i]] = kSesNoLane;
+}
+
+// restore: the name of every given session (keys are checked by k_ses_restore_check: none is
+// live, none comes twice, so there is nothing to compare with)
+__global__ void k_ses_restore_name_check(SesDir d, SesNamesIn nm, int64_t n, unsigned long long* bad) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && name_own_reason(nm.off[i], nm.len[i], nm.n_bytes, d.uuid_bytes)) ses_refuse(bad, i, OTR_RESTORE_E_NAME);
+}
+
+// beside k_ses_restore_copy: session i took free_list[n_free - 1 - i]
+__global__ void k_ses_restore_name_copy(SesDir d, SesNamesIn nm, int64_t n, const int32_t* free_list, int32_t n_free) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t slot = free_list[n_free - 1 - (int32_t)i];
+  const int32_t len = nm.len[i];
+  name_write_row(d.bytes + (size_t)slot * (size_t)d.row, d.row, nm.bytes, nm.off[i], len);
+  d.len[slot] = len;
+}
+
+// listed sessions: the length of each one's name, then the names packed at their offsets
+__global__ void k_ses_name_len(int32_t n_list, const int32_t* list, SesDir d, int64_t* len) {
+  const int32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g < n_list) len[g] = d.len[list[g]];
+}
+
+__global__ void k_ses_name_gather(int32_t n_list, const int32_t* list, const int64_t* off, SesDir d, uint8_t* bytes) {
+  const int32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n_list) return;
+  const uint8_t* row = d.bytes + (size_t)list[g] * (size_t)d.row;
+  const int64_t o = off[g];
+  const int32_t len = (int32_t)(off[g + 1] - o);
+  for (int32_t k = 0; k < len; ++k) bytes[o + k] = row[k];
+}
+
+// evictions in name order: stable LSD passes over a permutation of the key-ordered list.  The
+// key of pass w is sort word w of the row, or the name's length (w < 0).
+__global__ void k_ses_iota(int32_t n, int32_t* perm) {
+  const int32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g < n) perm[g] = g;
+}
+
+__global__ void k_ses_name_sort_key(int32_t n_list, const int32_t* list, const int32_t* perm, SesDir d, int32_t w,
+                                    unsigned long long* key) {
+  const int32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n_list) return;
+  const int32_t slot = list[perm[g]];
+  key[g] = w < 0 ? (unsigned long long)d.len[slot] : name_sort_word(d.bytes + (size_t)slot * (size_t)d.row, w);
+}
+
+__global__ void k_ses_permute(int32_t n_list, const int32_t* perm, const int32_t* list_in,
+                              const unsigned long long* key_in, int32_t* list_out, unsigned long long* key_out) {
+  const int32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n_list) return;
+  list_out[g] = list_in[perm[g]];
+  key_out[g] = key_in[perm[g]];
 }
 
 }  // namespace otr

@@ -47,6 +47,7 @@ enum SesBuf {
   B_R_KEY, B_R_TRIG, B_R_N, B_R_SU, B_R_STATUS, B_R_TRIM, B_R_OFF, B_R_ID, B_R_NEXT, B_R_T0, B_R_T1, B_R_LEN,
   B_R_QUEUE,
   B_RS_KEY, B_RS_OFF, B_RS_SEP, B_RS_LAST, B_RS_BYTES, B_RS_BAD, B_X_LEN, B_X_OFF, B_X_BYTES,
+  B_NM_BYTES, B_NM_OFF, B_NM_LEN, B_NL_LEN, B_NL_OFF, B_NL_BYTES, B_NS_KEY, B_NS_KEY2, B_NS_PERM, B_NS_PERM2,
   B_NUM
 };
 const char* const kBufName[B_NUM] = {
@@ -61,7 +62,8 @@ const char* const kBufName[B_NUM] = {
     "result shape_used", "result status", "result trimmed", "result report offsets", "result id", "result next id",
     "result t0", "result t1", "result length", "result queue length", "restore key", "restore offsets",
     "restore max_sep", "restore last_update", "restore bytes", "restore refusal", "record lengths", "record offsets",
-    "record bytes"};
+    "record bytes", "name bytes", "name offsets", "name lengths", "listed name lengths", "listed name offsets",
+    "listed name bytes", "name sort key", "sorted name sort key", "name order", "sorted name order"};
 
 }  // namespace
 
@@ -107,6 +109,15 @@ struct SessionStore {
   // exported records
   std::vector<int64_t> x_off;
   std::vector<uint8_t> x_bytes;
+  // K18: the uuid directory (dir.row == 0: none), its scratch words per table entry, the names
+  // of the last listing and the last name refusal
+  SesDir dir{};
+  int32_t* name_first = nullptr;
+  std::vector<int64_t> nl_off;
+  std::vector<uint8_t> nl_bytes;
+  bool names_have = false;
+  otr_session_name_refusal refusal{-1, -1, 0, 0};
+  bool named() const { return dir.row > 0; }
 
   int32_t live() const { return cfg.max_sessions - h_cnt[SES_NFREE]; }
 
@@ -143,7 +154,10 @@ struct SessionStore {
   int scan64(const int64_t* in, int64_t* out, int64_t n, std::string* err);
   int alloc(std::string* err);
   int rebuild(std::string* err);
-  int chunk_begin(const otr_session_points* pts, std::string* err);
+  int chunk_begin(const otr_session_points* pts, const SesNamesIn* nm, std::string* err);
+  int names_in(const otr_session_names* names, int64_t n, int memory, SesNamesIn* out, std::string* err);
+  int names_list(std::string* err);
+  int name_order(std::string* err);
   int round(std::string* err);
   int gather(std::string* err);
   int commit(const int32_t* su, const int32_t* status, int memory, std::string* err);
@@ -156,7 +170,7 @@ struct SessionStore {
   int list_flagged(std::string* err);
   int snapshot_list(otr_session_snapshot* out, std::string* err);
   template <bool REC>
-  int restore(SesGiven g, int memory, otr_session_restore_result* out, std::string* err);
+  int restore(SesGiven g, const SesNamesIn* nm, otr_session_restore_result* out, std::string* err);
   int release_list(const int32_t* list, int32_t n, std::string* err);
 };
 
@@ -207,6 +221,15 @@ int SessionStore::alloc(std::string* err) {
   st.time = fix<int64_t>(np, "session points time");
   free_list = fix<int32_t>(ms, "free sessions");
   cnt = fix<int32_t>(SES_WORDS, "store counters");
+  if (dir.uuid_bytes > 0) {
+    dir.row = name_row_bytes(dir.uuid_bytes);
+    dir.bytes = fix<uint8_t>(ms * (size_t)dir.row, "session names");
+    dir.len = fix<int32_t>(ms, "session name lengths");
+    name_first = fix<int32_t>(cap, "name scratch words");
+    HIPCHK(hipMemsetAsync(dir.bytes, 0, ms * (size_t)dir.row, stream));
+    HIPCHK(hipMemsetAsync(dir.len, 0, 4 * ms, stream));
+    HIPCHK(hipMemsetAsync(name_first, 0x7F, 4 * cap, stream));
+  }
   HIPCHK(hipMemsetAsync(tab.key, 0xFF, 8 * cap, stream));
   HIPCHK(hipMemsetAsync(tab.slot, 0xFF, 4 * cap, stream));
   HIPCHK(hipMemsetAsync(st.n, 0, 4 * ms, stream));
@@ -237,7 +260,39 @@ int SessionStore::rebuild(std::string* err) {
   return OTR_OK;
 }
 
-int SessionStore::chunk_begin(const otr_session_points* pts, std::string* err) {
+// the names of a call in device memory (copied when they are the host's)
+int SessionStore::names_in(const otr_session_names* names, int64_t n, int memory, SesNamesIn* out, std::string* err) {
+  *out = SesNamesIn{nullptr, 0, nullptr, nullptr};
+  if (n <= 0) return OTR_OK;
+  if (!names->off || !names->len || (names->n_bytes > 0 && !names->bytes)) {
+    if (err) *err = "null argument";
+    return OTR_BAD_REQUEST;
+  }
+  if (names->n_bytes < 0 || names->n_bytes > (int64_t)1 << 40) {
+    if (err) *err = "name bytes out of range (2^40 at most)";
+    return OTR_BAD_REQUEST;
+  }
+  out->n_bytes = names->n_bytes;
+  if (memory == OTR_MEM_DEVICE) {
+    out->bytes = names->bytes;
+    out->off = names->off;
+    out->len = names->len;
+    return OTR_OK;
+  }
+  uint8_t* bytes = buf<uint8_t>(B_NM_BYTES, names->n_bytes);
+  int64_t* off = buf<int64_t>(B_NM_OFF, n);
+  int32_t* len = buf<int32_t>(B_NM_LEN, n);
+  if (names->n_bytes > 0)
+    HIPCHK(hipMemcpyAsync(bytes, names->bytes, (size_t)names->n_bytes, hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(off, names->off, 8 * (size_t)n, hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(len, names->len, 4 * (size_t)n, hipMemcpyHostToDevice, stream));
+  out->bytes = bytes;
+  out->off = off;
+  out->len = len;
+  return OTR_OK;
+}
+
+int SessionStore::chunk_begin(const otr_session_points* pts, const SesNamesIn* nm, std::string* err) {
   int rc;
   const int64_t n = pts->n;
   W = 0;
@@ -278,14 +333,30 @@ int SessionStore::chunk_begin(const otr_session_points* pts, std::string* err) {
   k_ses_insert<<<g, 256, 0, stream>>>(tab, ch, entry, fresh, cnt);
   if ((rc = scan32(fresh, rank, n, err))) return rc;
   int32_t n_new = 0, flags = 0;
+  unsigned long long h_bad = kSesNoBad;
+  if (nm) {  // K18: the names against the directory, read back with the chunk's own refusals
+    unsigned long long* bad = buf<unsigned long long>(B_RS_BAD, 1);
+    HIPCHK(hipMemsetAsync(bad, 0xFF, 8, stream));
+    k_ses_name_first<<<g, 256, 0, stream>>>(tab, n, entry, name_first);
+    k_ses_name_check<<<g, 256, 0, stream>>>(tab, dir, *nm, n, entry, name_first, bad);
+    HIPCHK(hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, stream));
+  }
   HIPCHK(hipMemcpyAsync(&n_new, rank + (n - 1), 4, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipMemcpyAsync(&flags, cnt + SES_FLAGS, 4, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
-  if (flags || n_new > h_cnt[SES_NFREE]) {
+  const bool own = flags || n_new > h_cnt[SES_NFREE];
+  if (own || h_bad != kSesNoBad) {
+    if (nm) k_ses_name_unmark<<<g, 256, 0, stream>>>(n, entry, fresh, name_first);
     k_ses_rollback<<<g, 256, 0, stream>>>(tab, n, entry, fresh);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(stream));
-    if (err)
+    if (!own) {
+      static const char* const why[] = {"", "name longer than uuid_bytes", "the key is live under another name",
+                                        "name layout"};
+      refusal.point = (int64_t)(h_bad >> 8);
+      refusal.reason = (int32_t)(h_bad & 0xFF);
+      if (err) *err = "point " + std::to_string(refusal.point) + ": " + why[refusal.reason & 3];
+    } else if (err)
       *err = (flags & kSesFlagNoId) ? "key OTR_NO_ID is the store's empty mark"
                                     : "the chunk would take the live sessions beyond max_sessions (" +
                                           std::to_string(live()) + " live, " + std::to_string(cfg.max_sessions) +
@@ -297,6 +368,7 @@ int SessionStore::chunk_begin(const otr_session_points* pts, std::string* err) {
     k_ses_assign<<<g, 256, 0, stream>>>(tab, st, ch, entry, fresh, rank, free_list, h_cnt[SES_NFREE]);
     k_ses_add<<<1, 1, 0, stream>>>(cnt + SES_NFREE, -n_new);
     h_cnt[SES_NFREE] -= n_new;
+    if (nm) k_ses_name_write<<<g, 256, 0, stream>>>(tab, dir, *nm, n, entry, fresh, name_first);
   }
   k_ses_lane_slot<<<g, 256, 0, stream>>>(tab, n, entry, lane_slot, idx);
   int bits = 1;
@@ -607,6 +679,71 @@ int SessionStore::list_flagged(std::string* err) {
   return OTR_OK;
 }
 
+// K18: the names of the sessions listed in B_L_SLOT2, in the listing's order, in HBM
+// (B_NL_OFF / B_NL_BYTES) and in nl_off / nl_bytes
+int SessionStore::names_list(std::string* err) {
+  int rc;
+  const int32_t ns = n_list;
+  nl_off.assign((size_t)ns + 1, 0);
+  nl_bytes.clear();
+  int64_t* off = buf<int64_t>(B_NL_OFF, (size_t)ns + 1);
+  buf<uint8_t>(B_NL_BYTES, 0);
+  HIPCHK(hipMemsetAsync(off, 0, 8, stream));
+  names_have = true;
+  if (ns == 0) {
+    HIPCHK(hipStreamSynchronize(stream));
+    return OTR_OK;
+  }
+  const int32_t* list = (const int32_t*)b[B_L_SLOT2].p;
+  int64_t* len = buf<int64_t>(B_NL_LEN, ns);
+  k_ses_name_len<<<ses_grid(ns, 256), 256, 0, stream>>>(ns, list, dir, len);
+  if ((rc = scan64(len, off + 1, ns, err))) return rc;
+  HIPCHK(hipMemcpyAsync(nl_off.data(), off, 8 * ((size_t)ns + 1), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  const int64_t nb = nl_off[ns];
+  uint8_t* bytes = buf<uint8_t>(B_NL_BYTES, nb);
+  k_ses_name_gather<<<ses_grid(ns, 256), 256, 0, stream>>>(ns, list, off, dir, bytes);
+  HIPCHK(hipGetLastError());
+  nl_bytes.resize((size_t)nb);
+  if (nb > 0) HIPCHK(hipMemcpyAsync(nl_bytes.data(), bytes, (size_t)nb, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  return OTR_OK;
+}
+
+// K18: the key-ordered list of B_L_KEY2 / B_L_SLOT2 into ascending name order (ties keep the
+// key order): stable LSD passes over a permutation, the length first, then the sort words of
+// the rows from the last to the first
+int SessionStore::name_order(std::string* err) {
+  const int32_t ns = n_list;
+  if (ns < 2) return OTR_OK;
+  const unsigned g = ses_grid(ns, 256);
+  unsigned long long* key = buf<unsigned long long>(B_NS_KEY, ns);
+  unsigned long long* key2 = buf<unsigned long long>(B_NS_KEY2, ns);
+  int32_t* perm = buf<int32_t>(B_NS_PERM, ns);
+  int32_t* perm2 = buf<int32_t>(B_NS_PERM2, ns);
+  int32_t* list = (int32_t*)b[B_L_SLOT2].p;
+  unsigned long long* lkey = (unsigned long long*)b[B_L_KEY2].p;
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key, key2, perm, perm2, ns, 0, 64, stream));
+  void* tmp = buf<char>(B_TMP, tb);
+  k_ses_iota<<<g, 256, 0, stream>>>(ns, perm);
+  for (int32_t w = -1, pass = 0; pass <= name_sort_words(dir.uuid_bytes); ++pass) {
+    k_ses_name_sort_key<<<g, 256, 0, stream>>>(ns, list, perm, dir, w, key);
+    size_t tb2 = tb;
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb2, key, key2, perm, perm2, ns, 0, w < 0 ? 9 : 64, stream));
+    std::swap(perm, perm2);
+    w = w < 0 ? name_sort_words(dir.uuid_bytes) - 1 : w - 1;
+  }
+  // (the unsorted list's buffers are free by now)
+  int32_t* list_out = (int32_t*)b[B_L_SLOT].p;
+  unsigned long long* key_out = (unsigned long long*)b[B_L_KEY].p;
+  k_ses_permute<<<g, 256, 0, stream>>>(ns, perm, list, lkey, list_out, key_out);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(list, list_out, 4 * (size_t)ns, hipMemcpyDeviceToDevice, stream));
+  HIPCHK(hipMemcpyAsync(lkey, key_out, 8 * (size_t)ns, hipMemcpyDeviceToDevice, stream));
+  return OTR_OK;
+}
+
 // the sessions listed in B_L_KEY2 / B_L_SLOT2 as a snapshot in the store's host arrays
 int SessionStore::snapshot_list(otr_session_snapshot* out, std::string* err) {
   int rc;
@@ -614,6 +751,7 @@ int SessionStore::snapshot_list(otr_session_snapshot* out, std::string* err) {
   const int32_t ns = n_list;
   s_off.assign((size_t)ns + 1, 0);
   out->point_off = s_off.data();
+  if (named() && (rc = names_list(err))) return rc;
   if (ns == 0) return OTR_OK;
   const int32_t* list = (const int32_t*)b[B_L_SLOT2].p;
   int32_t* rep = buf<int32_t>(B_L_REP, ns);
@@ -671,7 +809,7 @@ int SessionStore::snapshot_list(otr_session_snapshot* out, std::string* err) {
 
 // K17: the given sessions (device arrays) merged into the store, all or nothing
 template <bool REC>
-int SessionStore::restore(SesGiven g, int memory, otr_session_restore_result* out, std::string* err) {
+int SessionStore::restore(SesGiven g, const SesNamesIn* nm, otr_session_restore_result* out, std::string* err) {
   int rc;
   const int64_t n = g.n;
   out->n_live = live();
@@ -686,6 +824,7 @@ int SessionStore::restore(SesGiven g, int memory, otr_session_restore_result* ou
   HIPCHK(hipMemsetAsync(cnt + SES_FLAGS, 0, 4, stream));
   const unsigned grid = ses_grid(n, 256);
   k_ses_restore_check<REC><<<grid, 256, 0, stream>>>(tab, g, cfg.max_points, first, entry, fresh, bad, cnt);
+  if (nm) k_ses_restore_name_check<<<grid, 256, 0, stream>>>(dir, *nm, n, bad);
   HIPCHK(hipGetLastError());
   unsigned long long h_bad = kSesNoBad;
   int32_t flags = 0;
@@ -715,7 +854,9 @@ int SessionStore::restore(SesGiven g, int memory, otr_session_restore_result* ou
                                       "key OTR_NO_ID is the store's empty mark",
                                       "count outside 1 .. max_points - 1",
                                       "duplicate key",
-                                      "the key has a live session"};
+                                      "the key has a live session",
+                                      "",
+                                      "name layout or longer than uuid_bytes"};
     if (h_bad != kSesNoBad) {
       out->bad_session = (int64_t)(h_bad >> 8);
       out->bad_reason = (int32_t)(h_bad & 0xFF);
@@ -729,6 +870,7 @@ int SessionStore::restore(SesGiven g, int memory, otr_session_restore_result* ou
     return OTR_BAD_REQUEST;
   }
   k_ses_restore_copy<REC><<<(unsigned)n, 64, 0, stream>>>(tab, st, g, entry, free_list, h_cnt[SES_NFREE]);
+  if (nm) k_ses_restore_name_copy<<<grid, 256, 0, stream>>>(dir, *nm, n, free_list, h_cnt[SES_NFREE]);
   k_ses_add<<<1, 1, 0, stream>>>(cnt + SES_NFREE, -(int32_t)n);
   HIPCHK(hipGetLastError());
   h_cnt[SES_NFREE] -= (int32_t)n;
@@ -742,11 +884,12 @@ int SessionStore::restore(SesGiven g, int memory, otr_session_restore_result* ou
 namespace {
 
 template <class F>
-int guarded(Matcher& m, std::string* err, bool need_store, F&& f) {
+int guarded(Matcher& m, std::string* err, bool need_store, F&& f, bool keep_names = false) {
   if (need_store && !m.ses) {
     if (err) *err = "no session store: call otr_sessions_open first";
     return OTR_BAD_REQUEST;
   }
+  if (m.ses && !keep_names) m.ses->names_have = false;  // a listing's names last until the next session call
   try {
     return f();
   } catch (const SesOom& o) {
@@ -768,10 +911,20 @@ bool points_ok(const otr_session_points* p) {
   return p->n <= 0 || (p->key && p->lat && p->lon && p->accuracy && p->time && p->timestamp);
 }
 
+// K18: a store with a directory takes its points and sessions with names, a plain one without
+const char* names_mismatch(const SessionStore& s, bool given) {
+  if (s.named() && !given) return "the store has a uuid directory: use the _named call";
+  if (!s.named() && given) return "the store has no uuid directory: open it with otr_sessions_open_named";
+  return nullptr;
+}
+
 }  // namespace
 
-int Matcher::sessions_open(const otr_session_config* cfg, std::string* err) {
+bool Matcher::sessions_named() const { return ses && ses->named(); }
+
+int Matcher::sessions_open(const otr_session_config* cfg, int32_t uuid_bytes, std::string* err) {
   if (ses) return bad(err, "the matcher already has a session store");
+  if (uuid_bytes < 0 || uuid_bytes > 255) return bad(err, "uuid_bytes outside 1 .. 255");
   if (cfg->max_sessions < 1 || cfg->max_sessions > (1 << 30) || cfg->max_points < 2 || cfg->mode < 0 ||
       cfg->mode > 2 || (int64_t)cfg->max_sessions * cfg->max_points > ((int64_t)1 << 40) || cfg->report_count < 0)
     return bad(err, "session config out of range");
@@ -780,6 +933,7 @@ int Matcher::sessions_open(const otr_session_config* cfg, std::string* err) {
   SessionStore* s = new SessionStore();
   s->cfg = *cfg;
   s->stream = stream;
+  s->dir.uuid_bytes = uuid_bytes;
   const int rc = guarded(*this, err, false, [&] { return s->alloc(err); });
   if (rc != OTR_OK) {
     sessions_destroy(s);
@@ -796,16 +950,21 @@ int Matcher::sessions_close(std::string* err) {
   return OTR_OK;
 }
 
-int Matcher::sessions_advance(const otr_session_points* pts, otr_trace_batch* out, std::string* err) {
+int Matcher::sessions_advance(const otr_session_points* pts, const otr_session_names* names, otr_trace_batch* out,
+                              std::string* err) {
   return guarded(*this, err, true, [&]() -> int {
     SessionStore& s = *ses;
     int rc;
     HIPCHK(hipSetDevice(graph_state().device));
+    if (names) s.refusal = otr_session_name_refusal{-1, -1, 0, 0};
     if (s.pending) return bad(err, "the last advance has not been committed");
     if (pts) {
+      if (const char* w = names_mismatch(s, names != nullptr)) return bad(err, w);
       if (s.chunk_open) return bad(err, "the current chunk is not consumed");
       if (!points_ok(pts)) return bad(err, "null argument");
-      if ((rc = s.chunk_begin(pts, err))) return rc;
+      SesNamesIn nm;
+      if (names && (rc = s.names_in(names, pts->n, pts->memory, &nm, err))) return rc;
+      if ((rc = s.chunk_begin(pts, names ? &nm : nullptr, err))) return rc;
     }
     s.W = 0;
     if (s.chunk_open && (rc = s.round(err))) return rc;
@@ -838,10 +997,13 @@ int Matcher::sessions_windows(otr_session_result* out, std::string* err) {
   });
 }
 
-int Matcher::sessions_push(const otr_session_points* pts, otr_session_result* out, std::string* err) {
+int Matcher::sessions_push(const otr_session_points* pts, const otr_session_names* names, otr_session_result* out,
+                           std::string* err) {
   return guarded(*this, err, true, [&]() -> int {
     SessionStore& s = *ses;
     int rc;
+    if (names) s.refusal = otr_session_name_refusal{-1, -1, 0, 0};
+    if (const char* w = names_mismatch(s, names != nullptr)) return bad(err, w);
     if (!graph_state().ready) {
       if (err) *err = "otr_configure has not been called";
       return OTR_NOT_CONFIGURED;
@@ -851,7 +1013,9 @@ int Matcher::sessions_push(const otr_session_points* pts, otr_session_result* ou
     if (!points_ok(pts)) return bad(err, "null argument");
     s.result_begin();
     HIPCHK(hipEventRecord(s.ev[0], stream));
-    if ((rc = s.chunk_begin(pts, err))) return rc;
+    SesNamesIn nm;
+    if (names && (rc = s.names_in(names, pts->n, pts->memory, &nm, err))) return rc;
+    if ((rc = s.chunk_begin(pts, names ? &nm : nullptr, err))) return rc;
     while (s.chunk_open) {
       if ((rc = s.round(err))) return rc;
       if (s.W == 0) break;
@@ -879,6 +1043,7 @@ int Matcher::sessions_punctuate(int64_t ts, otr_session_result* out, std::string
     s.W = 0;
     HIPCHK(hipEventRecord(s.ev[0], stream));
     if ((rc = s.list_sessions(1, ts, err))) return rc;
+    if (s.named() && (rc = s.name_order(err))) return rc;
     const int32_t ne = s.n_list;
     if (ne > 0) {
       const int32_t* list = (const int32_t*)s.b[B_L_SLOT2].p;
@@ -937,14 +1102,15 @@ void restore_result_begin(otr_session_restore_result* out) {
 
 }  // namespace
 
-int Matcher::sessions_restore(const otr_session_snapshot* snap, int memory, otr_session_restore_result* out,
-                              std::string* err) {
+int Matcher::sessions_restore(const otr_session_snapshot* snap, const otr_session_names* names, int memory,
+                              otr_session_restore_result* out, std::string* err) {
   restore_result_begin(out);
   return guarded(*this, err, true, [&]() -> int {
     SessionStore& s = *ses;
     int rc;
     HIPCHK(hipSetDevice(graph_state().device));
     out->n_live = s.live();
+    if (const char* w = names_mismatch(s, names != nullptr)) return bad(err, w);
     if (s.pending || s.chunk_open) return bad(err, "an advance / commit sequence is open");
     const int64_t n = snap->n_sessions, np = snap->n_points;
     if (n < 0 || np < 0 || n > (int64_t)1 << 30 || np > (int64_t)1 << 40)
@@ -998,7 +1164,9 @@ int Matcher::sessions_restore(const otr_session_snapshot* snap, int memory, otr_
       g.acc = acc;
       g.time = time;
     }
-    if ((rc = s.restore<false>(g, memory, out, err))) return rc;
+    SesNamesIn nm;
+    if (names && (rc = s.names_in(names, n, memory, &nm, err))) return rc;
+    if ((rc = s.restore<false>(g, names ? &nm : nullptr, out, err))) return rc;
     out->n_points = np;
     HIPCHK(hipEventRecord(s.ev[1], stream));
     HIPCHK(hipStreamSynchronize(stream));
@@ -1007,14 +1175,15 @@ int Matcher::sessions_restore(const otr_session_snapshot* snap, int memory, otr_
   });
 }
 
-int Matcher::sessions_restore_records(const otr_session_records* recs, otr_session_restore_result* out,
-                                      std::string* err) {
+int Matcher::sessions_restore_records(const otr_session_records* recs, const otr_session_names* names,
+                                      otr_session_restore_result* out, std::string* err) {
   restore_result_begin(out);
   return guarded(*this, err, true, [&]() -> int {
     SessionStore& s = *ses;
     int rc;
     HIPCHK(hipSetDevice(graph_state().device));
     out->n_live = s.live();
+    if (const char* w = names_mismatch(s, names != nullptr)) return bad(err, w);
     if (s.pending || s.chunk_open) return bad(err, "an advance / commit sequence is open");
     const int64_t n = recs->n_records, nb = recs->n_bytes;
     if (n < 0 || nb < 0 || n > (int64_t)1 << 30 || nb > (int64_t)1 << 44)
@@ -1040,7 +1209,9 @@ int Matcher::sessions_restore_records(const otr_session_records* recs, otr_sessi
       g.off = off;
       g.bytes = bytes;
     }
-    if ((rc = s.restore<true>(g, recs->memory, out, err))) return rc;
+    SesNamesIn nm;
+    if (names && (rc = s.names_in(names, n, recs->memory, &nm, err))) return rc;
+    if ((rc = s.restore<true>(g, names ? &nm : nullptr, out, err))) return rc;
     int64_t ends[2] = {0, 0};  // every record was as long as its count says
     HIPCHK(hipMemcpyAsync(&ends[0], g.off, 8, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipMemcpyAsync(&ends[1], g.off + n, 8, hipMemcpyDeviceToHost, stream));
@@ -1067,6 +1238,7 @@ int Matcher::sessions_export_records(otr_session_records* out, std::string* err)
     HIPCHK(hipMemsetAsync(off, 0, 8, stream));
     out->rec_off = s.x_off.data();
     out->d_rec_off = off;
+    if (s.named() && (rc = s.names_list(err))) return rc;
     if (ns == 0) {
       HIPCHK(hipStreamSynchronize(stream));
       return OTR_OK;
@@ -1115,6 +1287,49 @@ int Matcher::sessions_take(int n_parts, int part, int remove, otr_session_snapsh
     }
     return OTR_OK;
   });
+}
+
+// ---- K18: the names of a listing, the last name refusal ----------------------------------------
+
+int Matcher::sessions_names(otr_session_name_list* out, std::string* err) {
+  return guarded(
+      *this, err, true,
+      [&]() -> int {
+        SessionStore& s = *ses;
+        memset(out, 0, sizeof(*out));
+        if (!s.named()) return bad(err, "the store has no uuid directory: open it with otr_sessions_open_named");
+        if (!s.names_have)
+          return bad(err, "no listing: call otr_sessions_snapshot, otr_sessions_take or otr_sessions_export_records");
+        out->n = (int64_t)s.nl_off.size() - 1;
+        out->n_bytes = s.nl_off.back();
+        out->off = s.nl_off.data();
+        out->bytes = s.nl_bytes.data();
+        out->d_off = (const int64_t*)s.b[B_NL_OFF].p;
+        out->d_bytes = (const uint8_t*)s.b[B_NL_BYTES].p;
+        return OTR_OK;
+      },
+      true);
+}
+
+int Matcher::sessions_last_refusal(otr_session_name_refusal* out, std::string* err) {
+  return guarded(
+      *this, err, true,
+      [&]() -> int {
+        *out = ses->refusal;
+        return OTR_OK;
+      },
+      true);
+}
+
+void Matcher::sessions_refusal_clear() {
+  if (ses) ses->refusal = otr_session_name_refusal{-1, -1, 0, 0};
+}
+
+// otr_sessions_push_text: the message of the refused point
+void Matcher::sessions_refusal_message(const int64_t* d_message) {
+  if (!ses || !ses->refusal.reason || !d_message) return;
+  int64_t msg = -1;
+  if (hipMemcpy(&msg, d_message + ses->refusal.point, 8, hipMemcpyDeviceToHost) == hipSuccess) ses->refusal.message = msg;
 }
 
 }  // namespace otr

@@ -18,6 +18,16 @@ P = ctypes.POINTER
 MODES = {'auto': 0, 'bicycle': 1, 'pedestrian': 2}
 
 
+class NameRefusal(ValueError):
+    """A chunk refused by the session store's uuid directory: point is the arrival index in the
+    chunk, reason an _lib.OTR_NAME_E_* value, message the arrival index of the point's message
+    after sessions_push_text (-1 otherwise)."""
+
+    def __init__(self, text, point, reason, message=-1):
+        super().__init__(text)
+        self.point, self.reason, self.message = point, reason, message
+
+
 OTR_KEYS = ('speed_kph', 'queue_kph', 'delta')  # engine keys (DESIGN.md §3.5, §3.8), not meili's
 
 
@@ -358,8 +368,10 @@ class Matcher:
 
     def sessions_open(self, max_sessions, max_points, report_dist=500.0, report_count=10, report_time=60,
                       session_gap=60000, mode='auto', report_levels=(0, 1), transition_levels=(0, 1),
-                      threshold_sec=15, batch_probes=0):
-        """Open this matcher's session store (defaults: BatchingProcessor's gates)."""
+                      threshold_sec=15, batch_probes=0, uuid_bytes=0):
+        """Open this matcher's session store (defaults: BatchingProcessor's gates).  uuid_bytes > 0:
+        with the uuid directory (otr_sessions_open_named): every point and every restored session
+        then comes with a name of at most that many bytes."""
         c = _lib.SessionConfig()
         c.max_sessions, c.max_points = int(max_sessions), int(max_points)
         c.report_dist, c.report_count, c.report_time = float(report_dist), int(report_count), int(report_time)
@@ -369,7 +381,12 @@ class Matcher:
         c.transition_levels = _lib.levels_mask(transition_levels)
         c.threshold_sec = int(threshold_sec)
         c.batch_probes = int(batch_probes)
-        self._check(self._L.otr_sessions_open(self._h, ctypes.byref(c)), 'otr_sessions_open')
+        if uuid_bytes:
+            self._check(self._L.otr_sessions_open_named(self._h, ctypes.byref(c), int(uuid_bytes)),
+                        'otr_sessions_open_named')
+        else:
+            self._check(self._L.otr_sessions_open(self._h, ctypes.byref(c)), 'otr_sessions_open')
+        self.session_uuid_bytes = int(uuid_bytes)   # 0: the open store has no uuid directory
 
     def sessions_close(self):
         self._check(self._L.otr_sessions_close(self._h), 'otr_sessions_close')
@@ -392,12 +409,64 @@ class Matcher:
                 setattr(p, k, a.ctypes.data)
         return p
 
-    def sessions_push(self, points, device=False):
+    def _session_names(self, names, device):
+        """names: a sequence of bytes objects (host), or a dict of 'bytes', 'off', 'len' (numpy
+        arrays, or device pointers with device=True) and optionally 'n_bytes'."""
+        s = _lib.SessionNames()
+        if device:
+            s.bytes, s.n_bytes = int(names['bytes']) or None, int(names['n_bytes'])
+            s.off, s.len = int(names['off']) or None, int(names['len']) or None
+            return s
+        if isinstance(names, dict):
+            data = np.ascontiguousarray(names['bytes'], np.uint8)
+            off, ln = np.ascontiguousarray(names['off'], np.int64), np.ascontiguousarray(names['len'], np.int32)
+            n_bytes = int(names.get('n_bytes', len(data)))
+        else:
+            data, off, ln = _lib.pack_names(names)
+            n_bytes = len(data)
+        self._keep_names = [data, off, ln]
+        s.bytes, s.n_bytes = (data.ctypes.data if len(data) else None), n_bytes
+        s.off, s.len = off.ctypes.data, ln.ctypes.data
+        return s
+
+    def sessions_last_refusal(self):
+        """otr_sessions_last_refusal: {'point', 'message', 'reason'} of the last named call
+        (reason 0: it was not refused for a name)."""
+        r = _lib.SessionNameRefusal()
+        self._check(self._L.otr_sessions_last_refusal(self._h, ctypes.byref(r)), 'otr_sessions_last_refusal')
+        return {'point': int(r.point), 'message': int(r.message), 'reason': int(r.reason)}
+
+    def _check_named(self, rc, what):
+        """_check, a name refusal raising NameRefusal (a ValueError carrying point and reason)."""
+        if rc == _lib.OTR_BAD_REQUEST:
+            text = _lib.last_error()
+            r = _lib.SessionNameRefusal()
+            if self._L.otr_sessions_last_refusal(self._h, ctypes.byref(r)) == 0 and r.reason:
+                raise NameRefusal('%s refused: point %d: name %s (%s)' % (
+                    what, r.point, _lib.NAME_REASONS.get(r.reason, r.reason), text), int(r.point), int(r.reason),
+                    int(r.message))
+            raise ValueError('%s refused: %s' % (what, text))
+        self._check(rc, what)
+
+    def sessions_push(self, points, device=False, names=None):
         """otr_sessions_push: the chunk's windows and reports as a dict of numpy arrays
-        (_lib.session_result_to_numpy).  A refused chunk raises ValueError."""
+        (_lib.session_result_to_numpy).  A refused chunk raises ValueError.  names (a store with a
+        uuid directory): one name per point (_session_names); a name refusal raises NameRefusal."""
         p, r = self._session_points(points, device), _lib.SessionResult()
-        self._check(self._L.otr_sessions_push(self._h, ctypes.byref(p), ctypes.byref(r)), 'otr_sessions_push')
+        if names is not None:
+            nm = self._session_names(names, device)
+            self._check_named(self._L.otr_sessions_push_named(self._h, ctypes.byref(p), ctypes.byref(nm),
+                                                              ctypes.byref(r)), 'otr_sessions_push_named')
+        else:
+            self._check(self._L.otr_sessions_push(self._h, ctypes.byref(p), ctypes.byref(r)), 'otr_sessions_push')
         return _lib.session_result_to_numpy(r)
+
+    def sessions_names(self):
+        """otr_sessions_names: the names of the sessions of the last sessions_snapshot,
+        sessions_take or sessions_export_records, in its order, as a list of bytes."""
+        r = _lib.SessionNameList()
+        self._check(self._L.otr_sessions_names(self._h, ctypes.byref(r)), 'otr_sessions_names')
+        return _lib.names_to_list(r)
 
     # --- stream formatter (include/otr.h otr_format_messages, DESIGN.md §3 item 15) ---------
     def _message_args(self, text, fmt, msg_off, timestamp, device_ptr, nbytes):
@@ -468,8 +537,8 @@ class Matcher:
         format dict's host copies are made after the push (none with arrays=False)."""
         f, m = self._message_args(text, fmt, msg_off, timestamp, device_ptr, nbytes)
         r, s = _lib.FormatResult(), _lib.SessionResult()
-        self._check(self._L.otr_sessions_push_text(self._h, ctypes.byref(f), ctypes.byref(m), ctypes.byref(r),
-                                                   ctypes.byref(s)), 'otr_sessions_push_text')
+        self._check_named(self._L.otr_sessions_push_text(self._h, ctypes.byref(f), ctypes.byref(m), ctypes.byref(r),
+                                                         ctypes.byref(s)), 'otr_sessions_push_text')
         return _lib.format_result_to_numpy(r, arrays), _lib.session_result_to_numpy(s)
 
     def sessions_punctuate(self, ts):
@@ -477,12 +546,18 @@ class Matcher:
         self._check(self._L.otr_sessions_punctuate(self._h, int(ts), ctypes.byref(r)), 'otr_sessions_punctuate')
         return _lib.session_result_to_numpy(r)
 
-    def sessions_advance(self, points=None, device=False):
-        """otr_sessions_advance: a new chunk, or None to continue the current one.  Returns
-        (TraceBatch in HBM, windows dict); n_traces == 0: the chunk is consumed."""
+    def sessions_advance(self, points=None, device=False, names=None):
+        """otr_sessions_advance: a new chunk (with names on a store with a uuid directory), or None
+        to continue the current one.  Returns (TraceBatch in HBM, windows dict); n_traces == 0: the
+        chunk is consumed."""
         b = _lib.TraceBatch()
         p = ctypes.byref(self._session_points(points, device)) if points is not None else None
-        self._check(self._L.otr_sessions_advance(self._h, p, ctypes.byref(b)), 'otr_sessions_advance')
+        if names is not None:
+            nm = self._session_names(names, device)
+            self._check_named(self._L.otr_sessions_advance_named(self._h, p, ctypes.byref(nm), ctypes.byref(b)),
+                              'otr_sessions_advance_named')
+        else:
+            self._check(self._L.otr_sessions_advance(self._h, p, ctypes.byref(b)), 'otr_sessions_advance')
         return b, self.sessions_windows()
 
     def sessions_commit(self, shape_used, status=None):
@@ -508,12 +583,12 @@ class Matcher:
     def _restore_check(self, rc, r, what):
         if rc == _lib.OTR_BAD_REQUEST and r.bad_reason:
             where = 'session %d: ' % r.bad_session if r.bad_session >= 0 else ''
-            raise ValueError('%s refused: %s%s (%s)' % (what, where, _lib.RESTORE_REASONS.get(r.bad_reason, r.bad_reason),
+            raise ValueError('%s refused: %s%s (%s)' % (what, where, _lib.RESTORE_NAMED_REASONS.get(r.bad_reason, r.bad_reason),
                                                        _lib.last_error()))
         self._check(rc, what)
         return {k: getattr(r, k) for k in ('n_sessions', 'n_points', 'n_live', 'device_ms')}
 
-    def sessions_restore(self, snapshot, device=False):
+    def sessions_restore(self, snapshot, device=False, names=None):
         """otr_sessions_restore: the sessions of a snapshot dict (sessions_snapshot's layout)
         merged into the open store, all or nothing.  device=True: the dict holds device
         pointers plus 'n_sessions' and 'n_points'.  A refusal raises ValueError carrying the
@@ -534,11 +609,15 @@ class Matcher:
             s.n_sessions, s.n_points = ns, npt
             for (k, ct, _), a in zip(_lib.SNAPSHOT_FIELDS, keep):
                 setattr(s, k, ctypes.cast(ctypes.c_void_p(a.ctypes.data), P(ct)))
-        rc = self._L.otr_sessions_restore(self._h, ctypes.byref(s), _lib.OTR_MEM_DEVICE if device else _lib.OTR_MEM_HOST,
-                                          ctypes.byref(r))
+        mem = _lib.OTR_MEM_DEVICE if device else _lib.OTR_MEM_HOST
+        if names is not None:   # one name per session (a store with a uuid directory)
+            nm = self._session_names(names, device)
+            rc = self._L.otr_sessions_restore_named(self._h, ctypes.byref(s), ctypes.byref(nm), mem, ctypes.byref(r))
+            return self._restore_check(rc, r, 'otr_sessions_restore_named')
+        rc = self._L.otr_sessions_restore(self._h, ctypes.byref(s), mem, ctypes.byref(r))
         return self._restore_check(rc, r, 'otr_sessions_restore')
 
-    def sessions_restore_records(self, key, rec_off, data, device=False, n_records=None, n_bytes=None):
+    def sessions_restore_records(self, key, rec_off, data, device=False, n_records=None, n_bytes=None, names=None):
         """otr_sessions_restore_records: sessions as Batch.Serder's value bytes.  key: uint64 per
         record (session_key of the changelog key), rec_off: n + 1 byte offsets, data: the bytes
         (bytes or uint8 array).  device=True: the three are device addresses, with n_records and
@@ -556,6 +635,10 @@ class Matcher:
             self._keep = [k, o, d]
             c.n_records, c.n_bytes, c.memory = len(k), len(d), _lib.OTR_MEM_HOST
             c.key, c.rec_off, c.bytes = k.ctypes.data, o.ctypes.data, (d.ctypes.data if len(d) else None)
+        if names is not None:   # one name per record: its changelog key
+            nm = self._session_names(names, device)
+            rc = self._L.otr_sessions_restore_records_named(self._h, ctypes.byref(c), ctypes.byref(nm), ctypes.byref(r))
+            return self._restore_check(rc, r, 'otr_sessions_restore_records_named')
         rc = self._L.otr_sessions_restore_records(self._h, ctypes.byref(c), ctypes.byref(r))
         return self._restore_check(rc, r, 'otr_sessions_restore_records')
 

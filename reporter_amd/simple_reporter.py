@@ -377,19 +377,30 @@ def save_sessions(matcher, path):
     """The open session store's state as one .npz of (key, rec_off, bytes): every live session as
     the value Batch.Serder writes for it (Matcher.sessions_export_records).  With load_sessions
     this lets stream_text_tiles go on after a restart where the saved process stopped between two
-    chunks.  Returns the number of sessions saved."""
+    chunks.  A store with a uuid directory also saves its names (name_off, name_bytes: the
+    changelog key of record i).  Returns the number of sessions saved."""
     r = matcher.sessions_export_records()
+    extra = {}
+    if getattr(matcher, 'session_uuid_bytes', 0):
+        from . import _lib
+        data, off, ln = _lib.pack_names(matcher.sessions_names())
+        extra = {'name_off': np.concatenate([off, [len(data)]]).astype(np.int64), 'name_bytes': data}
     with open(path, 'wb') as f:
-        np.savez(f, key=r['key'], rec_off=r['rec_off'], bytes=r['bytes'])
+        np.savez(f, key=r['key'], rec_off=r['rec_off'], bytes=r['bytes'], **extra)
     return len(r['key'])
 
 
 def load_sessions(matcher, path):
     """The sessions of a save_sessions file merged into the matcher's open store
     (Matcher.sessions_restore_records: all or nothing, ValueError when refused).  Returns the
-    restore's counts."""
+    restore's counts.  A file with names goes into a store with a uuid directory, a file without
+    into a plain one (the store refuses the other pairings)."""
     with np.load(path) as z:
-        return matcher.sessions_restore_records(z['key'], z['rec_off'], z['bytes'])
+        names = None
+        if 'name_off' in z.files:
+            off = z['name_off']
+            names = {'bytes': z['name_bytes'], 'off': off[:-1], 'len': np.diff(off).astype(np.int32)}
+        return matcher.sessions_restore_records(z['key'], z['rec_off'], z['bytes'], names=names)
 
 
 def _exchange_by_file_owner(buf, itemsize, world, group=None):

@@ -36,6 +36,15 @@ existed it times the snapshot alone (the comparand in profiles/sessions_restore_
 
     python -m reporter_amd.tools.sessions_rate --traces 2000 --tile-store --out profiles/tile_store_c2dep.json
     python -m reporter_amd.tools.sessions_rate --traces 2000 --restore --out profiles/sessions_restore_c2dep.json
+
+`--names` runs the same stream through a store with the uuid directory (otr_sessions_open_named,
+uuid_bytes 36): every point carries the 36-byte name 'veh-' + its key in 32 digits (with `--text`
+the names are the uuids of the text).  It also reports `name_cost`: the stream's chunks through
+otr_sessions_advance on a store whose gates never pass (no window, so no matching), with and without
+names, HIP events on the matcher's stream around every call, summed per replay: the difference is
+the device time of the name kernels and of the names' copies.
+
+    python -m reporter_amd.tools.sessions_rate --traces 2000 --names --out profiles/session_names_c2dep.json
 """
 import argparse
 import json
@@ -110,25 +119,73 @@ def formatter_rates(m, msgs, kind, repeats):
     return out
 
 
-def replay(m, pts, cuts, max_points, batch_ms, tile_rows=0, text=None):
+NAME_BYTES = 36
+
+
+def stream_names(pts):
+    """One 36-byte name per point: 'veh-' and the key in 32 digits."""
+    from reporter_amd import _lib
+    data, off, ln = _lib.pack_names([b'veh-%032d' % k for k in pts['key'].tolist()])
+    return {'bytes': data, 'off': off, 'len': ln}
+
+
+def names_chunk(names, a, b):
+    """The names of points a .. b-1 over their own bytes."""
+    lo, hi = int(names['off'][a]), int(names['off'][b - 1]) + int(names['len'][b - 1])
+    return {'bytes': names['bytes'][lo:hi], 'off': names['off'][a:b] - lo, 'len': names['len'][a:b]}
+
+
+def name_cost(m, pts, cuts, max_points, names, repeats):
+    """The chunks through sessions_advance on a store that never reports, plain and named: the
+    summed device time (HIP events around every call) of a replay, median [min, max]."""
+    import torch
+    stream = torch.cuda.ExternalStream(m.stream)
+    chunks = [({k: v[a:b] for k, v in pts.items()}, names_chunk(names, a, b)) for a, b in zip(cuts[:-1], cuts[1:])]
+    out = {}
+    for kind in ('plain', 'named'):
+        sums = []
+        for _ in range(repeats + 1):
+            m.sessions_open(int(pts['key'].max()) + 1, max_points, report_dist=1e9, report_count=1 << 30,
+                            uuid_bytes=NAME_BYTES if kind == 'named' else 0)
+            total = 0.0
+            for c, nm in chunks:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                b, _ = m.sessions_advance(c, names=nm if kind == 'named' else None)
+                e1.record(stream)
+                e1.synchronize()
+                assert b.n_traces == 0
+                total += e0.elapsed_time(e1)
+            m.sessions_close()
+            sums.append(total)
+        v = sorted(sums[1:])
+        out[kind + '_advance_ms_median_min_max'] = [round(float(np.median(v)), 3), round(v[0], 3), round(v[-1], 3)]
+    out['names_ms'] = round(out['named_advance_ms_median_min_max'][0] - out['plain_advance_ms_median_min_max'][0], 3)
+    out['chunks'] = len(chunks)
+    return out
+
+
+def replay(m, pts, cuts, max_points, batch_ms, tile_rows=0, text=None, names=None):
     """One replay: a fresh store, every chunk pushed, a final punctuate.  tile_rows > 0: a tile
     store of that many rows takes every result (add_session) and is flushed at the end.
-    text: (kind, chunks of text_chunks): every chunk goes through sessions_push_text."""
-    m.sessions_open(int(pts['key'].max()) + 1, max_points)
+    text: (kind, chunks of text_chunks): every chunk goes through sessions_push_text.
+    names: stream_names' dict, or True with text: the store has the uuid directory."""
+    m.sessions_open(int(pts['key'].max()) + 1, max_points, uuid_bytes=NAME_BYTES if names is not None else 0)
     if tile_rows:
         m.tile_store_open(tile_rows, 3600, 2)
     add_ms = []
     chunks = text[1] if text else [{k: v[a:b] for k, v in pts.items()} for a, b in zip(cuts[:-1], cuts[1:])]
+    nchunks = None if text or names is None else [names_chunk(names, a, b) for a, b in zip(cuts[:-1], cuts[1:])]
     rounds = windows = reports = 0
     dev_ms = match_ms = parse_ms = format_ms = 0.0
     t0 = time.perf_counter()
-    for c in chunks:
+    for i, c in enumerate(chunks):
         if text:
             f, r = m.sessions_push_text(c[0], TEXT_FORMATS[text[0]], msg_off=c[1], timestamp=c[2], arrays=False)
             parse_ms += f['parse_ms']
             format_ms += f['total_ms']
         else:
-            r = m.sessions_push(c)
+            r = m.sessions_push(c, names=nchunks[i] if nchunks else None)
         rounds += r['n_rounds']
         windows += r['n_windows']
         reports += r['n_reports']
@@ -230,6 +287,8 @@ def main():
                     help='render the stream as messages and push them through otr_sessions_push_text')
     ap.add_argument('--restore', action='store_true',
                     help='time snapshot, export, take-all and the two restores on the store at the midpoint')
+    ap.add_argument('--names', action='store_true',
+                    help='the store has the uuid directory: every point is pushed with a 36-byte name')
     ap.add_argument('--graph', choices=['metro', 'city'], default='metro')
     ap.add_argument('--format-traces', type=int, default=0,
                     help='with --text: traces of the stream formatted alone (default: --traces)')
@@ -281,12 +340,15 @@ def main():
             alone = render(stream(gen.make_traces(gpath, args.format_traces, 100, 15, 10.0, 2, 0.0, 0.0, None,
                                                   t_begin=T_BEGIN, t_spread=1800)), args.text)
         res['formatter'] = formatter_rates(m, alone, args.text, max(args.repeats, 5))
+    names = (True if args.text else stream_names(pts)) if args.names else None
+    if args.names:
+        res['names'] = 'uuid directory, uuid_bytes %d' % NAME_BYTES
     for cs in args.chunk_s:
         sec = (pts['time'] - pts['time'][0]) // cs
         cuts = [0] + (np.flatnonzero(np.diff(sec)) + 1).tolist() + [n]
         text = (args.text, text_chunks(msgs, pts, cuts)) if args.text else None
-        replay(m, pts, cuts, args.max_points, batch_ms, text=text)
-        runs = [replay(m, pts, cuts, args.max_points, batch_ms, text=text) for _ in range(args.repeats)]
+        replay(m, pts, cuts, args.max_points, batch_ms, text=text, names=names)
+        runs = [replay(m, pts, cuts, args.max_points, batch_ms, text=text, names=names) for _ in range(args.repeats)]
         rate = sorted(n / r['wall_s'] for r in runs)
         r = runs[0]
         wall = float(np.median([x['wall_s'] for x in runs]))
@@ -303,9 +365,12 @@ def main():
             res['chunks']['%d_s' % cs].update(
                 format_parse_ms=round(float(np.median([x['parse_ms'] for x in runs])), 2),
                 format_total_ms=round(float(np.median([x['format_ms'] for x in runs])), 2))
+        if args.names and not args.text:
+            res['chunks']['%d_s' % cs]['name_cost'] = name_cost(m, pts, cuts, args.max_points, names, args.repeats)
         if args.tile_store:
-            replay(m, pts, cuts, args.max_points, batch_ms, args.tile_rows, text)
-            truns = [replay(m, pts, cuts, args.max_points, batch_ms, args.tile_rows, text) for _ in range(args.repeats)]
+            replay(m, pts, cuts, args.max_points, batch_ms, args.tile_rows, text, names)
+            truns = [replay(m, pts, cuts, args.max_points, batch_ms, args.tile_rows, text, names)
+                     for _ in range(args.repeats)]
             trate = sorted(n / x['wall_s'] for x in truns)
             t = truns[0]['tile']
 
