@@ -869,6 +869,50 @@ int otr_tile_store_add_rows(otr_matcher* m, const otr_tile_row* rows, int64_t n,
  * flush of an empty store returns zero files. */
 int otr_tile_store_flush(otr_matcher* m, otr_tile_flush_result* out);
 
+/* ---- tile file texts: rows in HBM to payload bytes ---------------
+ * What AnonymisingProcessor.store (AnonymisingProcessor.java:177-183) and simple_reporter.py
+ * (:188-196, 252-253) hand to S3, HTTP or a directory, written on the device: one byte buffer
+ * holding every file's text, file f at text[text_off[f] .. text_off[f+1]), and one holding the
+ * file names "{b*q}_{(b+1)*q-1}/{level}/{tile}" (q the quantisation; both products in uint64
+ * modulo 2^64, printed unsigned), name f at names[name_off[f] .. name_off[f+1]).  With H the
+ * column line segment_id,next_segment_id,duration,count,length,queue_length,minimum_timestamp,
+ * maximum_timestamp,source,vehicle_type a file's text is
+ *   OTR_TILE_RULES_STREAM: H, then per row "\n" and the fields (no trailing newline; next_id left
+ *     out when it is OTR_INVALID_SEGMENT_ID),
+ *   OTR_TILE_RULES_SIMPLE: H "\n", then per row the fields and "\n" (next_id always printed),
+ * the rows' bytes being exactly those of otr_tiles_format.  source and mode: at most 255 bytes
+ * each, null = empty; mode's ASCII a-z are upper-cased.  Host and device copies, owned by the
+ * matcher until its next tile-store, otr_tiles_text or otr_tiles_cull call. */
+typedef struct otr_tile_text_result {
+  int64_t n_rows, n_text_bytes, n_name_bytes;
+  int32_t n_files, reserved;
+  float device_ms; int32_t reserved2;  /* HIP-event time of the text stage */
+  const uint8_t* text;  const int64_t* text_off;  /* n_files + 1 */
+  const uint8_t* names; const int64_t* name_off;  /* n_files + 1 */
+  const uint64_t* file; const int64_t* row_off;   /* n_files, n_files + 1 */
+  const uint8_t* d_text;  const int64_t* d_text_off;
+  const uint8_t* d_names; const int64_t* d_name_off;
+  const uint64_t* d_file; const int64_t* d_row_off;
+} otr_tile_text_result;
+
+#define OTR_TILE_TEXT_NO_HOST 1   /* leave the host pointers null: device copies only */
+
+/* The texts of n rows (host or device memory) in which the rows of one file are adjacent, as
+ * otr_tiles_cull and the flush leave them: every run of equal `file` is one file, so a file
+ * value that recurs after another file is a second file of the same name.  n == 0: zero files,
+ * text_off = {0}.  OTR_BAD_REQUEST for quantisation < 1, unknown rules, or a source or mode
+ * longer than 255 bytes. */
+int otr_tiles_text(otr_matcher* m, const otr_tile_row* rows, int64_t n, int32_t memory, int32_t quantisation,
+                   int32_t rules, const char* source, const char* mode, int32_t flags, otr_tile_text_result* out);
+
+/* otr_tile_store_flush (same counts, same file table, the store empty afterwards), then the
+ * texts of the kept rows under OTR_TILE_RULES_STREAM and the store's quantisation, written from
+ * their device copy: flush->rows is null, no row crosses to the host.  A refusal (source or
+ * mode too long) or a failure of the text stage leaves the store as it was.  A flush of an empty
+ * store returns zero files and no text. */
+int otr_tile_store_flush_text(otr_matcher* m, const char* source, const char* mode, int32_t flags,
+                              otr_tile_flush_result* flush, otr_tile_text_result* out);
+
 /* report() (reporter_service.py:79-179) over n segment lists at once, evaluated by the
  * device code of the segment scan K7 (otr_report.h compiled for gfx950, one thread per
  * list) — what pins the device tail against the reference's own report() outputs.  Host

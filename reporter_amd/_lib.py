@@ -24,6 +24,7 @@ OTR_BAD_REQUEST = 400
 POINT_UNMATCHED, POINT_STATE, POINT_INTERPOLATED = 0, 1, 2
 OTR_TILE_RULES_SIMPLE = 0
 OTR_TILE_RULES_STREAM = 1
+OTR_TILE_TEXT_NO_HOST = 1
 OTR_INGEST_SHARD = 0
 OTR_INGEST_RAW = 1
 OTR_INGEST_JAVA_SV = 2
@@ -66,7 +67,7 @@ EXPORTS = ['otr_configure', 'otr_configure_json', 'otr_matcher_new', 'otr_matche
            'otr_sessions_restore_records', 'otr_sessions_export_records', 'otr_sessions_take', 'otr_uuid_key',
            'otr_sessions_open_named', 'otr_sessions_push_named', 'otr_sessions_advance_named',
            'otr_sessions_last_refusal', 'otr_sessions_names', 'otr_sessions_restore_named',
-           'otr_sessions_restore_records_named']
+           'otr_sessions_restore_records_named', 'otr_tiles_text', 'otr_tile_store_flush_text']
 
 
 class ServiceSplit(ctypes.Structure):
@@ -310,6 +311,20 @@ class TileFlushResult(ctypes.Structure):
                 [('d_' + k, ctypes.c_void_p) for k in TILE_FLUSH_FIELDS])
 
 
+# the arrays of otr_tile_text_result, in the struct's order
+TILE_TEXT_FIELDS = ['text', 'text_off', 'names', 'name_off', 'file', 'row_off']
+TILE_TEXT_COUNTS = ['n_rows', 'n_text_bytes', 'n_name_bytes', 'n_files']
+
+
+class TileTextResult(ctypes.Structure):
+    """otr_tile_text_result (include/otr.h): the files' texts and names, host and device arrays."""
+    _fields_ = ([('n_rows', ctypes.c_int64), ('n_text_bytes', ctypes.c_int64), ('n_name_bytes', ctypes.c_int64),
+                 ('n_files', ctypes.c_int32), ('reserved', ctypes.c_int32), ('device_ms', ctypes.c_float),
+                 ('reserved2', ctypes.c_int32)] +
+                [(k, ctypes.c_void_p) for k in TILE_TEXT_FIELDS] +
+                [('d_' + k, ctypes.c_void_p) for k in TILE_TEXT_FIELDS])
+
+
 def _copy(ptr, n, dt):
     """n records of dtype dt at the host address ptr, copied."""
     if n <= 0 or not ptr:
@@ -333,6 +348,32 @@ def tile_flush_to_numpy(r):
     out['row_off'] = _copy(r.row_off, nf + 1, np.int64)
     out['n_unclean'] = _copy(r.n_unclean, nf, np.int64)
     for k in TILE_FLUSH_FIELDS:
+        out['d_' + k] = int(getattr(r, 'd_' + k) or 0)
+    return out
+
+
+def _bytes(ptr, n):
+    """n bytes at the host address ptr as a numpy uint8 array (one copy, also beyond 2 GiB)."""
+    out = np.empty(max(n, 0), np.uint8)
+    if n > 0 and ptr:
+        ctypes.memmove(out.ctypes.data, ptr, n)
+    return out
+
+
+def tile_text_to_numpy(r, host=True):
+    """An otr_tile_text_result: its counts, device_ms and device pointers d_*, and with host=True
+    copies of text and names (uint8), text_off, name_off, row_off (int64) and file (uint64)."""
+    nf = int(r.n_files)
+    out = {k: int(getattr(r, k)) for k in TILE_TEXT_COUNTS}
+    out['device_ms'] = float(r.device_ms)
+    if host:
+        out['text'] = _bytes(r.text, int(r.n_text_bytes))
+        out['names'] = _bytes(r.names, int(r.n_name_bytes))
+        out['text_off'] = _copy(r.text_off, nf + 1, np.int64)
+        out['name_off'] = _copy(r.name_off, nf + 1, np.int64)
+        out['row_off'] = _copy(r.row_off, nf + 1, np.int64)
+        out['file'] = _copy(r.file, nf, np.uint64)
+    for k in TILE_TEXT_FIELDS:
         out['d_' + k] = int(getattr(r, 'd_' + k) or 0)
     return out
 
@@ -508,6 +549,12 @@ def lib():
         L.otr_tile_store_add_rows.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                               P(TileAddResult)]
         L.otr_tile_store_flush.argtypes = [ctypes.c_void_p, P(TileFlushResult)]
+    if hasattr(L, 'otr_tiles_text'):
+        L.otr_tiles_text.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                     ctypes.c_int32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32,
+                                     P(TileTextResult)]
+        L.otr_tile_store_flush_text.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32,
+                                                P(TileFlushResult), P(TileTextResult)]
     if hasattr(L, 'otr_format_messages'):
         L.otr_format_messages.argtypes = [ctypes.c_void_p, P(MessageFormat), P(Messages), P(FormatResult)]
         L.otr_sessions_push_text.argtypes = [ctypes.c_void_p, P(MessageFormat), P(Messages), P(FormatResult),

@@ -186,6 +186,20 @@ def build_namecheck(force=False, sanitize=False, out=None):
     return exe
 
 
+def build_tiletextcheck(force=False, sanitize=False, out=None):
+    """tools/tiletextcheck: the tile file texts' per-row and per-file rules as a stand-alone host
+    program (CPU tests only).  sanitize=True: built with AddressSanitizer and
+    UndefinedBehaviorSanitizer (any report is fatal), to `out` or tools/tiletextcheck_san."""
+    src = os.path.join(PKG, 'tools', 'tiletextcheck.cpp')
+    exe = out or os.path.join(PKG, 'tools', 'tiletextcheck_san' if sanitize else 'tiletextcheck')
+    deps = [src, os.path.join(CSRC, 'otr_tiletext.h'), os.path.join(ROOT, 'include', 'otr.h')]
+    if force or not _newer(exe, deps):
+        flags = ['-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
+                 '-fno-omit-frame-pointer'] if sanitize else ['-O2']
+        _run(['g++', '-std=c++17', '-Wall'] + flags + ['-o', exe, src])
+    return exe
+
+
 def build_mincheck(force=False):
     """tools/libmincheck.so: host build of the node tables' IN-gap codes (CPU tests only)."""
     src = os.path.join(PKG, 'tools', 'mincheck.cpp')
@@ -206,6 +220,7 @@ def build_all(force=False):
     build_mincheck(force)
     build_recordcheck(force)
     build_namecheck(force)
+    build_tiletextcheck(force)
     build_oracle(force)
     build_calib(force)
     with ThreadPoolExecutor(max_workers=3) as ex:

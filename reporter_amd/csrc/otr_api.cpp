@@ -610,6 +610,18 @@ int otr_tile_store_flush(otr_matcher* m, otr_tile_flush_result* out) {
   OTR_SESSIONS_CALL(!m || !out, tile_store_flush(out, &err));
 }
 
+// tile file texts (K19): AnonymisingProcessor.store's payloads (AnonymisingProcessor.java:177-183)
+int otr_tiles_text(otr_matcher* m, const otr_tile_row* rows, int64_t n, int32_t memory, int32_t quantisation,
+                   int32_t rules, const char* source, const char* mode, int32_t flags, otr_tile_text_result* out) {
+  OTR_SESSIONS_CALL(!m || !out || (n > 0 && !rows),
+                    tiles_text(rows, n, memory, quantisation, rules, source, mode, flags, out, &err));
+}
+
+int otr_tile_store_flush_text(otr_matcher* m, const char* source, const char* mode, int32_t flags,
+                              otr_tile_flush_result* flush, otr_tile_text_result* out) {
+  OTR_SESSIONS_CALL(!m || !flush || !out, tile_store_flush_text(source, mode, flags, flush, out, &err));
+}
+
 // simple_reporter.py:188-195: ','.join([id, next, duration, '1', length, queue, start, end,
 // source, mode.upper()]) + os.linesep
 // Segment.appendToStringBuffer (Segment.java:59-74) for OTR_TILE_RULES_STREAM

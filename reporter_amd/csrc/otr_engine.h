@@ -101,6 +101,9 @@ bool sessions_last_reports(SessionStore* s, SessionReports* out);  // false: no 
 struct TileStore;                      // otr_tilestore.hip (K15)
 void tile_store_destroy(TileStore* s);  // frees the store's device memory
 
+struct TileText;                      // otr_tilestore.hip (K19): the buffers of the file texts
+void tile_text_destroy(TileText* t);  // frees them
+
 // what cull_device leaves in the matcher's cull slots
 struct CulledRows {
   const otr_tile_row* sorted;  // all n rows in file, then rule order
@@ -113,6 +116,7 @@ struct Matcher {
   hipStream_t stream = nullptr;
   SessionStore* ses = nullptr;  // the session store (otr_sessions_open), owned
   TileStore* tst = nullptr;     // the tile store (otr_tile_store_open), owned
+  TileText* ttx = nullptr;      // the file texts of the last otr_tiles_text / flush_text, owned
   std::vector<DevBuf> bufs;
   GSlab gslab[2];
   std::vector<int32_t> h_turn;
@@ -225,6 +229,11 @@ struct Matcher {
                              int memory, otr_tile_add_result* out, std::string* err);
   int tile_store_add_rows(const otr_tile_row* rows, int64_t n, int memory, otr_tile_add_result* out, std::string* err);
   int tile_store_flush(otr_tile_flush_result* out, std::string* err);
+  // tile file texts (K19, otr_tiletext.h; otr_tilestore.hip)
+  int tiles_text(const otr_tile_row* rows, int64_t n, int memory, int quantisation, int rules, const char* source,
+                 const char* mode, int flags, otr_tile_text_result* out, std::string* err);
+  int tile_store_flush_text(const char* source, const char* mode, int flags, otr_tile_flush_result* flush,
+                            otr_tile_text_result* out, std::string* err);
   ~Matcher();
 };
 

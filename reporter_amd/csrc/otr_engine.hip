@@ -530,6 +530,7 @@ static int oom_error(hipStream_t stream, const DeviceOom& o, std::string* err) {
 Matcher::~Matcher() {
   if (ses) sessions_destroy(ses);
   if (tst) tile_store_destroy(tst);
+  if (ttx) tile_text_destroy(ttx);
   for (auto& b : bufs)
     if (b.p) (void)hipFree(b.p);
   for (auto& sl : gslab)

@@ -1,16 +1,20 @@
 // otr_tilestore.hip — host side of the tile store (K15, otr_tilestore.h): the store's row
 // buffer, the two passes of an add (count, scan, capacity check, write) and the flush (the
-// matcher's device cull, then the per-file table).  include/otr.h otr_tile_store_* for the rules.
+// matcher's device cull, then the per-file table), and of the tile file texts (K19,
+// otr_tiletext.h): lengths, scans, one emit pass.  include/otr.h otr_tile_store_* and
+// otr_tiles_text for the rules.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "otr_engine.h"
 #include "otr_tilestore.h"
+#include "otr_tiletext.h"
 
 #define HIPCHK(x)                                                                        \
   do {                                                                                   \
@@ -34,36 +38,33 @@ unsigned tst_grid(int64_t n, int threads) { return (unsigned)std::max<int64_t>(1
 
 constexpr int64_t kTstMaxRows = (int64_t)1 << 27;
 
-// growable buffers of an add and of a flush's file table (the rows are not among them)
+// growable buffers of an add, of a flush's file table (the rows are not among them) and of
+// the file texts
 enum TstBuf {
   T_OFF, T_ID, T_NEXT, T_T0, T_T1, T_LEN, T_QUEUE, T_KEY_A, T_KEY_B, T_IDX_A, T_IDX_B, T_CNT, T_ROW_OFF, T_TMP,
   T_F_HEAD, T_F_INCL, T_F_START, T_F_LISTED, T_F_LINCL, T_F_FILE, T_F_ROW_OFF, T_F_UNCLEAN,
+  T_X_ROWS, T_X_TAG, T_X_LEN, T_X_OFF, T_X_TEXT_OFF, T_X_NAME_LEN, T_X_NAME_OFF, T_X_TEXT, T_X_NAMES,
   T_NUM
 };
 const char* const kTstName[T_NUM] = {
     "report offsets", "report id", "report next id", "report t0", "report t1", "report length", "report queue length",
     "window order key", "sorted window order key", "window index", "window order", "window row counts",
     "window row offsets", "scan / sort workspace", "file head", "file rank", "file start", "file listed",
-    "listed file rank", "file table files", "file table row offsets", "file table unclean counts"};
+    "listed file rank", "file table files", "file table row offsets", "file table unclean counts",
+    "text rows", "text tag", "text row lengths", "text row offsets", "file text offsets", "file name lengths",
+    "file name offsets", "file texts", "file names"};
 
 }  // namespace
 
-struct TileStore {
-  otr_tile_store_config cfg{};
+// the growable buffers, the stream they are used on and a pair of events
+struct TstBufs {
   hipStream_t stream = nullptr;
-  otr_tile_row* rows = nullptr;  // [max_rows], the store's own allocation
-  unsigned long long* counters = nullptr;
-  int64_t n_rows = 0;
   hipEvent_t ev[2];
   bool ev_init = false;
   struct {
     void* p = nullptr;
     size_t bytes = 0;
   } b[T_NUM];
-  // what a flush returns
-  std::vector<otr_tile_row> h_rows;
-  std::vector<unsigned long long> h_file;
-  std::vector<int64_t> h_row_off, h_unclean;
 
   template <class T>
   T* buf(int slot, size_t n) {
@@ -84,25 +85,70 @@ struct TileStore {
   }
 
   int scan64(const int64_t* in, int64_t* out, int64_t n, std::string* err);
+  int events(std::string* err) {
+    if (ev_init) return OTR_OK;
+    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+    ev_init = true;
+    return OTR_OK;
+  }
+  int finish(float* device_ms, std::string* err);
+  void release() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (auto& x : b)
+      if (x.p) (void)hipFree(x.p);
+    if (ev_init)
+      for (auto& e : ev) (void)hipEventDestroy(e);
+  }
+};
+
+// The file texts of the last otr_tiles_text / otr_tile_store_flush_text (K19): device buffers
+// and the host copies the result points to.
+struct TileText : TstBufs {
+  std::vector<uint8_t> h_tag;
+  std::unique_ptr<uint8_t[]> h_text;  // grown, never zero-filled
+  size_t h_text_cap = 0;
+  std::vector<uint8_t> h_names;
+  std::vector<int64_t> h_text_off, h_name_off, h_row_off;
+  std::vector<unsigned long long> h_file;
+
+  int table(const otr_tile_row* d_rows, int64_t n, const unsigned long long** d_file, const int64_t** d_row_off,
+            int64_t* n_files, std::string* err);
+  int write(const otr_tile_row* d_rows, int64_t n, const unsigned long long* d_file, const int64_t* d_row_off,
+            int64_t n_files, int64_t quantisation, int rules, int flags, otr_tile_text_result* out, std::string* err);
+};
+
+void tile_text_destroy(TileText* t) {
+  if (!t) return;
+  t->release();
+  delete t;
+}
+
+struct TileStore : TstBufs {
+  otr_tile_store_config cfg{};
+  otr_tile_row* rows = nullptr;  // [max_rows], the store's own allocation
+  unsigned long long* counters = nullptr;
+  int64_t n_rows = 0;
+  // what a flush returns
+  std::vector<otr_tile_row> h_rows;
+  std::vector<unsigned long long> h_file;
+  std::vector<int64_t> h_row_off, h_unclean;
+
   int alloc(std::string* err);
   int add(const StoreArgs& in, int64_t n_reports, otr_tile_add_result* out, std::string* err);
   void add_result(otr_tile_add_result* out, int64_t n_reports, int64_t n_valid, int64_t added) const;
-  int finish(float* device_ms, std::string* err);
+  int flush(Matcher& m, TileText* text, int flags, otr_tile_flush_result* out, otr_tile_text_result* text_out,
+            std::string* err);
 };
 
 void tile_store_destroy(TileStore* s) {
   if (!s) return;
-  if (s->stream) (void)hipStreamSynchronize(s->stream);
+  s->release();
   if (s->rows) (void)hipFree(s->rows);
   if (s->counters) (void)hipFree(s->counters);
-  for (auto& x : s->b)
-    if (x.p) (void)hipFree(x.p);
-  if (s->ev_init)
-    for (auto& e : s->ev) (void)hipEventDestroy(e);
   delete s;
 }
 
-int TileStore::scan64(const int64_t* in, int64_t* out, int64_t n, std::string* err) {
+int TstBufs::scan64(const int64_t* in, int64_t* out, int64_t n, std::string* err) {
   size_t tb = 0;
   HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, in, out, (int)n, stream));
   void* tmp = buf<char>(T_TMP, tb);
@@ -122,9 +168,7 @@ int TileStore::alloc(std::string* err) {
     counters = nullptr;
     throw TstOom{"tile store counters", 8 * TST_WORDS};
   }
-  for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-  ev_init = true;
-  return OTR_OK;
+  return events(err);
 }
 
 void TileStore::add_result(otr_tile_add_result* out, int64_t n_reports, int64_t n_valid, int64_t added) const {
@@ -136,7 +180,7 @@ void TileStore::add_result(otr_tile_add_result* out, int64_t n_reports, int64_t 
 }
 
 // ev[0] was recorded at the call's start
-int TileStore::finish(float* device_ms, std::string* err) {
+int TstBufs::finish(float* device_ms, std::string* err) {
   HIPCHK(hipEventRecord(ev[1], stream));
   HIPCHK(hipStreamSynchronize(stream));
   HIPCHK(hipEventElapsedTime(device_ms, ev[0], ev[1]));
@@ -377,88 +421,289 @@ int Matcher::tile_store_add_rows(const otr_tile_row* rows, int64_t n, int memory
   });
 }
 
+// The flush.  text non-null (otr_tile_store_flush_text): the kept rows stay in HBM and their
+// file texts are written there; the store is emptied only once that has succeeded.
+int TileStore::flush(Matcher& m, TileText* text, int flags, otr_tile_flush_result* out,
+                     otr_tile_text_result* text_out, std::string* err) {
+  TileStore& s = *this;
+  int rc;
+  memset(out, 0, sizeof(*out));
+  const int64_t n = s.n_rows;
+  s.h_rows.clear();
+  s.h_file.clear();
+  s.h_unclean.clear();
+  s.h_row_off.assign(1, 0);
+  int64_t* d_row_off = s.buf<int64_t>(T_F_ROW_OFF, 1);
+  out->row_off = s.h_row_off.data();
+  if (n == 0) {
+    HIPCHK(hipMemsetAsync(d_row_off, 0, 8, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    out->d_row_off = d_row_off;
+    if (text) return text->write(nullptr, 0, nullptr, d_row_off, 0, cfg.quantisation, OTR_TILE_RULES_STREAM, flags,
+                                 text_out, err);
+    return OTR_OK;
+  }
+  HIPCHK(hipEventRecord(s.ev[0], stream));
+  CulledRows c;
+  if ((rc = m.cull_device(s.rows, n, s.cfg.privacy, OTR_TILE_RULES_STREAM, &c, err))) return rc;
+  // the files of the sorted rows, and which of them kept rows
+  const unsigned g = tst_grid(n, 256);
+  int64_t* head = s.buf<int64_t>(T_F_HEAD, n);
+  int64_t* head_incl = s.buf<int64_t>(T_F_INCL, n);
+  k_store_file_heads<<<g, 256, 0, stream>>>(c.sorted, n, head);
+  if ((rc = s.scan64(head, head_incl, n, err))) return rc;
+  int64_t nf = 0;
+  HIPCHK(hipMemcpyAsync(&nf, head_incl + (n - 1), 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (nf < 1 || nf > n) {
+    if (err) *err = "tile store file split failed";
+    return OTR_DEVICE_ERROR;
+  }
+  int64_t* start = s.buf<int64_t>(T_F_START, nf);
+  int64_t* listed = s.buf<int64_t>(T_F_LISTED, nf);
+  int64_t* listed_incl = s.buf<int64_t>(T_F_LINCL, nf);
+  k_store_file_starts<<<g, 256, 0, stream>>>(head, head_incl, n, start);
+  const unsigned gf = tst_grid(nf, 256);
+  k_store_file_listed<<<gf, 256, 0, stream>>>(start, nf, n, c.kept_incl, listed);
+  if ((rc = s.scan64(listed, listed_incl, nf, err))) return rc;
+  int64_t nl = 0;
+  HIPCHK(hipMemcpyAsync(&nl, listed_incl + (nf - 1), 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (nl < 0 || nl > nf || nl > c.n_kept || (nl == 0) != (c.n_kept == 0)) {
+    if (err) *err = "tile store file table failed";
+    return OTR_DEVICE_ERROR;
+  }
+  unsigned long long* d_file = s.buf<unsigned long long>(T_F_FILE, nl);
+  d_row_off = s.buf<int64_t>(T_F_ROW_OFF, (size_t)nl + 1);
+  int64_t* d_unclean = s.buf<int64_t>(T_F_UNCLEAN, nl);
+  k_store_file_table<<<gf, 256, 0, stream>>>(c.sorted, start, nf, n, c.kept_incl, listed, listed_incl, d_file,
+                                             d_row_off, d_unclean);
+  HIPCHK(hipGetLastError());
+  if (!text) s.h_rows.resize((size_t)c.n_kept);
+  s.h_file.resize((size_t)nl);
+  s.h_unclean.resize((size_t)nl);
+  s.h_row_off.resize((size_t)nl + 1);
+  if (!text && c.n_kept > 0)
+    HIPCHK(hipMemcpyAsync(s.h_rows.data(), c.kept, sizeof(otr_tile_row) * (size_t)c.n_kept, hipMemcpyDeviceToHost,
+                          stream));
+  if (nl > 0) {
+    HIPCHK(hipMemcpyAsync(s.h_file.data(), d_file, 8 * (size_t)nl, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(s.h_unclean.data(), d_unclean, 8 * (size_t)nl, hipMemcpyDeviceToHost, stream));
+  }
+  HIPCHK(hipMemcpyAsync(s.h_row_off.data(), d_row_off, 8 * ((size_t)nl + 1), hipMemcpyDeviceToHost, stream));
+  if ((rc = s.finish(&out->device_ms, err))) return rc;
+  // (the kept rows of one listed file are adjacent and two listed files differ in `file`: the
+  // text stage's file heads fall on d_row_off)
+  if (text && (rc = text->write(c.kept, c.n_kept, d_file, d_row_off, nl, cfg.quantisation, OTR_TILE_RULES_STREAM,
+                                flags, text_out, err)))
+    return rc;
+  s.n_rows = 0;  // the sorted and the kept rows are copies: the buffer is free again
+  out->n_rows_in = n;
+  out->n_rows = c.n_kept;
+  out->n_files = (int32_t)nl;
+  out->n_files_empty = (int32_t)(nf - nl);
+  out->rows = s.h_rows.empty() ? nullptr : s.h_rows.data();
+  out->file = s.h_file.empty() ? nullptr : (const uint64_t*)s.h_file.data();
+  out->row_off = s.h_row_off.data();
+  out->n_unclean = s.h_unclean.empty() ? nullptr : s.h_unclean.data();
+  out->d_rows = c.kept;
+  out->d_file = (const uint64_t*)d_file;
+  out->d_row_off = d_row_off;
+  out->d_n_unclean = d_unclean;
+  return OTR_OK;
+}
+
 int Matcher::tile_store_flush(otr_tile_flush_result* out, std::string* err) {
   return guarded(*this, err, true, [&]() -> int {
-    TileStore& s = *tst;
-    int rc;
-    memset(out, 0, sizeof(*out));
     HIPCHK(hipSetDevice(graph_state().device));
-    const int64_t n = s.n_rows;
-    s.h_rows.clear();
-    s.h_file.clear();
-    s.h_unclean.clear();
-    s.h_row_off.assign(1, 0);
-    int64_t* d_row_off = s.buf<int64_t>(T_F_ROW_OFF, 1);
-    out->row_off = s.h_row_off.data();
-    if (n == 0) {
-      HIPCHK(hipMemsetAsync(d_row_off, 0, 8, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      out->d_row_off = d_row_off;
-      return OTR_OK;
-    }
-    HIPCHK(hipEventRecord(s.ev[0], stream));
-    CulledRows c;
-    if ((rc = cull_device(s.rows, n, s.cfg.privacy, OTR_TILE_RULES_STREAM, &c, err))) return rc;
-    // the files of the sorted rows, and which of them kept rows
-    const unsigned g = tst_grid(n, 256);
-    int64_t* head = s.buf<int64_t>(T_F_HEAD, n);
-    int64_t* head_incl = s.buf<int64_t>(T_F_INCL, n);
-    k_store_file_heads<<<g, 256, 0, stream>>>(c.sorted, n, head);
-    if ((rc = s.scan64(head, head_incl, n, err))) return rc;
-    int64_t nf = 0;
-    HIPCHK(hipMemcpyAsync(&nf, head_incl + (n - 1), 8, hipMemcpyDeviceToHost, stream));
+    return tst->flush(*this, nullptr, 0, out, nullptr, err);
+  });
+}
+
+// ---- tile file texts (K19) ---------------------------------------------------------------
+
+// The file table of n > 0 rows that come without one: every run of equal `file` is a file.
+int TileText::table(const otr_tile_row* d_rows, int64_t n, const unsigned long long** d_file,
+                    const int64_t** d_row_off, int64_t* n_files, std::string* err) {
+  int rc;
+  const unsigned g = tst_grid(n, 256);
+  int64_t* head = buf<int64_t>(T_F_HEAD, n);
+  int64_t* head_incl = buf<int64_t>(T_F_INCL, n);
+  k_store_file_heads<<<g, 256, 0, stream>>>(d_rows, n, head);
+  if ((rc = scan64(head, head_incl, n, err))) return rc;
+  int64_t nf = 0;
+  HIPCHK(hipMemcpyAsync(&nf, head_incl + (n - 1), 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (nf < 1 || nf > n || nf >= (int64_t)INT32_MAX) {
+    if (err) *err = "tile text file split failed";
+    return OTR_DEVICE_ERROR;
+  }
+  int64_t* start = buf<int64_t>(T_F_START, nf);
+  unsigned long long* file = buf<unsigned long long>(T_F_FILE, nf);
+  int64_t* row_off = buf<int64_t>(T_F_ROW_OFF, (size_t)nf + 1);
+  k_store_file_starts<<<g, 256, 0, stream>>>(head, head_incl, n, start);
+  k_tile_text_table<<<tst_grid(nf + 1, 256), 256, 0, stream>>>(d_rows, start, nf, n, file, row_off);
+  HIPCHK(hipGetLastError());
+  *d_file = file;
+  *d_row_off = row_off;
+  *n_files = nf;
+  return OTR_OK;
+}
+
+// The texts and names of n rows in HBM whose file table is (d_file, d_row_off, n_files), all
+// on the device; h_tag holds the call's tag.  Lengths, two scans, one synchronise for the two
+// totals, then the emit pass and the names.
+int TileText::write(const otr_tile_row* d_rows, int64_t n, const unsigned long long* d_file,
+                    const int64_t* d_row_off, int64_t n_files, int64_t quantisation, int rules, int flags,
+                    otr_tile_text_result* out, std::string* err) {
+  int rc;
+  memset(out, 0, sizeof(*out));
+  if ((rc = events(err))) return rc;
+  HIPCHK(hipEventRecord(ev[0], stream));
+  const int64_t nf = n_files;
+  const int32_t tag_len = (int32_t)h_tag.size();
+  int64_t* off = buf<int64_t>(T_X_OFF, (size_t)n + 1);
+  int64_t* text_off = buf<int64_t>(T_X_TEXT_OFF, (size_t)nf + 1);
+  int64_t* name_off = buf<int64_t>(T_X_NAME_OFF, (size_t)nf + 1);
+  uint8_t* tag = buf<uint8_t>(T_X_TAG, kTileTextTagMax);
+  HIPCHK(hipMemsetAsync(off, 0, 8, stream));
+  HIPCHK(hipMemsetAsync(text_off, 0, 8, stream));
+  HIPCHK(hipMemsetAsync(name_off, 0, 8, stream));
+  int64_t total[2] = {0, 0};  // text bytes, name bytes
+  if (n > 0) {
+    int64_t* len = buf<int64_t>(T_X_LEN, n);
+    int64_t* name_len = buf<int64_t>(T_X_NAME_LEN, nf);
+    HIPCHK(hipMemcpyAsync(tag, h_tag.data(), (size_t)tag_len, hipMemcpyHostToDevice, stream));
+    k_tile_text_len<<<tst_grid(n, 256), 256, 0, stream>>>(d_rows, n, rules, tag_len, len);
+    if ((rc = scan64(len, off + 1, n, err))) return rc;
+    k_tile_text_files<<<tst_grid(nf + 1, 256), 256, 0, stream>>>(d_file, d_row_off, off, nf, quantisation, text_off,
+                                                                 name_len);
+    if ((rc = scan64(name_len, name_off + 1, nf, err))) return rc;
+    HIPCHK(hipMemcpyAsync(&total[0], off + n, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&total[1], name_off + nf, 8, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
-    if (nf < 1 || nf > n) {
-      if (err) *err = "tile store file split failed";
+    // (a row is at least 17 bytes and at most 122 + the tag, a name 8 to 20 + 1 + 20 + 1 + 1 + 1 + 7)
+    if (total[0] < 17 * n || total[0] > n * (int64_t)(122 + kTileTextTagMax + kTileTextHeader + 1) || total[1] < 8 * nf ||
+        total[1] > 51 * nf) {
+      if (err) *err = "tile text lengths failed";
       return OTR_DEVICE_ERROR;
     }
-    int64_t* start = s.buf<int64_t>(T_F_START, nf);
-    int64_t* listed = s.buf<int64_t>(T_F_LISTED, nf);
-    int64_t* listed_incl = s.buf<int64_t>(T_F_LINCL, nf);
-    k_store_file_starts<<<g, 256, 0, stream>>>(head, head_incl, n, start);
-    const unsigned gf = tst_grid(nf, 256);
-    k_store_file_listed<<<gf, 256, 0, stream>>>(start, nf, n, c.kept_incl, listed);
-    if ((rc = s.scan64(listed, listed_incl, nf, err))) return rc;
-    int64_t nl = 0;
-    HIPCHK(hipMemcpyAsync(&nl, listed_incl + (nf - 1), 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    if (nl < 0 || nl > nf || nl > c.n_kept || (nl == 0) != (c.n_kept == 0)) {
-      if (err) *err = "tile store file table failed";
-      return OTR_DEVICE_ERROR;
-    }
-    unsigned long long* d_file = s.buf<unsigned long long>(T_F_FILE, nl);
-    d_row_off = s.buf<int64_t>(T_F_ROW_OFF, (size_t)nl + 1);
-    int64_t* d_unclean = s.buf<int64_t>(T_F_UNCLEAN, nl);
-    k_store_file_table<<<gf, 256, 0, stream>>>(c.sorted, start, nf, n, c.kept_incl, listed, listed_incl, d_file,
-                                               d_row_off, d_unclean);
+  }
+  uint8_t* text = buf<uint8_t>(T_X_TEXT, (size_t)total[0]);
+  uint8_t* names = buf<uint8_t>(T_X_NAMES, (size_t)total[1]);
+  if (n > 0) {
+    k_tile_text_emit<<<tst_grid(n, kTtRows), kTtRows, kTtLds, stream>>>(d_rows, n, rules, tag, tag_len, off, text);
+    k_tile_text_names<<<tst_grid(nf, 256), 256, 0, stream>>>(d_file, name_off, nf, quantisation, names);
     HIPCHK(hipGetLastError());
-    s.h_rows.resize((size_t)c.n_kept);
-    s.h_file.resize((size_t)nl);
-    s.h_unclean.resize((size_t)nl);
-    s.h_row_off.resize((size_t)nl + 1);
-    if (c.n_kept > 0)
-      HIPCHK(hipMemcpyAsync(s.h_rows.data(), c.kept, sizeof(otr_tile_row) * (size_t)c.n_kept, hipMemcpyDeviceToHost,
-                            stream));
-    if (nl > 0) {
-      HIPCHK(hipMemcpyAsync(s.h_file.data(), d_file, 8 * (size_t)nl, hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipMemcpyAsync(s.h_unclean.data(), d_unclean, 8 * (size_t)nl, hipMemcpyDeviceToHost, stream));
+  }
+  const bool host = !(flags & OTR_TILE_TEXT_NO_HOST);
+  if (host) {
+    if (h_text_cap < (size_t)total[0] || !h_text) {
+      h_text_cap = (size_t)total[0] + (size_t)total[0] / 4 + 16;
+      h_text.reset();
+      h_text.reset(new uint8_t[h_text_cap]);
     }
-    HIPCHK(hipMemcpyAsync(s.h_row_off.data(), d_row_off, 8 * ((size_t)nl + 1), hipMemcpyDeviceToHost, stream));
-    if ((rc = s.finish(&out->device_ms, err))) return rc;
-    s.n_rows = 0;  // the sorted and the kept rows are copies: the buffer is free again
-    out->n_rows_in = n;
-    out->n_rows = c.n_kept;
-    out->n_files = (int32_t)nl;
-    out->n_files_empty = (int32_t)(nf - nl);
-    out->rows = s.h_rows.empty() ? nullptr : s.h_rows.data();
-    out->file = s.h_file.empty() ? nullptr : (const uint64_t*)s.h_file.data();
-    out->row_off = s.h_row_off.data();
-    out->n_unclean = s.h_unclean.empty() ? nullptr : s.h_unclean.data();
-    out->d_rows = c.kept;
-    out->d_file = (const uint64_t*)d_file;
-    out->d_row_off = d_row_off;
-    out->d_n_unclean = d_unclean;
-    return OTR_OK;
+    h_names.resize((size_t)total[1] + 1);
+    h_text_off.resize((size_t)nf + 1);
+    h_name_off.resize((size_t)nf + 1);
+    h_row_off.resize((size_t)nf + 1);
+    h_file.resize((size_t)nf + 1);
+    if (total[0] > 0) HIPCHK(hipMemcpyAsync(h_text.get(), text, (size_t)total[0], hipMemcpyDeviceToHost, stream));
+    if (total[1] > 0) HIPCHK(hipMemcpyAsync(h_names.data(), names, (size_t)total[1], hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(h_text_off.data(), text_off, 8 * ((size_t)nf + 1), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(h_name_off.data(), name_off, 8 * ((size_t)nf + 1), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(h_row_off.data(), d_row_off, 8 * ((size_t)nf + 1), hipMemcpyDeviceToHost, stream));
+    if (nf > 0) HIPCHK(hipMemcpyAsync(h_file.data(), d_file, 8 * (size_t)nf, hipMemcpyDeviceToHost, stream));
+  }
+  if ((rc = finish(&out->device_ms, err))) return rc;
+  out->n_rows = n;
+  out->n_text_bytes = total[0];
+  out->n_name_bytes = total[1];
+  out->n_files = (int32_t)nf;
+  if (host) {
+    out->text = h_text.get();
+    out->text_off = h_text_off.data();
+    out->names = h_names.data();
+    out->name_off = h_name_off.data();
+    out->file = (const uint64_t*)h_file.data();
+    out->row_off = h_row_off.data();
+  }
+  out->d_text = text;
+  out->d_text_off = text_off;
+  out->d_names = names;
+  out->d_name_off = name_off;
+  out->d_file = (const uint64_t*)d_file;
+  out->d_row_off = d_row_off;
+  return OTR_OK;
+}
+
+namespace {
+
+// the call's tag into t.h_tag; false: source or mode longer than 255 bytes
+bool text_tag(std::vector<uint8_t>* tag, const char* source, const char* mode, int rules) {
+  const char* src = source ? source : "";
+  const char* md = mode ? mode : "";
+  const size_t ls = strnlen(src, kTileTextTagPart + 1), lm = strnlen(md, kTileTextTagPart + 1);
+  if (ls > (size_t)kTileTextTagPart || lm > (size_t)kTileTextTagPart) return false;
+  tag->resize(kTileTextTagMax);
+  tag->resize((size_t)tile_text_tag_put((const uint8_t*)src, (int32_t)ls, (const uint8_t*)md, (int32_t)lm, rules,
+                                        tag->data()));
+  return true;
+}
+
+// the matcher's text state, created at its first use (the device and the stream are set)
+int text_state(Matcher& m, std::string* err) {
+  HIPCHK(hipSetDevice(graph_state().device));
+  if (!m.stream) HIPCHK(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
+  if (!m.ttx) m.ttx = new TileText();
+  m.ttx->stream = m.stream;
+  return OTR_OK;
+}
+
+const char* const kTagTooLong = "tile text: source and mode take at most 255 bytes each";
+
+}  // namespace
+
+int Matcher::tiles_text(const otr_tile_row* rows, int64_t n, int memory, int quantisation, int rules,
+                        const char* source, const char* mode, int flags, otr_tile_text_result* out,
+                        std::string* err) {
+  std::vector<uint8_t> tag;
+  if (quantisation < 1) return bad(err, "tile text: quantisation below 1");
+  if (!tile_text_rules_ok(rules)) return bad(err, "tile text: unknown rules " + std::to_string(rules));
+  if (!text_tag(&tag, source, mode, rules)) return bad(err, kTagTooLong);
+  if (n < 0 || n >= (int64_t)INT32_MAX) return bad(err, "tile text: row count out of range");
+  return guarded(*this, err, false, [&]() -> int {
+    int rc;
+    if ((rc = text_state(*this, err))) return rc;
+    TileText& t = *ttx;
+    t.h_tag = tag;
+    const otr_tile_row* d_rows = rows;
+    const unsigned long long* d_file = nullptr;
+    const int64_t* d_row_off = t.buf<int64_t>(T_F_ROW_OFF, 1);
+    int64_t nf = 0;
+    if (n > 0) {
+      if (memory != OTR_MEM_DEVICE) {
+        otr_tile_row* d = t.buf<otr_tile_row>(T_X_ROWS, n);
+        HIPCHK(hipMemcpyAsync(d, rows, sizeof(otr_tile_row) * (size_t)n, hipMemcpyHostToDevice, stream));
+        d_rows = d;
+      }
+      if ((rc = t.table(d_rows, n, &d_file, &d_row_off, &nf, err))) return rc;
+    } else {
+      HIPCHK(hipMemsetAsync((void*)d_row_off, 0, 8, stream));
+    }
+    return t.write(d_rows, n, d_file, d_row_off, nf, quantisation, rules, flags, out, err);
+  });
+}
+
+int Matcher::tile_store_flush_text(const char* source, const char* mode, int flags, otr_tile_flush_result* flush,
+                                   otr_tile_text_result* out, std::string* err) {
+  std::vector<uint8_t> tag;
+  if (!text_tag(&tag, source, mode, OTR_TILE_RULES_STREAM)) return bad(err, kTagTooLong);
+  return guarded(*this, err, true, [&]() -> int {
+    int rc;
+    if ((rc = text_state(*this, err))) return rc;
+    ttx->h_tag = tag;
+    return tst->flush(*this, ttx, flags, flush, out, err);
   });
 }
 

@@ -721,6 +721,50 @@ class Matcher:
         out['quantisation'] = self._tile_quantisation
         return out
 
+    # --- tile file texts (include/otr.h otr_tiles_text) ----------------
+    @staticmethod
+    def _tag_bytes(x):
+        return x if isinstance(x, (bytes, bytearray)) else str(x).encode()
+
+    def tiles_text(self, rows=None, quantisation=3600, rules=0, source='smpl_rprt', mode='auto', device_ptr=None,
+                   n=None, host=True):
+        """otr_tiles_text: the file texts and names of rows grouped by file (numpy _lib.TILE_ROW,
+        or device_ptr and n), written on the device.  Returns _lib.tile_text_to_numpy's dict:
+        text and names (uint8), text_off, name_off, file, row_off, the counts and the device
+        pointers d_* (matcher-owned until its next tile call); host=False: device pointers only."""
+        r = _lib.TileTextResult()
+        flags = 0 if host else _lib.OTR_TILE_TEXT_NO_HOST
+        args = (int(quantisation), int(rules), self._tag_bytes(source), self._tag_bytes(mode), flags, ctypes.byref(r))
+        if device_ptr is not None:
+            rc = self._L.otr_tiles_text(self._h, device_ptr or None, int(n), _lib.OTR_MEM_DEVICE, *args)
+        else:
+            rows = np.ascontiguousarray(rows, dtype=_lib.TILE_ROW)
+            self._keep = [rows]
+            rc = self._L.otr_tiles_text(self._h, rows.ctypes.data if len(rows) else None, len(rows),
+                                        _lib.OTR_MEM_HOST, *args)
+        self._check(rc, 'otr_tiles_text')
+        return _lib.tile_text_to_numpy(r, host)
+
+    def tile_store_flush_text(self, source='reporter', mode='auto', host=True):
+        """otr_tile_store_flush_text: the flush with the files' texts written on the device.
+        Returns tile_store_flush's dict without 'rows' (they stay in HBM, d_rows), plus text,
+        text_off, names, name_off, n_text_bytes, n_name_bytes, text_ms and the device pointers
+        d_text, d_text_off, d_names, d_name_off; host=False: no text or names on the host."""
+        fl, r = _lib.TileFlushResult(), _lib.TileTextResult()
+        self._check(self._L.otr_tile_store_flush_text(self._h, self._tag_bytes(source), self._tag_bytes(mode),
+                                                      0 if host else _lib.OTR_TILE_TEXT_NO_HOST, ctypes.byref(fl),
+                                                      ctypes.byref(r)), 'otr_tile_store_flush_text')
+        out = _lib.tile_flush_to_numpy(fl)
+        del out['rows']
+        out['quantisation'] = self._tile_quantisation
+        text = _lib.tile_text_to_numpy(r, host)
+        out['text_ms'] = text['device_ms']
+        for k in ('text', 'text_off', 'names', 'name_off', 'n_text_bytes', 'n_name_bytes', 'd_text', 'd_text_off',
+                  'd_names', 'd_name_off'):
+            if k in text:
+                out[k] = text[k]
+        return out
+
     def match_batch_numpy(self, traces, **kw):
         r = self.match_batch(traces, copy_out=True, **kw)
         return _lib.result_to_numpy(r)

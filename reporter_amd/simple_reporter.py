@@ -252,6 +252,28 @@ def rows_to_tiles(rows, quantisation=3600, mode='auto', source='smpl_rprt', rule
     return tiles
 
 
+def text_payloads(res):
+    """{name: text} cut from the one byte buffer of a Matcher.tiles_text / tile_store_flush_text
+    result (its text, text_off, names, name_off).  Two files of one name (a file value that
+    recurs in the rows) are joined in order."""
+    text, names = res['text'].tobytes(), res['names'].tobytes()
+    t, m = res['text_off'].tolist(), res['name_off'].tolist()
+    out = {}
+    for f in range(int(res['n_files'])):
+        key = names[m[f]:m[f + 1]].decode()
+        body = text[t[f]:t[f + 1]].decode()
+        out[key] = out[key] + body if key in out else body
+    return out
+
+
+def tiles_text_device(matcher, device_ptr, n, quantisation=3600, mode='auto', source='smpl_rprt', rules=0):
+    """rows_to_tiles' counterpart on the device: the n rows at device_ptr (grouped by file, as
+    cull_rows leaves them in HBM) to {tile_key: text}, the text being the column line followed by
+    the file's lines, what write_tiles puts into the file."""
+    return text_payloads(matcher.tiles_text(device_ptr=device_ptr, n=n, quantisation=quantisation, rules=rules,
+                                            source=source, mode=mode))
+
+
 def _window_batch(traces, inactivity):
     from .tools.gen import Traces
     idx_lat, idx_lon, idx_time, offs, modes = [], [], [], [0], []
@@ -348,7 +370,17 @@ def stream_tile_payloads(flush, mode='auto', source='reporter'):
     return out
 
 
-def stream_text_tiles(matcher, chunks, fmt, end_ts, mode='auto', source='reporter'):
+def stream_tile_payloads_device(matcher, mode='auto', source='reporter', flush_out=None):
+    """stream_tile_payloads of the matcher's tile store with the texts written on the device
+    (Matcher.tile_store_flush_text): flushes the store and returns the same {name: text}; no row
+    crosses to the host.  flush_out: a dict that receives the flush (counts, file table, text)."""
+    flush = matcher.tile_store_flush_text(source, mode)
+    if flush_out is not None:
+        flush_out.update(flush)
+    return text_payloads(flush)
+
+
+def stream_text_tiles(matcher, chunks, fmt, end_ts, mode='auto', source='reporter', device_text=False):
     """The streaming reporter's whole topology with the text uploaded once per chunk and
     nothing parsed on the host: raw messages → keyed points (KeyedFormattingProcessor) →
     sessions (BatchingProcessor) → matches and reports → tile rows → cleaned files
@@ -356,7 +388,8 @@ def stream_text_tiles(matcher, chunks, fmt, end_ts, mode='auto', source='reporte
     an iterable of (text, msg_off or None, timestamp) as Matcher.sessions_push_text takes them;
     end_ts: the stream time of the final punctuate.  Returns {'payloads': those of
     stream_tile_payloads, 'flush': the tile store's flush, 'counts': messages, points, dropped,
-    unsupported, windows, reports}."""
+    unsupported, windows, reports}.  device_text=True: the file texts are written on the device
+    too (stream_tile_payloads_device; the flush then has no 'rows')."""
     counts = dict.fromkeys(('messages', 'points', 'dropped', 'unsupported', 'windows', 'reports'), 0)
     for text, msg_off, timestamp in chunks:
         f, s = matcher.sessions_push_text(text, fmt, msg_off=msg_off, timestamp=timestamp, arrays=False)
@@ -369,6 +402,10 @@ def stream_text_tiles(matcher, chunks, fmt, end_ts, mode='auto', source='reporte
     matcher.tile_store_add_session()
     counts['windows'] += s['n_windows']
     counts['reports'] += s['n_reports']
+    if device_text:
+        flush = {}
+        payloads = stream_tile_payloads_device(matcher, mode, source, flush_out=flush)
+        return {'payloads': payloads, 'flush': flush, 'counts': counts}
     flush = matcher.tile_store_flush()
     return {'payloads': stream_tile_payloads(flush, mode, source), 'flush': flush, 'counts': counts}
 

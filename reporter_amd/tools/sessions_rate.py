@@ -45,6 +45,16 @@ names, HIP events on the matcher's stream around every call, summed per replay: 
 the device time of the name kernels and of the names' copies.
 
     python -m reporter_amd.tools.sessions_rate --traces 2000 --names --out profiles/session_names_c2dep.json
+
+`--tile-store --text` (no value after `--text`) measures the last step of the chain, the flush to
+finished file payloads, in one process on two fills of the store: the replay's own rows (10 s
+chunks, privacy 2) and a seeded add_rows of `--tile-rows` rows over 300 files at privacy 1.  One
+warm-up of each path (their payloads are compared there), then `--repeats` timed runs alternating:
+the host path tile_store_flush + stream_tile_payloads, and the device path tile_store_flush_text +
+stream_tile_payloads_device, both as host wall time ending in the {name: text} dict, the device
+path's device_ms (flush + text stage) beside it; median [min, max].
+
+    python -m reporter_amd.tools.sessions_rate --traces 2000 --tile-store --text --out profiles/tile_text_c2dep.json
 """
 import argparse
 import json
@@ -165,11 +175,12 @@ def name_cost(m, pts, cuts, max_points, names, repeats):
     return out
 
 
-def replay(m, pts, cuts, max_points, batch_ms, tile_rows=0, text=None, names=None):
+def replay(m, pts, cuts, max_points, batch_ms, tile_rows=0, text=None, names=None, hold=False):
     """One replay: a fresh store, every chunk pushed, a final punctuate.  tile_rows > 0: a tile
     store of that many rows takes every result (add_session) and is flushed at the end.
     text: (kind, chunks of text_chunks): every chunk goes through sessions_push_text.
-    names: stream_names' dict, or True with text: the store has the uuid directory."""
+    names: stream_names' dict, or True with text: the store has the uuid directory.
+    hold: the tile store is neither flushed nor closed (the caller does both)."""
     m.sessions_open(int(pts['key'].max()) + 1, max_points, uuid_bytes=NAME_BYTES if names is not None else 0)
     if tile_rows:
         m.tile_store_open(tile_rows, 3600, 2)
@@ -198,6 +209,7 @@ def replay(m, pts, cuts, max_points, batch_ms, tile_rows=0, text=None, names=Non
     tile = None
     if tile_rows:
         add_ms.append(m.tile_store_add_session()['device_ms'])
+    if tile_rows and not hold:
         t1 = time.perf_counter()
         fl = m.tile_store_flush()
         tile = {'adds': len(add_ms), 'add_ms': float(np.sum(add_ms)), 'add_ms_max': float(np.max(add_ms)),
@@ -208,6 +220,75 @@ def replay(m, pts, cuts, max_points, batch_ms, tile_rows=0, text=None, names=Non
     m.sessions_close()
     return {'tile': tile, 'wall_s': wall, 'parse_ms': parse_ms, 'format_ms': format_ms, 'rounds': rounds, 'windows': windows, 'reports': reports, 'stream_ms': dev_ms, 'match_ms': match_ms,
             'evicted': ev['n_evicted'], 'eviction_windows': ev['n_windows'], 'chunks': len(chunks)}
+
+
+def seeded_rows(n, files=300, seed=19):
+    """n tile rows over `files` files of one hour, a few thousand pairs a file: ids of 11 to 12 digits,
+    a next id on three rows of four, times of 10 digits (about 80 bytes of text a row)."""
+    from reporter_amd import _lib
+    rng = np.random.RandomState(seed)
+    rows = np.zeros(n, _lib.TILE_ROW)
+    tile = rng.randint(0, files, n).astype(np.uint64)
+    index = rng.randint(0, 4000, n).astype(np.uint64)
+    rows['id'] = np.uint64(1) | (np.uint64(700000) + tile) << np.uint64(3) | index << np.uint64(25)
+    rows['next_id'] = rows['id'] + (np.uint64(1) << np.uint64(25))
+    rows['next_id'][rng.randint(0, 4, n) == 0] = 0x3fffffffffff
+    rows['file'] = (np.uint64(T_BEGIN // 3600) << np.uint64(25)) | (np.uint64(1) << np.uint64(22)) | \
+        ((rows['id'] >> np.uint64(3)) & np.uint64(0x3fffff))
+    rows['start'] = T_BEGIN + rng.randint(0, 3600, n)
+    rows['end'] = rows['start'] + rng.randint(1, 120, n)
+    rows['duration'] = rows['end'] - rows['start']
+    rows['length'] = rng.randint(20, 1500, n)
+    rows['queue_length'] = rng.randint(0, 4, n) // 3 * rng.randint(0, 100, n)
+    return rows
+
+
+def tile_text_rates(m, fill, close, repeats):
+    """The flush to file payloads both ways on the store `fill` leaves open (`close` closes it):
+    one warm-up each, then `repeats` timed runs alternating."""
+    from reporter_amd import simple_reporter as sr
+
+    def host():
+        fill()
+        t0 = time.perf_counter()
+        fl = m.tile_store_flush()
+        p = sr.stream_tile_payloads(fl, 'auto', 'reporter')
+        wall = 1e3 * (time.perf_counter() - t0)
+        close()
+        return p, {'wall_ms': wall, 'flush_ms': fl['device_ms'], 'rows_held': fl['n_rows_in'], 'rows_kept': fl['n_rows'],
+                   'files': fl['n_files']}
+
+    def device():
+        fill()
+        fl = {}
+        t0 = time.perf_counter()
+        p = sr.stream_tile_payloads_device(m, 'auto', 'reporter', flush_out=fl)
+        wall = 1e3 * (time.perf_counter() - t0)
+        close()
+        return p, {'wall_ms': wall, 'flush_ms': fl['device_ms'], 'text_ms': fl['text_ms'],
+                   'device_ms': fl['device_ms'] + fl['text_ms'], 'text_bytes': fl['n_text_bytes']}
+
+    (pa, a), (pb, b) = host(), device()
+    if pa != pb:
+        raise RuntimeError('the device texts differ from stream_tile_payloads')
+    del pa, pb
+    runs_a, runs_b = [], []
+    for _ in range(repeats):
+        runs_a.append(host()[1])
+        runs_b.append(device()[1])
+
+    def med(runs, k):
+        v = sorted(x[k] for x in runs)
+        return [round(float(np.median(v)), 3), round(float(v[0]), 3), round(float(v[-1]), 3)]
+
+    return {'rows_held': a['rows_held'], 'rows_kept': a['rows_kept'], 'files': a['files'], 'text_bytes': b['text_bytes'],
+            'host_path': {'what': 'tile_store_flush + stream_tile_payloads', 'wall_ms_median_min_max': med(runs_a, 'wall_ms'),
+                          'flush_ms_median_min_max': med(runs_a, 'flush_ms')},
+            'device_path': {'what': 'tile_store_flush_text + stream_tile_payloads_device',
+                            'wall_ms_median_min_max': med(runs_b, 'wall_ms'),
+                            'device_ms_median_min_max': med(runs_b, 'device_ms'),
+                            'flush_ms_median_min_max': med(runs_b, 'flush_ms'),
+                            'text_ms_median_min_max': med(runs_b, 'text_ms')}}
 
 
 def restore_rates(m, pts, max_points, repeats):
@@ -283,8 +364,9 @@ def main():
     ap.add_argument('--tile-store', action='store_true',
                     help='also replay with a tile store: add_session after every push, one flush at the end')
     ap.add_argument('--tile-rows', type=int, default=1 << 22, help='max_rows of that store')
-    ap.add_argument('--text', choices=['sv', 'json'], default=None,
-                    help='render the stream as messages and push them through otr_sessions_push_text')
+    ap.add_argument('--text', choices=['sv', 'json', 'tiles'], nargs='?', const='tiles', default=None,
+                    help='sv, json: render the stream as messages and push them through otr_sessions_push_text; '
+                         'no value, with --tile-store: time the flush to file payloads on the host and on the device')
     ap.add_argument('--restore', action='store_true',
                     help='time snapshot, export, take-all and the two restores on the store at the midpoint')
     ap.add_argument('--names', action='store_true',
@@ -319,6 +401,32 @@ def main():
                'method': '1 warm-up, %d timed; median [min, max]; device_ms of the call, or HIP events on the '
                          "matcher's stream around it" % args.repeats,
                'restore': restore_rates(m, pts, args.max_points, args.repeats)}
+        line = json.dumps(res, indent=1)
+        print(line)
+        if args.out:
+            with open(args.out, 'w') as f:
+                f.write(line + '\n')
+        return
+    if args.text == 'tiles':
+        if not args.tile_store:
+            ap.error('--text without a value goes with --tile-store')
+        sec = (pts['time'] - pts['time'][0]) // 10
+        cuts = [0] + (np.flatnonzero(np.diff(sec)) + 1).tolist() + [n]
+        rows = seeded_rows(args.tile_rows)
+
+        def fill_rows():
+            m.tile_store_open(args.tile_rows, 3600, 1)
+            m.tile_store_add_rows(rows)
+
+        res = {'workload': 'c2dep: %s graph, %d traces x 100 probes @15 s, sigma 10 m, deployed configuration; and '
+                           '%d seeded rows over 300 files' % (args.graph, args.traces, args.tile_rows),
+               'method': 'one process; 1 warm-up of each path, then %d timed runs alternating; host wall time from '
+                         'the flush call to the {name: text} dict; median [min, max]' % args.repeats,
+               'tile_text': {
+                   'replay_10_s_privacy_2': tile_text_rates(
+                       m, lambda: replay(m, pts, cuts, args.max_points, batch_ms, args.tile_rows, hold=True),
+                       m.tile_store_close, args.repeats),
+                   'add_rows_privacy_1': tile_text_rates(m, fill_rows, m.tile_store_close, args.repeats)}}
         line = json.dumps(res, indent=1)
         print(line)
         if args.out:
