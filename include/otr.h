@@ -913,6 +913,125 @@ int otr_tiles_text(otr_matcher* m, const otr_tile_row* rows, int64_t n, int32_t 
 int otr_tile_store_flush_text(otr_matcher* m, const char* source, const char* mode, int32_t flags,
                               otr_tile_flush_result* flush, otr_tile_text_result* out);
 
+/* ---- tile store: snapshot, restore, Segment.ListSerder records ----
+ * The reference keeps the anonymiser's state in two Kafka state stores with changelogs
+ * (AnonymisingProcessor.java:47-59): anonymise_tile, String "{time_range_start}_{tile_id}.{slice}"
+ * -> the bytes of Segment.ListSerder (Segment.java:131-155), and anonymise_max_slice,
+ * TimeQuantisedTile.Serder (TimeQuantisedTile.java:55-71) -> the current slice.  A Segment carries
+ * the doubles min and max, an otr_tile_row only floor(t0), ceil(t1) and the rounded duration, so a
+ * store that is to write those bytes keeps the two times beside every row. */
+#define OTR_TILE_STORE_TIMES 1   /* keep t0[max_rows] and t1[max_rows] (doubles, 16 B per row) */
+
+/* otr_tile_store_open with flags; 0 is otr_tile_store_open.  On a store with OTR_TILE_STORE_TIMES
+ * every add of reports writes the report's t0 and t1 beside each of its rows (a report that spans
+ * several buckets gives each of its rows the same pair), the flushes give the same results and
+ * reset it the same way, and otr_tile_store_add_rows is refused with OTR_BAD_REQUEST (finished rows
+ * have no times): otr_tile_store_restore takes its place. */
+int otr_tile_store_open_ex(otr_matcher* m, const otr_tile_store_config* cfg, int32_t flags);
+
+/* The held rows in arrival order; t0 / t1 per row on a store with the times, null otherwise.
+ * Host and device copies, owned by the matcher until its next tile-store call. */
+typedef struct otr_tile_snapshot {
+  int64_t n_rows;
+  int32_t quantisation;  int32_t flags;   /* the store's (output; ignored by a restore) */
+  const otr_tile_row* rows;  const double* t0;  const double* t1;
+  const otr_tile_row* d_rows;  const double* d_t0;  const double* d_t1;   /* output only */
+} otr_tile_snapshot;
+#define OTR_TILE_SNAPSHOT_NO_HOST 1   /* leave the host pointers null: device copies only */
+
+/* Why a tile restore is refused; where an index has several reasons the lowest value is reported. */
+#define OTR_TILE_RESTORE_E_LAYOUT 1     /* offsets not non-decreasing or beyond n_bytes; a record shorter than 4
+                                           bytes or not 4 + 40*count long (64-bit; count < 0 too) */
+#define OTR_TILE_RESTORE_E_KEY 2        /* start < 0, start % q != 0, start / q >= 2^39, tile_id outside
+                                           0 .. 0x1FFFFFF, slice < 0 */
+#define OTR_TILE_RESTORE_E_COUNT 3      /* count 0 (the reference never puts an empty list,
+                                           AnonymisingProcessor.java:138-141) or count > slice_size */
+#define OTR_TILE_RESTORE_E_SEGMENT 4    /* a segment failing Segment.valid; max >= 2^62; id & 0x1FFFFFF != tile_id;
+                                           or start / q outside [(long)min / q, (long)max / q] */
+#define OTR_TILE_RESTORE_E_DUPLICATE 5  /* not the first occurrence of its (start, tile_id, slice) in the input */
+#define OTR_TILE_RESTORE_E_MAP 6        /* a map entry with an invalid key (as E_KEY), a negative value or a
+                                           repeated key (bad_slice -1, bad_tile the lowest such entry); reported
+                                           only when no slice record has a reason */
+#define OTR_TILE_RESTORE_E_FULL 7       /* held + restored rows > max_rows (bad_slice -1); only when nothing
+                                           above applies */
+#define OTR_TILE_RESTORE_E_ROW 8        /* otr_tile_store_restore on a store with the times: a row that is not
+                                           the row its report gives (bad_slice: the lowest such row) */
+
+typedef struct otr_tile_restore_result {
+  int64_t n_slices, n_rows;             /* restored by this call */
+  int64_t n_unreferenced_slices, n_unreferenced_rows;   /* valid records the map does not name: not restored */
+  int64_t n_missing_slices;             /* slices the map names and the input lacks */
+  int64_t n_rows_held;                  /* after the call */
+  int64_t bad_slice;                    /* lowest refused record (otr_tile_store_restore: row), -1: none */
+  int64_t bad_tile;                     /* lowest refused map entry, -1: none */
+  int32_t bad_reason;                   /* OTR_TILE_RESTORE_E_*, 0 when restored */
+  float device_ms;
+} otr_tile_restore_result;
+
+/* flags: 0 or OTR_TILE_SNAPSHOT_NO_HOST.  The store is untouched; an empty store gives n_rows 0. */
+int otr_tile_store_snapshot(otr_matcher* m, int32_t flags, otr_tile_snapshot* out);
+
+/* Appends snap's n_rows rows (host or device arrays) to the held rows, all or nothing.  A plain
+ * store takes the rows as they are, exactly as otr_tile_store_add_rows does, and ignores any
+ * times.  A store with the times requires them, and every row must equal, bit for bit in all nine
+ * fields, the row an add derives from (row.file >> 25, id, next_id, t0, t1, length, queue_length):
+ * the report passes Segment.valid and the bucket lies in its span.  Otherwise OTR_BAD_REQUEST with
+ * OTR_TILE_RESTORE_E_ROW and the lowest such index in bad_slice; OTR_TILE_RESTORE_E_FULL when
+ * held + given > max_rows and no row is refused. */
+int otr_tile_store_restore(otr_matcher* m, const otr_tile_snapshot* snap, int32_t memory,
+                           otr_tile_restore_result* out);
+
+/* The held rows as the reference's records, in `file` order (bucket << 25 | level << 22 | tile
+ * index; time_range_start = bucket * q, tile_id = level | index << 3 = id & 0x1FFFFFF).  A file
+ * with n held rows gives slice records s = 0 .. ceil(n / S) - 1 holding its rows
+ * [sS, min((s+1)S, n)) in arrival order, and one map entry with value n / S (floor): when n is a
+ * multiple of S the slice the map names has no record yet, the reference's state after its S-th
+ * add (AnonymisingProcessor.java:147-151).  Slice record i is bytes[rec_off[i] .. rec_off[i+1]):
+ * int32 count, then count x (int64 id, int64 next_id, double min, double max, int32 length,
+ * int32 queue), big-endian, 4 + 40*count bytes (Segment.java:82-89, 145-148); next_id
+ * OTR_INVALID_SEGMENT_ID for none, min and max the kept t0 and t1 by bits.  Its key is
+ * (start[i], tile_id[i], slice[i]), and as the changelog's String names[name_off[i] ..
+ * name_off[i+1]).  map_bytes: 20 bytes per map entry, int64 start, int64 tile_id (the
+ * TimeQuantisedTile.Serder key), int32 slice (Kafka's integer value), big-endian.  Slices ascend
+ * by (file, slice), map entries by file.
+ * As an input (otr_tile_store_restore_records): n_slices, n_bytes, slice_size (the largest count
+ * accepted), memory, start, tile_id, slice, rec_off, bytes (any address, records at any offset),
+ * n_tiles and map_bytes (n_tiles < 0: no map); names and the d_ pointers are ignored. */
+typedef struct otr_tile_records {
+  int64_t n_slices, n_bytes, n_name_bytes;
+  int64_t n_tiles;
+  int32_t slice_size;  int32_t memory;   /* OTR_MEM_HOST / OTR_MEM_DEVICE (input; an export sets host) */
+  const int64_t* start;  const int64_t* tile_id;  const int32_t* slice;  const int64_t* rec_off;  /* n_slices + 1 */
+  const uint8_t* bytes;  const uint8_t* names;  const int64_t* name_off;  const uint8_t* map_bytes;
+  /* export only: the same arrays in HBM */
+  const int64_t* d_start;  const int64_t* d_tile_id;  const int32_t* d_slice;  const int64_t* d_rec_off;
+  const uint8_t* d_bytes;  const uint8_t* d_names;  const int64_t* d_name_off;  const uint8_t* d_map_bytes;
+} otr_tile_records;
+
+/* A store with the times only (OTR_BAD_REQUEST naming OTR_TILE_STORE_TIMES otherwise);
+ * slice_size >= 1, the reference's SLICE_SIZE is 20000 (AnonymisingProcessor.java:45).  The store
+ * is untouched.  An empty store gives zero slices and rec_off = {0}.  Host and device arrays,
+ * owned by the matcher until its next tile-store call. */
+int otr_tile_store_export_records(otr_matcher* m, int32_t slice_size, otr_tile_records* out);
+
+/* Appends the rows of the referenced slice records in (file, slice, position) order, each row
+ * derived from its segment exactly as an add derives it; a plain store keeps the rows only.  With
+ * a map a record is referenced when its (start, tile_id) has an entry and slice <= its value;
+ * unreferenced records are validated like the rest and not restored (the reference's punctuate
+ * deletes them with a warning, :258-265), slices the map names and the input lacks are accepted
+ * and counted (:242-243).  Without a map every record is referenced.  All or nothing: on a refusal
+ * OTR_BAD_REQUEST, the store untouched, bad_slice / bad_reason the lowest refused index and the
+ * lowest of its reasons.  ListSerder's own deserialiser returns an empty list (Segment.java:165-167)
+ * and so loses every restored slice; this call restores what the serialiser wrote. */
+int otr_tile_store_restore_records(otr_matcher* m, const otr_tile_records* in, otr_tile_restore_result* out);
+
+/* The changelog's String key of a slice: Long.toString(start) "_" Long.toString(tile_id) "."
+ * Integer.toString(slice).  Returns its length (at most 52, no terminator counted; one is written
+ * when it fits) or -1 when cap is too small.  The parse accepts exactly what those print: an
+ * optional '-', no '+', no leading zeros, no spaces; returns 0, or nonzero for anything else. */
+int otr_tile_slice_key(int64_t start, int64_t tile_id, int32_t slice, char* buf, int64_t cap);
+int otr_tile_slice_key_parse(const char* text, int64_t len, int64_t* start, int64_t* tile_id, int32_t* slice);
+
 /* report() (reporter_service.py:79-179) over n segment lists at once, evaluated by the
  * device code of the segment scan K7 (otr_report.h compiled for gfx950, one thread per
  * list) — what pins the device tail against the reference's own report() outputs.  Host

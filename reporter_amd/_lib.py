@@ -25,6 +25,12 @@ POINT_UNMATCHED, POINT_STATE, POINT_INTERPOLATED = 0, 1, 2
 OTR_TILE_RULES_SIMPLE = 0
 OTR_TILE_RULES_STREAM = 1
 OTR_TILE_TEXT_NO_HOST = 1
+OTR_TILE_STORE_TIMES = 1
+OTR_TILE_SNAPSHOT_NO_HOST = 1
+OTR_TILE_RESTORE_E_LAYOUT, OTR_TILE_RESTORE_E_KEY, OTR_TILE_RESTORE_E_COUNT, OTR_TILE_RESTORE_E_SEGMENT = 1, 2, 3, 4
+OTR_TILE_RESTORE_E_DUPLICATE, OTR_TILE_RESTORE_E_MAP, OTR_TILE_RESTORE_E_FULL, OTR_TILE_RESTORE_E_ROW = 5, 6, 7, 8
+TILE_RESTORE_REASONS = {1: 'layout', 2: 'key', 3: 'count', 4: 'segment', 5: 'duplicate', 6: 'map', 7: 'full',
+                        8: 'row'}
 OTR_INGEST_SHARD = 0
 OTR_INGEST_RAW = 1
 OTR_INGEST_JAVA_SV = 2
@@ -67,7 +73,10 @@ EXPORTS = ['otr_configure', 'otr_configure_json', 'otr_matcher_new', 'otr_matche
            'otr_sessions_restore_records', 'otr_sessions_export_records', 'otr_sessions_take', 'otr_uuid_key',
            'otr_sessions_open_named', 'otr_sessions_push_named', 'otr_sessions_advance_named',
            'otr_sessions_last_refusal', 'otr_sessions_names', 'otr_sessions_restore_named',
-           'otr_sessions_restore_records_named', 'otr_tiles_text', 'otr_tile_store_flush_text']
+           'otr_sessions_restore_records_named', 'otr_tiles_text', 'otr_tile_store_flush_text',
+           'otr_tile_store_open_ex', 'otr_tile_store_snapshot', 'otr_tile_store_restore',
+           'otr_tile_store_export_records', 'otr_tile_store_restore_records', 'otr_tile_slice_key',
+           'otr_tile_slice_key_parse']
 
 
 class ServiceSplit(ctypes.Structure):
@@ -325,6 +334,36 @@ class TileTextResult(ctypes.Structure):
                 [('d_' + k, ctypes.c_void_p) for k in TILE_TEXT_FIELDS])
 
 
+class TileSnapshot(ctypes.Structure):
+    """otr_tile_snapshot (include/otr.h): the held rows in arrival order, with their times."""
+    _fields_ = [('n_rows', ctypes.c_int64), ('quantisation', ctypes.c_int32), ('flags', ctypes.c_int32),
+                ('rows', ctypes.c_void_p), ('t0', ctypes.c_void_p), ('t1', ctypes.c_void_p),
+                ('d_rows', ctypes.c_void_p), ('d_t0', ctypes.c_void_p), ('d_t1', ctypes.c_void_p)]
+
+
+TILE_RESTORE_COUNTS = ['n_slices', 'n_rows', 'n_unreferenced_slices', 'n_unreferenced_rows', 'n_missing_slices',
+                       'n_rows_held', 'bad_slice', 'bad_tile']
+
+
+class TileRestoreResult(ctypes.Structure):
+    """otr_tile_restore_result (include/otr.h): what a tile restore did, or why it was refused."""
+    _fields_ = ([(k, ctypes.c_int64) for k in TILE_RESTORE_COUNTS] +
+                [('bad_reason', ctypes.c_int32), ('device_ms', ctypes.c_float)])
+
+
+# the arrays of otr_tile_records, in the struct's order
+TILE_RECORD_FIELDS = ['start', 'tile_id', 'slice', 'rec_off', 'bytes', 'names', 'name_off', 'map_bytes']
+
+
+class TileRecords(ctypes.Structure):
+    """otr_tile_records (include/otr.h): the tile store as Segment.ListSerder slice records and
+    the slice map's entries."""
+    _fields_ = ([('n_slices', ctypes.c_int64), ('n_bytes', ctypes.c_int64), ('n_name_bytes', ctypes.c_int64),
+                 ('n_tiles', ctypes.c_int64), ('slice_size', ctypes.c_int32), ('memory', ctypes.c_int32)] +
+                [(k, ctypes.c_void_p) for k in TILE_RECORD_FIELDS] +
+                [('d_' + k, ctypes.c_void_p) for k in TILE_RECORD_FIELDS])
+
+
 def _copy(ptr, n, dt):
     """n records of dtype dt at the host address ptr, copied."""
     if n <= 0 or not ptr:
@@ -348,6 +387,46 @@ def tile_flush_to_numpy(r):
     out['row_off'] = _copy(r.row_off, nf + 1, np.int64)
     out['n_unclean'] = _copy(r.n_unclean, nf, np.int64)
     for k in TILE_FLUSH_FIELDS:
+        out['d_' + k] = int(getattr(r, 'd_' + k) or 0)
+    return out
+
+
+def tile_snapshot_to_numpy(r, host=True):
+    """An otr_tile_snapshot: n_rows, quantisation, flags, the device pointers d_rows, d_t0, d_t1
+    and with host=True copies of rows and, from a store with the times, t0 and t1 (else None)."""
+    n = int(r.n_rows)
+    out = {'n_rows': n, 'quantisation': int(r.quantisation), 'flags': int(r.flags)}
+    for k in ('rows', 't0', 't1'):
+        out['d_' + k] = int(getattr(r, 'd_' + k) or 0)
+    if host:
+        timed = bool(r.flags & OTR_TILE_STORE_TIMES)
+        out['rows'] = _copy(r.rows, n, TILE_ROW)
+        out['t0'] = _copy(r.t0, n, np.float64) if timed else None
+        out['t1'] = _copy(r.t1, n, np.float64) if timed else None
+    return out
+
+
+def tile_restore_to_dict(r):
+    out = {k: int(getattr(r, k)) for k in TILE_RESTORE_COUNTS}
+    out['bad_reason'], out['device_ms'] = int(r.bad_reason), float(r.device_ms)
+    return out
+
+
+def tile_records_to_numpy(r):
+    """An otr_tile_records export: host copies of start, tile_id, rec_off, name_off (int64), slice
+    (int32), bytes, names, map_bytes (uint8), the counts, slice_size and the device pointers d_*."""
+    ns, nt = int(r.n_slices), int(r.n_tiles)
+    out = {'n_slices': ns, 'n_bytes': int(r.n_bytes), 'n_name_bytes': int(r.n_name_bytes), 'n_tiles': nt,
+           'slice_size': int(r.slice_size)}
+    out['start'] = _copy(r.start, ns, np.int64)
+    out['tile_id'] = _copy(r.tile_id, ns, np.int64)
+    out['slice'] = _copy(r.slice, ns, np.int32)
+    out['rec_off'] = _copy(r.rec_off, ns + 1, np.int64)
+    out['name_off'] = _copy(r.name_off, ns + 1, np.int64)
+    out['bytes'] = _bytes(r.bytes, int(r.n_bytes))
+    out['names'] = _bytes(r.names, int(r.n_name_bytes))
+    out['map_bytes'] = _bytes(r.map_bytes, 20 * max(nt, 0))
+    for k in TILE_RECORD_FIELDS:
         out['d_' + k] = int(getattr(r, 'd_' + k) or 0)
     return out
 
@@ -555,6 +634,16 @@ def lib():
                                      P(TileTextResult)]
         L.otr_tile_store_flush_text.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32,
                                                 P(TileFlushResult), P(TileTextResult)]
+    if hasattr(L, 'otr_tile_store_open_ex'):
+        L.otr_tile_store_open_ex.argtypes = [ctypes.c_void_p, P(TileStoreConfig), ctypes.c_int32]
+        L.otr_tile_store_snapshot.argtypes = [ctypes.c_void_p, ctypes.c_int32, P(TileSnapshot)]
+        L.otr_tile_store_restore.argtypes = [ctypes.c_void_p, P(TileSnapshot), ctypes.c_int32, P(TileRestoreResult)]
+        L.otr_tile_store_export_records.argtypes = [ctypes.c_void_p, ctypes.c_int32, P(TileRecords)]
+        L.otr_tile_store_restore_records.argtypes = [ctypes.c_void_p, P(TileRecords), P(TileRestoreResult)]
+        L.otr_tile_slice_key.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_char_p,
+                                         ctypes.c_int64]
+        L.otr_tile_slice_key_parse.argtypes = [ctypes.c_char_p, ctypes.c_int64, P(ctypes.c_int64), P(ctypes.c_int64),
+                                               P(ctypes.c_int32)]
     if hasattr(L, 'otr_format_messages'):
         L.otr_format_messages.argtypes = [ctypes.c_void_p, P(MessageFormat), P(Messages), P(FormatResult)]
         L.otr_sessions_push_text.argtypes = [ctypes.c_void_p, P(MessageFormat), P(Messages), P(FormatResult),

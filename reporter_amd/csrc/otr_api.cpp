@@ -584,7 +584,28 @@ int otr_sessions_push_text(otr_matcher* m, const otr_message_format* fmt, const 
 // the tile store (K15): BatchingProcessor.forward → AnonymisingProcessor.process / punctuate
 // (BatchingProcessor.java:108-141, AnonymisingProcessor.java:119-175, 222-266), in HBM
 int otr_tile_store_open(otr_matcher* m, const otr_tile_store_config* cfg) {
-  OTR_SESSIONS_CALL(!m || !cfg, tile_store_open(cfg, &err));
+  OTR_SESSIONS_CALL(!m || !cfg, tile_store_open(cfg, 0, &err));
+}
+
+int otr_tile_store_open_ex(otr_matcher* m, const otr_tile_store_config* cfg, int32_t flags) {
+  OTR_SESSIONS_CALL(!m || !cfg, tile_store_open(cfg, flags, &err));
+}
+
+int otr_tile_store_snapshot(otr_matcher* m, int32_t flags, otr_tile_snapshot* out) {
+  OTR_SESSIONS_CALL(!m || !out, tile_store_snapshot(flags, out, &err));
+}
+
+int otr_tile_store_restore(otr_matcher* m, const otr_tile_snapshot* snap, int32_t memory,
+                           otr_tile_restore_result* out) {
+  OTR_SESSIONS_CALL(!m || !snap || !out, tile_store_restore(snap, memory, out, &err));
+}
+
+int otr_tile_store_export_records(otr_matcher* m, int32_t slice_size, otr_tile_records* out) {
+  OTR_SESSIONS_CALL(!m || !out, tile_store_export_records(slice_size, out, &err));
+}
+
+int otr_tile_store_restore_records(otr_matcher* m, const otr_tile_records* in, otr_tile_restore_result* out) {
+  OTR_SESSIONS_CALL(!m || !in || !out, tile_store_restore_records(in, out, &err));
 }
 
 int otr_tile_store_close(otr_matcher* m) { OTR_SESSIONS_CALL(!m, tile_store_close(&err)); }

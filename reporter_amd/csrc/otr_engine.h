@@ -221,7 +221,11 @@ struct Matcher {
   const uint8_t* fmt_text = nullptr;
   int64_t fmt_text_len = 0;
   // the tile store (K15, otr_tilestore.hip)
-  int tile_store_open(const otr_tile_store_config* cfg, std::string* err);
+  int tile_store_open(const otr_tile_store_config* cfg, int flags, std::string* err);
+  int tile_store_snapshot(int flags, otr_tile_snapshot* out, std::string* err);
+  int tile_store_restore(const otr_tile_snapshot* snap, int memory, otr_tile_restore_result* out, std::string* err);
+  int tile_store_export_records(int32_t slice_size, otr_tile_records* out, std::string* err);
+  int tile_store_restore_records(const otr_tile_records* in, otr_tile_restore_result* out, std::string* err);
   int tile_store_close(std::string* err);
   int tile_store_add_session(otr_tile_add_result* out, std::string* err);
   int tile_store_add_reports(int64_t n_windows, const int64_t* rep_off, const uint64_t* id, const uint64_t* next_id,

@@ -35,6 +35,8 @@ struct StoreArgs {
   unsigned long long* counters;  // pass 1 output: TST_*
   const int64_t* row_off;       // pass 2 input: exclusive offsets, by position
   otr_tile_row* rows;           // pass 2 output: the first free row of the store
+  double* row_t0;               // a store with the times (TIMES): the report's t0 and t1 beside
+  double* row_t1;               // every row, from the first free row on
 };
 
 // the sort key of add_session's window order: triggers ascending; an eviction's windows
@@ -51,8 +53,10 @@ __global__ void k_store_order_key(const int64_t* trigger, int64_t n, unsigned lo
 // contiguous (buckets ascending), the reports of a chunk are placed by a wave prefix sum
 // and the chunks by the running base, so a window's rows come out in report order and the
 // windows at their scanned offsets.  WRITE false counts (row_cnt, the valid reports and
-// whether rep_off runs backwards), WRITE true writes every row whole from one lane.
-template <bool WRITE>
+// whether rep_off runs backwards), WRITE true writes every row whole from one lane.  TIMES
+// (OTR_TILE_STORE_TIMES) is a template parameter so that the plain store's instance stays the
+// instruction stream it was.
+template <bool WRITE, bool TIMES = false>
 __global__ __launch_bounds__(256) void k_store_rows(StoreArgs a) {
   const int64_t p = (int64_t)blockIdx.x * kStoreWaves + threadIdx.x / OTR_WAVE;
   if (p >= a.n_windows) return;  // wave-uniform
@@ -80,8 +84,13 @@ __global__ __launch_bounds__(256) void k_store_rows(StoreArgs a) {
       const unsigned long long id = a.id[r], nx = a.next_id[r];
       const int speed_bin = tile_speed_bin(len, t0, t1);
       int64_t k = base + (int64_t)(incl - nb);
-      for (int64_t bk = sp.min_bucket; bk <= sp.max_bucket; ++bk, ++k)
+      for (int64_t bk = sp.min_bucket; bk <= sp.max_bucket; ++bk, ++k) {
         a.rows[k] = tile_row_of(bk, id, nx, sp, len, qu, speed_bin);
+        if (TIMES) {
+          a.row_t0[k] = t0;
+          a.row_t1[k] = t1;
+        }
+      }
     }
     base += (int64_t)__shfl(incl, OTR_WAVE - 1);
     valid += keep ? 1ull : 0ull;

@@ -1,7 +1,8 @@
 // otr_tilestore.hip — host side of the tile store (K15, otr_tilestore.h): the store's row
 // buffer, the two passes of an add (count, scan, capacity check, write) and the flush (the
 // matcher's device cull, then the per-file table), and of the tile file texts (K19,
-// otr_tiletext.h): lengths, scans, one emit pass.  include/otr.h otr_tile_store_* and
+// otr_tiletext.h): lengths, scans, one emit pass, and of the store's snapshot, restore and
+// changelog records (K20, otr_tile_records.h).  include/otr.h otr_tile_store_* and
 // otr_tiles_text for the rules.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -15,6 +16,7 @@
 #include "otr_engine.h"
 #include "otr_tilestore.h"
 #include "otr_tiletext.h"
+#include "otr_tile_records.h"
 
 #define HIPCHK(x)                                                                        \
   do {                                                                                   \
@@ -44,6 +46,13 @@ enum TstBuf {
   T_OFF, T_ID, T_NEXT, T_T0, T_T1, T_LEN, T_QUEUE, T_KEY_A, T_KEY_B, T_IDX_A, T_IDX_B, T_CNT, T_ROW_OFF, T_TMP,
   T_F_HEAD, T_F_INCL, T_F_START, T_F_LISTED, T_F_LINCL, T_F_FILE, T_F_ROW_OFF, T_F_UNCLEAN,
   T_X_ROWS, T_X_TAG, T_X_LEN, T_X_OFF, T_X_TEXT_OFF, T_X_NAME_LEN, T_X_NAME_OFF, T_X_TEXT, T_X_NAMES,
+  // K20: a snapshot (and a restore's staging), an export's outputs, a record restore's input and work
+  T_S_ROWS, T_S_T0, T_S_T1, T_S_VERDICT,
+  T_E_SHEAD, T_E_SINCL, T_E_POS, T_E_START, T_E_TILE, T_E_SLICE, T_E_REC_LEN, T_E_REC_OFF, T_E_NAME_LEN, T_E_NAME_OFF,
+  T_E_BYTES, T_E_NAMES, T_E_MAP,
+  T_I_START, T_I_TILE, T_I_SLICE, T_I_OFF, T_I_BYTES, T_I_MAP, T_I_COUNT, T_I_KEY_OK, T_I_FILE, T_I_FILE_A, T_I_FILE_B,
+  T_I_SLICE_KEY, T_I_SLICE_B, T_I_IDX_A, T_I_IDX_B, T_I_IDX_C, T_I_WORDS, T_I_REF, T_I_ROW_OFF,
+  T_M_FILE_A, T_M_FILE_B, T_M_IDX_A, T_M_IDX_B, T_M_VALUE, T_M_OK,
   T_NUM
 };
 const char* const kTstName[T_NUM] = {
@@ -52,7 +61,16 @@ const char* const kTstName[T_NUM] = {
     "window row offsets", "scan / sort workspace", "file head", "file rank", "file start", "file listed",
     "listed file rank", "file table files", "file table row offsets", "file table unclean counts",
     "text rows", "text tag", "text row lengths", "text row offsets", "file text offsets", "file name lengths",
-    "file name offsets", "file texts", "file names"};
+    "file name offsets", "file texts", "file names",
+    "snapshot rows", "snapshot t0", "snapshot t1", "restore verdict",
+    "slice heads", "slice ranks", "slice positions", "slice starts", "slice tile ids", "slice numbers",
+    "record lengths", "record offsets", "slice name lengths", "slice name offsets", "record bytes", "slice names",
+    "map entries",
+    "input starts", "input tile ids", "input slices", "input record offsets", "input record bytes", "input map entries",
+    "input counts", "input key flags", "input file keys", "input file keys in slice order", "sorted input file keys",
+    "input slice keys", "sorted input slice keys", "input index", "input slice order", "input order",
+    "restore verdict and counters", "referenced counts", "restored row offsets",
+    "map file keys", "sorted map file keys", "map index", "map order", "map values", "map key flags"};
 
 }  // namespace
 
@@ -128,10 +146,27 @@ struct TileStore : TstBufs {
   otr_tile_row* rows = nullptr;  // [max_rows], the store's own allocation
   unsigned long long* counters = nullptr;
   int64_t n_rows = 0;
+  int flags = 0;         // OTR_TILE_STORE_*
+  double* t0 = nullptr;  // [max_rows] each with OTR_TILE_STORE_TIMES
+  double* t1 = nullptr;
   // what a flush returns
   std::vector<otr_tile_row> h_rows;
   std::vector<unsigned long long> h_file;
   std::vector<int64_t> h_row_off, h_unclean;
+  // what a snapshot and an export return (K20)
+  std::vector<otr_tile_row> h_snap_rows;
+  std::vector<double> h_snap_t0, h_snap_t1;
+  std::vector<int64_t> h_start, h_tile, h_rec_off, h_name_off;
+  std::vector<int32_t> h_slice;
+  std::vector<uint8_t> h_bytes, h_names, h_map;
+
+  bool timed() const { return (flags & OTR_TILE_STORE_TIMES) != 0; }
+  int sort_pairs(const unsigned long long* k_in, unsigned long long* k_out, const int32_t* v_in, int32_t* v_out,
+                 int64_t n, std::string* err);
+  int snapshot(int sflags, otr_tile_snapshot* out, std::string* err);
+  int restore(const otr_tile_snapshot* snap, int memory, otr_tile_restore_result* out, std::string* err);
+  int export_records(int32_t slice_size, otr_tile_records* out, std::string* err);
+  int restore_records(const otr_tile_records* in, otr_tile_restore_result* out, std::string* err);
 
   int alloc(std::string* err);
   int add(const StoreArgs& in, int64_t n_reports, otr_tile_add_result* out, std::string* err);
@@ -145,6 +180,8 @@ void tile_store_destroy(TileStore* s) {
   s->release();
   if (s->rows) (void)hipFree(s->rows);
   if (s->counters) (void)hipFree(s->counters);
+  if (s->t0) (void)hipFree(s->t0);
+  if (s->t1) (void)hipFree(s->t1);
   delete s;
 }
 
@@ -167,6 +204,13 @@ int TileStore::alloc(std::string* err) {
     (void)hipGetLastError();
     counters = nullptr;
     throw TstOom{"tile store counters", 8 * TST_WORDS};
+  }
+  if (timed()) {
+    const size_t tb = sizeof(double) * (size_t)cfg.max_rows;
+    if (hipMalloc((void**)&t0, tb) != hipSuccess || hipMalloc((void**)&t1, tb) != hipSuccess) {
+      (void)hipGetLastError();
+      throw TstOom{"tile store times", 2 * tb};
+    }
   }
   return events(err);
 }
@@ -199,6 +243,8 @@ int TileStore::add(const StoreArgs& in, int64_t n_reports, otr_tile_add_result* 
   a.counters = counters;
   a.row_off = off;
   a.rows = rows + n_rows;
+  a.row_t0 = timed() ? t0 + n_rows : nullptr;
+  a.row_t1 = timed() ? t1 + n_rows : nullptr;
   const unsigned blocks = tst_grid(W, kStoreWaves);
   HIPCHK(hipMemsetAsync(counters, 0, 8 * TST_WORDS, stream));
   HIPCHK(hipMemsetAsync(off, 0, 8, stream));
@@ -223,7 +269,10 @@ int TileStore::add(const StoreArgs& in, int64_t n_reports, otr_tile_add_result* 
     return OTR_BAD_REQUEST;
   }
   if (total > 0) {
-    k_store_rows<true><<<blocks, 256, 0, stream>>>(a);
+    if (timed())
+      k_store_rows<true, true><<<blocks, 256, 0, stream>>>(a);
+    else
+      k_store_rows<true><<<blocks, 256, 0, stream>>>(a);
     HIPCHK(hipGetLastError());
   }
   float ms = 0.f;
@@ -260,7 +309,8 @@ int guarded(Matcher& m, std::string* err, bool need_store, F&& f) {
 
 }  // namespace
 
-int Matcher::tile_store_open(const otr_tile_store_config* cfg, std::string* err) {
+int Matcher::tile_store_open(const otr_tile_store_config* cfg, int flags, std::string* err) {
+  if (flags & ~OTR_TILE_STORE_TIMES) return bad(err, "unknown tile store flags");
   if (tst) return bad(err, "the matcher already has a tile store");
   if (cfg->max_rows < 1 || cfg->max_rows > kTstMaxRows || cfg->quantisation < 60 || cfg->privacy < 1)
     return bad(err, "tile store config out of range (max_rows 1 .. 1<<27, quantisation >= 60, privacy >= 1)");
@@ -268,6 +318,7 @@ int Matcher::tile_store_open(const otr_tile_store_config* cfg, std::string* err)
   if (!stream) HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
   TileStore* s = new TileStore();
   s->cfg = *cfg;
+  s->flags = flags;
   s->stream = stream;
   const int rc = guarded(*this, err, false, [&] { return s->alloc(err); });
   if (rc != OTR_OK) {
@@ -398,6 +449,9 @@ int Matcher::tile_store_add_rows(const otr_tile_row* rows, int64_t n, int memory
                                  std::string* err) {
   return guarded(*this, err, true, [&]() -> int {
     TileStore& s = *tst;
+    if (s.timed())
+      return bad(err, "finished rows have no times: a tile store opened with OTR_TILE_STORE_TIMES takes "
+                      "otr_tile_store_restore instead");
     if (n <= 0) {
       s.add_result(out, 0, 0, 0);
       return OTR_OK;
@@ -704,6 +758,437 @@ int Matcher::tile_store_flush_text(const char* source, const char* mode, int fla
     if ((rc = text_state(*this, err))) return rc;
     ttx->h_tag = tag;
     return tst->flush(*this, ttx, flags, flush, out, err);
+  });
+}
+
+// ---- snapshot, restore, Segment.ListSerder records (K20) -------------------------------------
+
+namespace {
+
+void restore_result(otr_tile_restore_result* out, int64_t held) {
+  memset(out, 0, sizeof(*out));
+  out->bad_slice = out->bad_tile = -1;
+  out->n_rows_held = held;
+}
+
+hipMemcpyKind copy_in(int memory) { return memory == OTR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; }
+
+const char* const kTileRestoreReason[] = {"",      "layout", "key",  "count", "segment", "duplicate",
+                                          "map", "full",   "row"};
+
+}  // namespace
+
+int TileStore::sort_pairs(const unsigned long long* k_in, unsigned long long* k_out, const int32_t* v_in,
+                          int32_t* v_out, int64_t n, std::string* err) {
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k_in, k_out, v_in, v_out, (int)n, 0, 64, stream));
+  void* tmp = buf<char>(T_TMP, tb);
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, k_in, k_out, v_in, v_out, (int)n, 0, 64, stream));
+  return OTR_OK;
+}
+
+int TileStore::snapshot(int sflags, otr_tile_snapshot* out, std::string* err) {
+  memset(out, 0, sizeof(*out));
+  out->quantisation = cfg.quantisation;
+  out->flags = flags;
+  const size_t n = (size_t)n_rows;
+  out->n_rows = n_rows;
+  if (n == 0) return OTR_OK;
+  const bool host = !(sflags & OTR_TILE_SNAPSHOT_NO_HOST);
+  otr_tile_row* d_rows = buf<otr_tile_row>(T_S_ROWS, n);
+  HIPCHK(hipMemcpyAsync(d_rows, rows, sizeof(otr_tile_row) * n, hipMemcpyDeviceToDevice, stream));
+  out->d_rows = d_rows;
+  if (host) {
+    h_snap_rows.resize(n);
+    HIPCHK(hipMemcpyAsync(h_snap_rows.data(), rows, sizeof(otr_tile_row) * n, hipMemcpyDeviceToHost, stream));
+    out->rows = h_snap_rows.data();
+  }
+  if (timed()) {
+    double* d_t0 = buf<double>(T_S_T0, n);
+    double* d_t1 = buf<double>(T_S_T1, n);
+    HIPCHK(hipMemcpyAsync(d_t0, t0, 8 * n, hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_t1, t1, 8 * n, hipMemcpyDeviceToDevice, stream));
+    out->d_t0 = d_t0;
+    out->d_t1 = d_t1;
+    if (host) {
+      h_snap_t0.resize(n);
+      h_snap_t1.resize(n);
+      HIPCHK(hipMemcpyAsync(h_snap_t0.data(), t0, 8 * n, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipMemcpyAsync(h_snap_t1.data(), t1, 8 * n, hipMemcpyDeviceToHost, stream));
+      out->t0 = h_snap_t0.data();
+      out->t1 = h_snap_t1.data();
+    }
+  }
+  HIPCHK(hipStreamSynchronize(stream));
+  return OTR_OK;
+}
+
+int TileStore::restore(const otr_tile_snapshot* snap, int memory, otr_tile_restore_result* out, std::string* err) {
+  int rc;
+  restore_result(out, n_rows);
+  const int64_t n = snap->n_rows;
+  if (n < 0 || n > kTstMaxRows) return bad(err, "tile restore: row count out of range");
+  if (n == 0) return OTR_OK;
+  if (!snap->rows || (timed() && (!snap->t0 || !snap->t1)))
+    return bad(err, timed() ? "tile restore: a store with OTR_TILE_STORE_TIMES needs rows, t0 and t1"
+                            : "null argument");
+  HIPCHK(hipEventRecord(ev[0], stream));
+  const otr_tile_row* d_rows = snap->rows;
+  const double *d_t0 = snap->t0, *d_t1 = snap->t1;
+  if (timed()) {
+    if (memory != OTR_MEM_DEVICE) {  // staged: nothing reaches the store before the check has passed
+      otr_tile_row* r = buf<otr_tile_row>(T_S_ROWS, n);
+      double* a = buf<double>(T_S_T0, n);
+      double* b = buf<double>(T_S_T1, n);
+      HIPCHK(hipMemcpyAsync(r, snap->rows, sizeof(otr_tile_row) * (size_t)n, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(a, snap->t0, 8 * (size_t)n, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(b, snap->t1, 8 * (size_t)n, hipMemcpyHostToDevice, stream));
+      d_rows = r;
+      d_t0 = a;
+      d_t1 = b;
+    }
+    unsigned long long* verdict = buf<unsigned long long>(T_S_VERDICT, 1);
+    unsigned long long h_verdict = 0;
+    HIPCHK(hipMemsetAsync(verdict, 0xFF, 8, stream));
+    k_tilerec_check_rows<<<tst_grid(n, 256), 256, 0, stream>>>(d_rows, d_t0, d_t1, n, cfg.quantisation, verdict);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&h_verdict, verdict, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (h_verdict != kTileRecNone) {
+      out->bad_slice = (int64_t)h_verdict;
+      out->bad_reason = OTR_TILE_RESTORE_E_ROW;
+      return bad(err, "tile restore: row " + std::to_string(out->bad_slice) +
+                          " is not the row its report gives under the store's quantisation");
+    }
+  }
+  if (n > cfg.max_rows - n_rows) {
+    out->bad_reason = OTR_TILE_RESTORE_E_FULL;
+    return bad(err, "the restore would take the tile store beyond max_rows (" + std::to_string(n_rows) +
+                        " rows held, " + std::to_string(n) + " given, max_rows " + std::to_string(cfg.max_rows) + ")");
+  }
+  const hipMemcpyKind kind = (timed() || memory == OTR_MEM_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  HIPCHK(hipMemcpyAsync(rows + n_rows, d_rows, sizeof(otr_tile_row) * (size_t)n, kind, stream));
+  if (timed()) {
+    HIPCHK(hipMemcpyAsync(t0 + n_rows, d_t0, 8 * (size_t)n, hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipMemcpyAsync(t1 + n_rows, d_t1, 8 * (size_t)n, hipMemcpyDeviceToDevice, stream));
+  }
+  if ((rc = finish(&out->device_ms, err))) return rc;
+  n_rows += n;
+  out->n_rows = n;
+  out->n_rows_held = n_rows;
+  return OTR_OK;
+}
+
+int TileStore::export_records(int32_t slice_size, otr_tile_records* out, std::string* err) {
+  int rc;
+  memset(out, 0, sizeof(*out));
+  if (!timed())
+    return bad(err, "the records carry the reports' times: open the tile store with OTR_TILE_STORE_TIMES");
+  if (slice_size < 1) return bad(err, "tile export: slice_size below 1");
+  const int64_t n = n_rows, S = slice_size, q = cfg.quantisation;
+  out->slice_size = slice_size;
+  out->memory = OTR_MEM_HOST;
+  HIPCHK(hipEventRecord(ev[0], stream));
+  int64_t* rec_off = buf<int64_t>(T_E_REC_OFF, 1);
+  int64_t* name_off = buf<int64_t>(T_E_NAME_OFF, 1);
+  int64_t nf = 0, ns = 0, total[2] = {0, 0};
+  int64_t *start = nullptr, *tile = nullptr;
+  int32_t* slice = nullptr;
+  uint32_t* map_words = nullptr;
+  if (n > 0) {
+    const unsigned g = tst_grid(n, 256);
+    unsigned long long* key_a = buf<unsigned long long>(T_KEY_A, n);
+    unsigned long long* key_b = buf<unsigned long long>(T_KEY_B, n);
+    int32_t* idx_a = buf<int32_t>(T_IDX_A, n);
+    int32_t* idx_b = buf<int32_t>(T_IDX_B, n);
+    // arrival order within a file: a stable sort by `file` alone
+    k_tilerec_keys<<<g, 256, 0, stream>>>(rows, n, key_a, idx_a);
+    if ((rc = sort_pairs(key_a, key_b, idx_a, idx_b, n, err))) return rc;
+    int64_t* head = buf<int64_t>(T_F_HEAD, n);
+    int64_t* head_incl = buf<int64_t>(T_F_INCL, n);
+    k_tilerec_heads<<<g, 256, 0, stream>>>(key_b, n, head);
+    if ((rc = scan64(head, head_incl, n, err))) return rc;
+    HIPCHK(hipMemcpyAsync(&nf, head_incl + (n - 1), 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (nf < 1 || nf > n) {
+      if (err) *err = "tile export file split failed";
+      return OTR_DEVICE_ERROR;
+    }
+    int64_t* fstart = buf<int64_t>(T_F_START, nf);
+    int64_t* shead = buf<int64_t>(T_E_SHEAD, n);
+    int64_t* shead_incl = buf<int64_t>(T_E_SINCL, n);
+    k_store_file_starts<<<g, 256, 0, stream>>>(head, head_incl, n, fstart);
+    k_tilerec_slice_heads<<<g, 256, 0, stream>>>(head_incl, fstart, n, S, shead);
+    if ((rc = scan64(shead, shead_incl, n, err))) return rc;
+    HIPCHK(hipMemcpyAsync(&ns, shead_incl + (n - 1), 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (ns < nf || ns > n) {
+      if (err) *err = "tile export slice split failed";
+      return OTR_DEVICE_ERROR;
+    }
+    int64_t* pos = buf<int64_t>(T_E_POS, (size_t)ns + 1);
+    start = buf<int64_t>(T_E_START, ns);
+    tile = buf<int64_t>(T_E_TILE, ns);
+    slice = buf<int32_t>(T_E_SLICE, ns);
+    map_words = buf<uint32_t>(T_E_MAP, 5 * (size_t)nf);
+    int64_t* rec_len = buf<int64_t>(T_E_REC_LEN, ns);
+    int64_t* name_len = buf<int64_t>(T_E_NAME_LEN, ns);
+    rec_off = buf<int64_t>(T_E_REC_OFF, (size_t)ns + 1);
+    name_off = buf<int64_t>(T_E_NAME_OFF, (size_t)ns + 1);
+    k_tilerec_table<<<g, 256, 0, stream>>>(key_b, head, head_incl, fstart, nf, shead, shead_incl, n, ns, S, q, pos,
+                                           start, tile, slice, map_words);
+    k_tilerec_lens<<<tst_grid(ns, 256), 256, 0, stream>>>(pos, start, tile, slice, ns, rec_len, name_len);
+    HIPCHK(hipMemsetAsync(rec_off, 0, 8, stream));
+    HIPCHK(hipMemsetAsync(name_off, 0, 8, stream));
+    if ((rc = scan64(rec_len, rec_off + 1, ns, err))) return rc;
+    if ((rc = scan64(name_len, name_off + 1, ns, err))) return rc;
+    HIPCHK(hipMemcpyAsync(&total[0], rec_off + ns, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&total[1], name_off + ns, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (total[0] != kTileRecHeader * ns + kTileRecSegment * n || total[1] < 5 * ns || total[1] > kTileKeyMax * ns) {
+      if (err) *err = "tile export lengths failed";
+      return OTR_DEVICE_ERROR;
+    }
+    uint8_t* bytes = buf<uint8_t>(T_E_BYTES, (size_t)total[0]);
+    uint8_t* names = buf<uint8_t>(T_E_NAMES, (size_t)total[1]);
+    const int64_t n_words = total[0] / 4;
+    k_tilerec_emit<<<tst_grid(n_words, kTileRecEmit), kTileRecEmit, 0, stream>>>(rows, t0, t1, idx_b, pos, rec_off, ns,
+                                                                                 n_words, (uint32_t*)bytes);
+    k_tilerec_names<<<tst_grid(ns, 256), 256, 0, stream>>>(start, tile, slice, name_off, ns, names);
+    HIPCHK(hipGetLastError());
+    h_bytes.resize((size_t)total[0]);
+    h_names.resize((size_t)total[1]);
+    h_map.resize((size_t)(kTileMapEntry * nf));
+    HIPCHK(hipMemcpyAsync(h_bytes.data(), bytes, (size_t)total[0], hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(h_names.data(), names, (size_t)total[1], hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(h_map.data(), map_words, h_map.size(), hipMemcpyDeviceToHost, stream));
+    out->bytes = h_bytes.data();
+    out->names = h_names.data();
+    out->map_bytes = h_map.data();
+    out->d_bytes = bytes;
+    out->d_names = names;
+    out->d_map_bytes = (const uint8_t*)map_words;
+  } else {
+    HIPCHK(hipMemsetAsync(rec_off, 0, 8, stream));
+    HIPCHK(hipMemsetAsync(name_off, 0, 8, stream));
+  }
+  h_start.resize((size_t)ns);
+  h_tile.resize((size_t)ns);
+  h_slice.resize((size_t)ns);
+  h_rec_off.resize((size_t)ns + 1);
+  h_name_off.resize((size_t)ns + 1);
+  if (ns > 0) {
+    HIPCHK(hipMemcpyAsync(h_start.data(), start, 8 * (size_t)ns, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(h_tile.data(), tile, 8 * (size_t)ns, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(h_slice.data(), slice, 4 * (size_t)ns, hipMemcpyDeviceToHost, stream));
+  }
+  HIPCHK(hipMemcpyAsync(h_rec_off.data(), rec_off, 8 * ((size_t)ns + 1), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(h_name_off.data(), name_off, 8 * ((size_t)ns + 1), hipMemcpyDeviceToHost, stream));
+  float ms = 0.f;
+  if ((rc = finish(&ms, err))) return rc;
+  out->n_slices = ns;
+  out->n_bytes = total[0];
+  out->n_name_bytes = total[1];
+  out->n_tiles = nf;
+  out->start = ns ? h_start.data() : nullptr;
+  out->tile_id = ns ? h_tile.data() : nullptr;
+  out->slice = ns ? h_slice.data() : nullptr;
+  out->rec_off = h_rec_off.data();
+  out->name_off = h_name_off.data();
+  out->d_start = start;
+  out->d_tile_id = tile;
+  out->d_slice = slice;
+  out->d_rec_off = rec_off;
+  out->d_name_off = name_off;
+  return OTR_OK;
+}
+
+int TileStore::restore_records(const otr_tile_records* in, otr_tile_restore_result* out, std::string* err) {
+  int rc;
+  restore_result(out, n_rows);
+  const int64_t n = in->n_slices, nb = in->n_bytes, nt = in->n_tiles < 0 ? -1 : in->n_tiles;
+  if (n < 0 || n >= (int64_t)INT32_MAX || nb < 0 || nt >= (int64_t)INT32_MAX)
+    return bad(err, "tile records: counts out of range");
+  if (in->slice_size < 1) return bad(err, "tile records: slice_size below 1");
+  if ((n > 0 && (!in->start || !in->tile_id || !in->slice)) || !in->rec_off || (nb > 0 && !in->bytes) ||
+      (nt > 0 && !in->map_bytes))
+    return bad(err, "null argument");
+  HIPCHK(hipEventRecord(ev[0], stream));
+  TileRecIn a{};
+  a.n_slices = n;
+  a.n_bytes = nb;
+  a.q = cfg.quantisation;
+  a.slice_size = in->slice_size;
+  const uint8_t* d_map = in->map_bytes;
+  if (in->memory == OTR_MEM_DEVICE) {
+    a.start = in->start;
+    a.tile_id = in->tile_id;
+    a.slice = in->slice;
+    a.rec_off = in->rec_off;
+    a.bytes = in->bytes;
+  } else {
+    int64_t* st = buf<int64_t>(T_I_START, n);
+    int64_t* ti = buf<int64_t>(T_I_TILE, n);
+    int32_t* sl = buf<int32_t>(T_I_SLICE, n);
+    int64_t* of = buf<int64_t>(T_I_OFF, (size_t)n + 1);
+    uint8_t* by = buf<uint8_t>(T_I_BYTES, (size_t)nb);
+    if (n > 0) {
+      HIPCHK(hipMemcpyAsync(st, in->start, 8 * (size_t)n, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(ti, in->tile_id, 8 * (size_t)n, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(sl, in->slice, 4 * (size_t)n, hipMemcpyHostToDevice, stream));
+    }
+    HIPCHK(hipMemcpyAsync(of, in->rec_off, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, stream));
+    if (nb > 0) HIPCHK(hipMemcpyAsync(by, in->bytes, (size_t)nb, hipMemcpyHostToDevice, stream));
+    if (nt > 0) {
+      uint8_t* mp = buf<uint8_t>(T_I_MAP, (size_t)(kTileMapEntry * nt));
+      HIPCHK(hipMemcpyAsync(mp, in->map_bytes, (size_t)(kTileMapEntry * nt), hipMemcpyHostToDevice, stream));
+      d_map = mp;
+    }
+    a.start = st;
+    a.tile_id = ti;
+    a.slice = sl;
+    a.rec_off = of;
+    a.bytes = by;
+  }
+  // words: the records' verdict, the map's verdict, then the TRC_* counters
+  unsigned long long* words = buf<unsigned long long>(T_I_WORDS, 2 + TRC_WORDS);
+  unsigned long long h_words[2 + TRC_WORDS];
+  HIPCHK(hipMemsetAsync(words, 0xFF, 16, stream));
+  HIPCHK(hipMemsetAsync(words + 2, 0, 8 * TRC_WORDS, stream));
+  int32_t* count = buf<int32_t>(T_I_COUNT, n);
+  int32_t* key_ok = buf<int32_t>(T_I_KEY_OK, n);
+  unsigned long long* file_key = buf<unsigned long long>(T_I_FILE, n);
+  unsigned long long* file_a = buf<unsigned long long>(T_I_FILE_A, n);
+  unsigned long long* file_b = buf<unsigned long long>(T_I_FILE_B, n);
+  unsigned long long* slice_key = buf<unsigned long long>(T_I_SLICE_KEY, n);
+  unsigned long long* slice_b = buf<unsigned long long>(T_I_SLICE_B, n);
+  int32_t* idx_a = buf<int32_t>(T_I_IDX_A, n);
+  int32_t* idx_b = buf<int32_t>(T_I_IDX_B, n);
+  int32_t* order = buf<int32_t>(T_I_IDX_C, n);
+  if (n > 0) {
+    const unsigned g = tst_grid(n, 256);
+    k_tilerec_validate<<<tst_grid(n, 256 / OTR_WAVE), 256, 0, stream>>>(a, count, key_ok, file_key, slice_key, idx_a,
+                                                                        words);
+    HIPCHK(hipGetLastError());
+    // (file, slice) order, stable: by slice, then by file
+    if ((rc = sort_pairs(slice_key, slice_b, idx_a, idx_b, n, err))) return rc;
+    k_tilerec_gather<<<g, 256, 0, stream>>>(file_key, idx_b, n, file_a);
+    if ((rc = sort_pairs(file_a, file_b, idx_b, order, n, err))) return rc;
+    k_tilerec_duplicates<<<g, 256, 0, stream>>>(file_b, order, slice_key, key_ok, n, words);
+    HIPCHK(hipGetLastError());
+  }
+  unsigned long long* map_b = buf<unsigned long long>(T_M_FILE_B, nt > 0 ? nt : 1);
+  int32_t* map_order = buf<int32_t>(T_M_IDX_B, nt > 0 ? nt : 1);
+  int32_t* map_value = buf<int32_t>(T_M_VALUE, nt > 0 ? nt : 1);
+  if (nt > 0) {
+    unsigned long long* map_a = buf<unsigned long long>(T_M_FILE_A, nt);
+    int32_t* map_idx = buf<int32_t>(T_M_IDX_A, nt);
+    int32_t* map_ok = buf<int32_t>(T_M_OK, nt);
+    const unsigned gm = tst_grid(nt, 256);
+    k_tilerec_map_keys<<<gm, 256, 0, stream>>>(d_map, nt, a.q, map_a, map_idx, map_value, map_ok, words + 1,
+                                               words + 2);
+    if ((rc = sort_pairs(map_a, map_b, map_idx, map_order, nt, err))) return rc;
+    k_tilerec_map_duplicates<<<gm, 256, 0, stream>>>(map_b, map_order, map_ok, nt, words + 1);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipMemcpyAsync(h_words, words, 16, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  if (h_words[0] != kTileRecNone) {
+    out->bad_slice = (int64_t)(h_words[0] >> 8);
+    out->bad_reason = (int32_t)(h_words[0] & 0xFF);
+    return bad(err, "tile records: slice record " + std::to_string(out->bad_slice) + ": " +
+                        kTileRestoreReason[out->bad_reason]);
+  }
+  if (h_words[1] != kTileRecNone) {
+    out->bad_tile = (int64_t)h_words[1];
+    out->bad_reason = OTR_TILE_RESTORE_E_MAP;
+    return bad(err, "tile records: map entry " + std::to_string(out->bad_tile) +
+                        ": invalid key, negative value or repeated key");
+  }
+  if (n > 0) {
+    int64_t* ref = buf<int64_t>(T_I_REF, n);
+    int64_t* row_off = buf<int64_t>(T_I_ROW_OFF, (size_t)n + 1);
+    HIPCHK(hipMemsetAsync(row_off, 0, 8, stream));
+    // (the slice keys' sorted copy is free again: the join reads the keys in input order)
+    k_tilerec_join<<<tst_grid(n, 256), 256, 0, stream>>>(file_b, order, slice_key, count, n, map_b, map_order,
+                                                         map_value, nt, ref, words + 2);
+    HIPCHK(hipGetLastError());
+    if ((rc = scan64(ref, row_off + 1, n, err))) return rc;
+    HIPCHK(hipMemcpyAsync(h_words, words, sizeof(h_words), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    const int64_t total = (int64_t)h_words[2 + TRC_ROWS];
+    if (total > cfg.max_rows - n_rows) {
+      out->bad_reason = OTR_TILE_RESTORE_E_FULL;
+      return bad(err, "the restore would take the tile store beyond max_rows (" + std::to_string(n_rows) +
+                          " rows held, " + std::to_string(total) + " referenced, max_rows " +
+                          std::to_string(cfg.max_rows) + ")");
+    }
+    if (total > 0) {
+      k_tilerec_write<<<tst_grid(n, 256 / OTR_WAVE), 256, 0, stream>>>(a, order, ref, row_off, rows + n_rows,
+                                                                       timed() ? t0 + n_rows : nullptr,
+                                                                       timed() ? t1 + n_rows : nullptr);
+      HIPCHK(hipGetLastError());
+    }
+    if ((rc = finish(&out->device_ms, err))) return rc;
+    n_rows += total;
+    out->n_rows = total;
+    out->n_slices = (int64_t)h_words[2 + TRC_SLICES];
+    out->n_unreferenced_rows = (int64_t)h_words[2 + TRC_UNREF_ROWS];
+    out->n_unreferenced_slices = (int64_t)h_words[2 + TRC_UNREF_SLICES];
+  } else {
+    HIPCHK(hipMemcpyAsync(h_words, words, sizeof(h_words), hipMemcpyDeviceToHost, stream));
+    if ((rc = finish(&out->device_ms, err))) return rc;
+  }
+  if (nt >= 0) out->n_missing_slices = (int64_t)h_words[2 + TRC_NAMED] - out->n_slices;
+  out->n_rows_held = n_rows;
+  return OTR_OK;
+}
+
+}  // namespace otr
+
+// the changelog's String keys, on the host (include/otr.h; the rules are otr_tile_records.h's)
+extern "C" int otr_tile_slice_key(int64_t start, int64_t tile_id, int32_t slice, char* buf, int64_t cap) {
+  const int32_t n = otr::tile_key_len(start, tile_id, slice);
+  if (!buf || cap < n) return -1;
+  otr::tile_key_put(start, tile_id, slice, (uint8_t*)buf);
+  if (cap > n) buf[n] = 0;
+  return n;
+}
+
+extern "C" int otr_tile_slice_key_parse(const char* text, int64_t len, int64_t* start, int64_t* tile_id,
+                                        int32_t* slice) {
+  if (!text || !start || !tile_id || !slice) return 1;
+  return otr::tile_key_parse(text, len, start, tile_id, slice) ? 0 : 1;
+}
+
+namespace otr {
+
+int Matcher::tile_store_snapshot(int flags, otr_tile_snapshot* out, std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    HIPCHK(hipSetDevice(graph_state().device));
+    return tst->snapshot(flags, out, err);
+  });
+}
+
+int Matcher::tile_store_restore(const otr_tile_snapshot* snap, int memory, otr_tile_restore_result* out,
+                                std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    HIPCHK(hipSetDevice(graph_state().device));
+    return tst->restore(snap, memory, out, err);
+  });
+}
+
+int Matcher::tile_store_export_records(int32_t slice_size, otr_tile_records* out, std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    HIPCHK(hipSetDevice(graph_state().device));
+    return tst->export_records(slice_size, out, err);
+  });
+}
+
+int Matcher::tile_store_restore_records(const otr_tile_records* in, otr_tile_restore_result* out, std::string* err) {
+  return guarded(*this, err, true, [&]() -> int {
+    HIPCHK(hipSetDevice(graph_state().device));
+    return tst->restore_records(in, out, err);
   });
 }
 

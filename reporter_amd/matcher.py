@@ -90,6 +90,26 @@ def session_key(uuid_bytes):
     return int(_lib.lib().otr_uuid_key(b, len(b)))
 
 
+def tile_slice_key(start, tile_id, slice_):
+    """otr_tile_slice_key: the anonymise_tile changelog's String key of a slice record,
+    "{start}_{tile_id}.{slice}" (bytes)."""
+    buf = ctypes.create_string_buffer(64)
+    n = _lib.lib().otr_tile_slice_key(int(start), int(tile_id), int(slice_), buf, 64)
+    if n < 0:
+        raise RuntimeError('otr_tile_slice_key failed')
+    return buf.raw[:n]
+
+
+def tile_slice_key_parse(text):
+    """otr_tile_slice_key_parse: (start, tile_id, slice) of a changelog key exactly as
+    Long.toString / Integer.toString print it; ValueError for anything else."""
+    b = text.encode() if isinstance(text, str) else bytes(text)
+    a, t, s = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+    if _lib.lib().otr_tile_slice_key_parse(b, len(b), ctypes.byref(a), ctypes.byref(t), ctypes.byref(s)) != 0:
+        raise ValueError('not a tile slice key: %r' % b)
+    return a.value, t.value, s.value
+
+
 JAVA_TIME_PATTERN = 'yyyy-MM-dd HH:mm:ss'
 
 
@@ -658,12 +678,113 @@ class Matcher:
         return _lib.snapshot_to_numpy(r)
 
     # --- tile store (include/otr.h otr_tile_store_*) -----------------
-    def tile_store_open(self, max_rows, quantisation=3600, privacy=1):
-        """Open this matcher's tile store: the streaming path's anonymiser stage in HBM."""
+    def tile_store_open(self, max_rows, quantisation=3600, privacy=1, times=False):
+        """Open this matcher's tile store: the streaming path's anonymiser stage in HBM.
+        times=True (otr_tile_store_open_ex with OTR_TILE_STORE_TIMES): the store keeps every
+        report's t0 and t1 beside its rows, which tile_store_export_records needs."""
         c = _lib.TileStoreConfig()
         c.max_rows, c.quantisation, c.privacy = int(max_rows), int(quantisation), int(privacy)
-        self._check(self._L.otr_tile_store_open(self._h, ctypes.byref(c)), 'otr_tile_store_open')
+        if times:
+            self._check(self._L.otr_tile_store_open_ex(self._h, ctypes.byref(c), _lib.OTR_TILE_STORE_TIMES),
+                        'otr_tile_store_open_ex')
+        else:
+            self._check(self._L.otr_tile_store_open(self._h, ctypes.byref(c)), 'otr_tile_store_open')
         self._tile_quantisation = int(quantisation)
+        self._tile_times = bool(times)
+
+    # --- tile store: snapshot, restore, records (include/otr.h, DESIGN.md §3 item 19) --------
+    def _tile_restore_check(self, rc, r, what):
+        if rc == _lib.OTR_BAD_REQUEST and r.bad_reason:
+            where = 'slice %d: ' % r.bad_slice if r.bad_slice >= 0 else \
+                'map entry %d: ' % r.bad_tile if r.bad_tile >= 0 else ''
+            e = ValueError('%s refused: %s%s (%s)' % (what, where, _lib.TILE_RESTORE_REASONS.get(r.bad_reason, r.bad_reason),
+                                                     _lib.last_error()))
+            e.result = _lib.tile_restore_to_dict(r)
+            raise e
+        self._check(rc, what)
+        return _lib.tile_restore_to_dict(r)
+
+    def tile_store_snapshot(self, host=True):
+        """otr_tile_store_snapshot: the held rows in arrival order (rows, and t0 / t1 or None),
+        n_rows, quantisation, flags and the device pointers d_rows, d_t0, d_t1 (matcher-owned
+        until its next tile-store call); host=False: device pointers only.  The store is untouched."""
+        r = _lib.TileSnapshot()
+        self._check(self._L.otr_tile_store_snapshot(self._h, 0 if host else _lib.OTR_TILE_SNAPSHOT_NO_HOST,
+                                                    ctypes.byref(r)), 'otr_tile_store_snapshot')
+        return _lib.tile_snapshot_to_numpy(r, host)
+
+    def tile_store_restore(self, snapshot, device=False):
+        """otr_tile_store_restore: the rows of a snapshot dict appended to the held rows, all or
+        nothing.  device=True: the dict's d_rows, d_t0, d_t1 and n_rows are used.  A refusal
+        raises ValueError (its .result holds bad_slice and bad_reason)."""
+        s, r = _lib.TileSnapshot(), _lib.TileRestoreResult()
+        if device:
+            s.n_rows = int(snapshot['n_rows'])
+            s.rows, s.t0, s.t1 = (int(snapshot.get('d_' + k) or 0) or None for k in ('rows', 't0', 't1'))
+        else:
+            rows = np.ascontiguousarray(snapshot['rows'], dtype=_lib.TILE_ROW)
+            keep = [rows]
+            s.n_rows, s.rows = len(rows), (rows.ctypes.data if len(rows) else None)
+            if snapshot.get('t0') is not None:
+                a, b = (np.ascontiguousarray(snapshot[k], np.float64) for k in ('t0', 't1'))
+                if len(a) != len(rows) or len(b) != len(rows):
+                    raise ValueError('tile snapshot: arrays of different lengths')
+                keep += [a, b]
+                s.t0, s.t1 = (a.ctypes.data, b.ctypes.data) if len(rows) else (None, None)
+            self._keep = keep
+        rc = self._L.otr_tile_store_restore(self._h, ctypes.byref(s), _lib.OTR_MEM_DEVICE if device else _lib.OTR_MEM_HOST,
+                                            ctypes.byref(r))
+        return self._tile_restore_check(rc, r, 'otr_tile_store_restore')
+
+    def tile_store_export_records(self, slice_size=20000):
+        """otr_tile_store_export_records (a store opened with times=True): the held rows as the
+        reference's slice records and map entries, _lib.tile_records_to_numpy's dict plus the
+        store's 'quantisation'.  The store is untouched."""
+        r = _lib.TileRecords()
+        self._check(self._L.otr_tile_store_export_records(self._h, int(slice_size), ctypes.byref(r)),
+                    'otr_tile_store_export_records')
+        out = _lib.tile_records_to_numpy(r)
+        out['quantisation'] = self._tile_quantisation
+        return out
+
+    def tile_store_restore_records(self, records, device=False, use_map=True):
+        """otr_tile_store_restore_records.  records: dict of start, tile_id, slice, rec_off, bytes,
+        slice_size and, with use_map, map_bytes (missing or None: no map); device=True: the
+        dict's d_* device addresses with n_slices, n_bytes and n_tiles.  The bytes may start at
+        any address.  Returns the restore's counts; a refusal raises ValueError (.result)."""
+        c, r = _lib.TileRecords(), _lib.TileRestoreResult()
+        c.slice_size = int(records['slice_size'])
+        has_map = use_map and records.get('d_map_bytes' if device else 'map_bytes') is not None
+        if device:
+            c.n_slices, c.n_bytes, c.memory = int(records['n_slices']), int(records['n_bytes']), _lib.OTR_MEM_DEVICE
+            for k in ('start', 'tile_id', 'slice', 'rec_off', 'bytes'):
+                setattr(c, k, int(records['d_' + k]) or None)
+            c.n_tiles = int(records['n_tiles']) if has_map else -1
+            c.map_bytes = (int(records['d_map_bytes']) or None) if has_map else None
+        else:
+            st = np.ascontiguousarray(records['start'], np.int64)
+            ti = np.ascontiguousarray(records['tile_id'], np.int64)
+            sl = np.ascontiguousarray(records['slice'], np.int32)
+            of = np.ascontiguousarray(records['rec_off'], np.int64)
+            data = records['bytes']
+            d = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
+            if len(of) != len(st) + 1 or len(ti) != len(st) or len(sl) != len(st):
+                raise ValueError('tile records: arrays of different lengths')
+            keep = [st, ti, sl, of, d]
+            c.n_slices, c.n_bytes, c.memory = len(st), len(d), _lib.OTR_MEM_HOST
+            c.start, c.tile_id, c.slice = (a.ctypes.data if len(st) else None for a in (st, ti, sl))
+            c.rec_off, c.bytes = of.ctypes.data, (d.ctypes.data if len(d) else None)
+            c.n_tiles = -1
+            if has_map:
+                mb = records['map_bytes']
+                mp = np.frombuffer(mb, np.uint8) if isinstance(mb, (bytes, bytearray)) else np.ascontiguousarray(mb, np.uint8)
+                if len(mp) % 20:
+                    raise ValueError('tile records: map_bytes is not a multiple of 20 bytes')
+                keep.append(mp)
+                c.n_tiles, c.map_bytes = len(mp) // 20, (mp.ctypes.data if len(mp) else None)
+            self._keep = keep
+        rc = self._L.otr_tile_store_restore_records(self._h, ctypes.byref(c), ctypes.byref(r))
+        return self._tile_restore_check(rc, r, 'otr_tile_store_restore_records')
 
     def tile_store_close(self):
         self._check(self._L.otr_tile_store_close(self._h), 'otr_tile_store_close')

@@ -413,8 +413,9 @@ def stream_text_tiles(matcher, chunks, fmt, end_ts, mode='auto', source='reporte
 def save_sessions(matcher, path):
     """The open session store's state as one .npz of (key, rec_off, bytes): every live session as
     the value Batch.Serder writes for it (Matcher.sessions_export_records).  With load_sessions
-    this lets stream_text_tiles go on after a restart where the saved process stopped between two
-    chunks.  A store with a uuid directory also saves its names (name_off, name_bytes: the
+    the sessions go on after a restart where the saved process stopped between two chunks; the
+    tile store's unflushed rows are the other half of that state: save_tiles / load_tiles.
+    A store with a uuid directory also saves its names (name_off, name_bytes: the
     changelog key of record i).  Returns the number of sessions saved."""
     r = matcher.sessions_export_records()
     extra = {}
@@ -438,6 +439,36 @@ def load_sessions(matcher, path):
             off = z['name_off']
             names = {'bytes': z['name_bytes'], 'off': off[:-1], 'len': np.diff(off).astype(np.int32)}
         return matcher.sessions_restore_records(z['key'], z['rec_off'], z['bytes'], names=names)
+
+
+TILE_SAVE_ARRAYS = ('start', 'tile_id', 'slice', 'rec_off', 'bytes', 'map_bytes')
+
+
+def save_tiles(matcher, path, slice_size=20000):
+    """The open tile store's unflushed rows (a store opened with times=True) as one .npz of the
+    reference's changelog records (Matcher.tile_store_export_records): the slice records' keys,
+    offsets and Segment.ListSerder bytes, the slice map's entries, the slice_size and the store's
+    quantisation.  With save_sessions and the two loads this lets stream_text_tiles go on after a
+    restart with the output of an uninterrupted run.  Returns the number of rows saved."""
+    r = matcher.tile_store_export_records(slice_size)
+    with open(path, 'wb') as f:
+        np.savez(f, slice_size=np.int64(r['slice_size']), quantisation=np.int64(r['quantisation']),
+                 **{k: r[k] for k in TILE_SAVE_ARRAYS})
+    return (int(r['n_bytes']) - 4 * int(r['n_slices'])) // 40
+
+
+def load_tiles(matcher, path):
+    """The rows of a save_tiles file appended to the matcher's open tile store
+    (Matcher.tile_store_restore_records: all or nothing).  ValueError when the restore is refused
+    or the file's quantisation is not the open store's.  Returns the restore's counts."""
+    with np.load(path) as z:
+        q = int(z['quantisation'])
+        if q != int(matcher._tile_quantisation):
+            raise ValueError('load_tiles: the file was saved at quantisation %d, the open store has %d'
+                             % (q, matcher._tile_quantisation))
+        rec = {k: z[k] for k in TILE_SAVE_ARRAYS}
+        rec['slice_size'] = int(z['slice_size'])
+        return matcher.tile_store_restore_records(rec)
 
 
 def _exchange_by_file_owner(buf, itemsize, world, group=None):

@@ -55,6 +55,15 @@ stream_tile_payloads_device, both as host wall time ending in the {name: text} d
 path's device_ms (flush + text stage) beside it; median [min, max].
 
     python -m reporter_amd.tools.sessions_rate --traces 2000 --tile-store --text --out profiles/tile_text_c2dep.json
+
+`--tile-store --records` times the tile store's state leaving and coming back (K20) on a store with
+the times: export_records, restore_records from device and from host arrays, and snapshot +
+restore, on the replay's held rows at the stream's midpoint and on `--tile-rows` synthetic rows,
+each beside a plain device-to-device copy of the record bytes and beside the host path (snapshot to
+the host plus the Python restatement, on at most 65536 rows); and one add on a store with the
+times against the same add on a plain store.
+
+    python -m reporter_amd.tools.sessions_rate --traces 2000 --tile-store --records --out profiles/tile_records_c2dep.json
 """
 import argparse
 import json
@@ -354,6 +363,115 @@ def restore_rates(m, pts, max_points, repeats):
     return out
 
 
+def synthetic_reports(n, files=300, q=3600):
+    """n valid reports over `files` (bucket, tile) files, one row each, as one window."""
+    k = np.arange(n, dtype=np.int64)
+    tile = (k % files).astype(np.uint64)
+    idx = ((k // files) % 50).astype(np.uint64)
+    sid = np.uint64(1) | (tile << np.uint64(3))
+    t0 = T_BEGIN + 10.0 + (k % 3000) + 0.25 * (k % 4)
+    return {'rep_off': np.array([0, n], np.int64), 'id': sid | (idx << np.uint64(25)),
+            'next_id': sid | ((idx + np.uint64(1)) << np.uint64(25)), 't0': t0, 't1': t0 + 2.5 + (k % 7),
+            'length': (40 + k % 400).astype(np.int32), 'queue_length': (k % 3).astype(np.int32)}
+
+
+def records_rates(m, M, fill, repeats, slice_size=20000, host_rows=1 << 16):
+    """fill(m, times) leaves m's tile store open and filled.  Device time (HIP events on the
+    matcher's stream around the call, so host copies are inside) and wall time of the export, of
+    restore_records from the export's device arrays and from its host arrays, of snapshot + restore
+    into a second matcher's store, beside a plain device-to-device copy of the record bytes; and
+    the host path on the first `host_rows` held rows: snapshot to the host plus the Python
+    restatement (tests/tile_records_ref.py)."""
+    import torch
+    from tests import tile_records_ref as X
+    fill(m, True)
+    n = m.tile_store_snapshot(host=False)['n_rows']
+    m2 = M.Matcher()
+
+    def timed(f, matcher=m):
+        s = torch.cuda.ExternalStream(matcher.stream)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record(s)
+        r = f()
+        e1.record(s)
+        e1.synchronize()
+        return r, e0.elapsed_time(e1), 1e3 * (time.perf_counter() - t0)
+
+    def mmm(v):
+        v = sorted(v)
+        return [round(float(np.median(v)), 3), round(v[0], 3), round(v[-1], 3)]
+
+    t = {k: [] for k in ('export', 'restore_records_device', 'restore_records_host', 'snapshot_device', 'restore_rows_device',
+                         'copy_d2d')}
+    w = {k: [] for k in t}
+    for i in range(repeats + 1):
+        rec, a, b = timed(lambda: m.tile_store_export_records(slice_size))
+        snap, c, d = timed(lambda: m.tile_store_snapshot(host=False))
+        runs = {'export': (a, b), 'snapshot_device': (c, d)}
+        for kind in ('restore_records_device', 'restore_records_host', 'restore_rows_device'):
+            m2.tile_store_open(max(n, 1), 3600, 2, times=True)
+            if kind == 'restore_rows_device':
+                r, a, b = timed(lambda: m2.tile_store_restore(snap, device=True), m2)
+            else:
+                r, a, b = timed(lambda: m2.tile_store_restore_records(rec, device=kind.endswith('device')), m2)
+            assert r['n_rows'] == n, (kind, r, n)
+            m2.tile_store_close()
+            runs[kind] = (a, b)
+        src = torch.empty(max(rec['n_bytes'], 1), dtype=torch.uint8, device='cuda')
+        dst = torch.empty_like(src)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record()
+        dst.copy_(src)
+        e1.record()
+        e1.synchronize()
+        runs['copy_d2d'] = (e0.elapsed_time(e1), 1e3 * (time.perf_counter() - t0))
+        if i:   # the first pass is the warm-up
+            for k, (a, b) in runs.items():
+                t[k].append(a)
+                w[k].append(b)
+    out = {'rows': n, 'slice_size': slice_size, 'slices': rec['n_slices'], 'files': rec['n_tiles'],
+           'record_bytes': rec['n_bytes'], 'snapshot_bytes': 72 * n}
+    for k in t:
+        out[k + '_device_ms_median_min_max'] = mmm(t[k])
+        out[k + '_wall_ms_median_min_max'] = mmm(w[k])
+    # the host path: the rows and times to the host, the restatement writes and reads the bytes
+    t0 = time.perf_counter()
+    s = m.tile_store_snapshot()
+    snap_ms = 1e3 * (time.perf_counter() - t0)
+    h = min(n, host_rows)
+    held = (s['rows'][:h], s['t0'][:h], s['t1'][:h])
+    t0 = time.perf_counter()
+    hrec = X.export(held, 3600, slice_size)
+    exp_ms = 1e3 * (time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    X.restore_records(X.empty_held(), hrec, 3600, h)
+    res_ms = 1e3 * (time.perf_counter() - t0)
+    out['host_path'] = {'snapshot_to_host_wall_ms': round(snap_ms, 3), 'rows_restated': h,
+                        'python_export_wall_ms': round(exp_ms, 1), 'python_restore_wall_ms': round(res_ms, 1)}
+    m.tile_store_close()
+    return out
+
+
+def add_times(m, reports, max_rows, repeats):
+    """The same add on a plain store and on a store with the times: device_ms, median [min, max]."""
+    out = {}
+    for times in (False, True):
+        v = []
+        for i in range(repeats + 1):
+            m.tile_store_open(max_rows, 3600, 2, times=times)
+            r = m.tile_store_add_reports(reports)
+            m.tile_store_close()
+            if i:
+                v.append(r['device_ms'])
+        v = sorted(v)
+        out['timed_add_ms' if times else 'plain_add_ms'] = [round(float(np.median(v)), 3), round(v[0], 3), round(v[-1], 3)]
+    out['rows'] = r['n_rows_added']
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--traces', type=int, default=2000, help='traces of the c2dep workload (bench.py --json-traces)')
@@ -369,6 +487,8 @@ def main():
                          'no value, with --tile-store: time the flush to file payloads on the host and on the device')
     ap.add_argument('--restore', action='store_true',
                     help='time snapshot, export, take-all and the two restores on the store at the midpoint')
+    ap.add_argument('--records', action='store_true',
+                    help='with --tile-store: time export, restore_records and snapshot + restore of the tile store')
     ap.add_argument('--names', action='store_true',
                     help='the store has the uuid directory: every point is pushed with a 36-byte name')
     ap.add_argument('--graph', choices=['metro', 'city'], default='metro')
@@ -401,6 +521,41 @@ def main():
                'method': '1 warm-up, %d timed; median [min, max]; device_ms of the call, or HIP events on the '
                          "matcher's stream around it" % args.repeats,
                'restore': restore_rates(m, pts, args.max_points, args.repeats)}
+        line = json.dumps(res, indent=1)
+        print(line)
+        if args.out:
+            with open(args.out, 'w') as f:
+                f.write(line + '\n')
+        return
+    if args.records:
+        if not args.tile_store:
+            ap.error('--records goes with --tile-store')
+        sec = (pts['time'] - pts['time'][0]) // 10
+        cuts = [0] + (np.flatnonzero(np.diff(sec)) + 1).tolist() + [n]
+        half = cuts[:len(cuts) // 2 + 1]
+        syn = synthetic_reports(args.tile_rows)
+
+        def fill_replay(mm, times):
+            mm.sessions_open(int(pts['key'].max()) + 1, args.max_points)
+            mm.tile_store_open(args.tile_rows, 3600, 2, times=times)
+            for a, b in zip(half[:-1], half[1:]):
+                mm.sessions_push({k: v[a:b] for k, v in pts.items()})
+                mm.tile_store_add_session()
+            mm.sessions_close()
+
+        def fill_synthetic(mm, times):
+            mm.tile_store_open(args.tile_rows, 3600, 2, times=times)
+            mm.tile_store_add_reports(syn)
+
+        res = {'workload': 'c2dep: %s graph, %d traces x 100 probes @15 s, sigma 10 m, deployed configuration, 10 s '
+                           'chunks to the midpoint; and %d synthetic reports over 300 files'
+                           % (args.graph, args.traces, args.tile_rows),
+               'method': '1 warm-up pass, %d timed; median [min, max]; device time: HIP events on the matcher\'s stream '
+                         'around the call (its copies to the host included); restores go into a second matcher\'s '
+                         'empty store with the times' % args.repeats,
+               'tile_records': {'replay_midpoint': records_rates(m, M, fill_replay, args.repeats),
+                                'synthetic': records_rates(m, M, fill_synthetic, args.repeats),
+                                'add_timed_against_plain': add_times(m, syn, args.tile_rows, args.repeats)}}
         line = json.dumps(res, indent=1)
         print(line)
         if args.out:
