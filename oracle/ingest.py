@@ -45,9 +45,14 @@ def _py2_float(s, overflow_ok=False):
 
 
 def _py2_int(s):
+    """int() without '_' separators; a Python 2 long beyond int64 is refused (a divergence the
+    device path keeps: its times and accuracies are 64-bit)."""
     if '_' in s:
         raise ValueError(s)
-    return int(s)
+    v = int(s)
+    if not -2 ** 63 <= v < 2 ** 63:
+        raise ValueError(s)
+    return v
 
 
 def py2_str_float(x):
@@ -186,6 +191,12 @@ def _java_time(s, time_format):
     return v, None
 
 
+def _f32(v):
+    """floatValue(): the double rounded to a float (beyond its range: infinite), as a double."""
+    with np.errstate(over='ignore'):
+        return float(np.float32(v))
+
+
 def java_sv_records(text, idx=(1, 0, 9, 10, 5), sep='|', time_format='ymdhms'):
     recs = []
     for n, message in enumerate(_lines(text)):
@@ -195,18 +206,18 @@ def java_sv_records(text, idx=(1, 0, 9, 10, 5), sep='|', time_format='ymdhms'):
         except IndexError:
             raise IngestError(n, 'fields')
         try:
-            la = float(np.float32(_py2_float(lat)))
-            lo = float(np.float32(_py2_float(lon)))
+            la, lo = _f32(_py2_float(lat)), _f32(_py2_float(lon))
         except ValueError:
             raise IngestError(n, 'float')
         t, why = _java_time(tm, time_format)
         if why:
             raise IngestError(n, why)
         try:
-            af = float(np.float32(_py2_float(acc)))
+            af = _f32(_py2_float(acc))
         except ValueError:
             raise IngestError(n, 'accuracy')
-        a = math.ceil(af)
+        # (int)Math.ceil(float): the cast saturates, at an infinite float too
+        a = (2 ** 31 - 1 if af > 0 else -2 ** 31) if math.isinf(af) else math.ceil(af)
         a = max(min(a, 2 ** 31 - 1), -2 ** 31)
         if abs(a) > 1 << 24:
             raise IngestError(n, 'accuracy')

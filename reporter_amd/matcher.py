@@ -359,6 +359,8 @@ class Matcher:
         if time_format is None:
             time_format = _lib.OTR_TIME_EPOCH if rules == _lib.OTR_INGEST_SHARD else _lib.OTR_TIME_YMDHMS
         f.time_format = int(time_format)
+        if not 0 <= int(inactivity) < 1 << 31:   # an int32 in the C-ABI: refused, never wrapped
+            raise ValueError('inactivity out of range: %r' % (inactivity,))
         f.inactivity = int(inactivity)
         f.mode = {'auto': 0, 'bicycle': 1, 'pedestrian': 2}[mode] if isinstance(mode, str) else int(mode)
         if bbox is not None:

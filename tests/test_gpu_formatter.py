@@ -3,7 +3,9 @@ otr_sessions_push_text) against its restatement tests/formatter_ref.py: the corp
 smallest shapes bit for bit, in host and device memory, with offsets and with newlines; the city
 stream pushed as SV and as JSON text against sessions_push of the restated points; the whole
 text → tile files chain; refusals; and otr_ingest / match_batch unmoved by formatter calls.  What
-the corpus covers is pinned by tests/test_formatter_cpu.py.  One child process per job."""
+the corpus covers is pinned by tests/test_formatter_cpu.py.  The numerals of tests/ingest_cases.py
+(pinned by tests/test_ingest_cases_cpu.py) go through as psv coordinates: the only place where
+k_format_parse's compile of the number parsers meets them.  One child process per job."""
 import os
 import pickle
 import subprocess
@@ -85,6 +87,18 @@ BAD = {'psv': (b'not a message', b'2017-01-01 00:00:00|veh-1000||||1e30||||1|2',
                b'2017-13-01 00:00:00|veh-1000||||1||||1|2'),
        'json': (b'not a message', b'{"id":"veh-1000","latitude":1e1,"longitude":2,"timestamp":5,"accuracy":1}', b'',
                 b'{"id":"veh-1000","latitude":1,"longitude":2,"timestamp":5,"accuracy":1} x', b'{"id":"veh-1000"}')}
+
+
+def numeral_messages():
+    """The numerals of tests/ingest_cases.py as psv messages, each the latitude of one message and
+    the longitude of the next; those that end in a drop or a refusal stand between plain ones."""
+    from tests import ingest_cases as ic
+    n = ic.numerals()
+    nums = list(n['main'])
+    for s in n['refused'] + n['py2_refused'] + n['rejected'] + n['non_finite'] + n['in_texts']:
+        nums += [s, '1.5']
+    return [('2017-01-01 06:05:40|veh-%d||||5||||%s|%s' % (i % 3, s, nums[i - 1])).encode('latin-1')
+            for i, s in enumerate(nums)]
 
 
 def push_stream(graph_dir, fmt_name):
@@ -172,6 +186,11 @@ elif job == 'edges':
     m = M.Matcher()
     for i, (name, fname, text, off) in enumerate(T.edge_cases()):
         out[name] = fmt_call(m, text, F.FORMATS[fname], off, 5, device=i %% 2 == 1)
+elif job == 'numerals':
+    M.configure(M.default_config(gen.graph_path('tiny', graph_dir)))
+    m = M.Matcher()
+    text, off, seen = T.case_text(T.numeral_messages(), True)
+    out['numerals'] = fmt_call(m, text, F.FORMATS['psv'], off, 5, device=False)
 elif job.startswith('push'):
     fname = {'push_sv': 'psv', 'push_json': 'json'}[job]
     fmt = F.FORMATS[fname]
@@ -353,6 +372,28 @@ def test_edges(run_job):
     assert r['bytes16']['n_points'] == 1 and r['bytes15']['n_dropped'] == 1
     assert r['all_dropped']['n_dropped'] == 65 and r['all_dropped']['n_points'] == 0
     assert r['json257']['n_messages'] == 257 and kept > 1000
+
+
+def test_ingest_numerals(run_job):
+    """Every numeral of tests/ingest_cases.py as a psv latitude and longitude: kept with the float
+    of Python's own float(), refused where w and w + 1 disagree, dropped where the grammar fails
+    or the value is not finite."""
+    from tests import ingest_cases as ic
+    r = run_job('numerals')
+    text, off, seen = case_text(numeral_messages(), True)
+    want = _check_format(r['numerals'], text, seen, F.FORMATS['psv'], 5, 'numerals')
+    n = ic.numerals()
+    status = want['status'].tolist()
+    bad = len(n['rejected']) + len(n['non_finite']) + len(n['in_texts'])
+    # (the empty numeral as the last field is a trailing empty string: String.split drops it)
+    assert (status.count(F.U_PRECISION), status.count(F.D_FLOAT), status.count(F.D_FIELDS)) == (
+        2 * len(n['refused']), 2 * bad - 1, 1)
+    assert status.count(0) == len(seen) - 2 * len(n['refused']) - 2 * bad
+    with np.errstate(over='ignore'):
+        main = np.array([float(s) for s in n['main']]).astype(np.float32)
+    got = r['numerals']
+    assert not any(status[:len(main)]) and got['lat'][:len(main)].tobytes() == main.tobytes()
+    assert got['lon'][1:len(main)].tobytes() == main[:-1].tobytes()
 
 
 @pytest.mark.parametrize('job', ['push_sv', 'push_json'])
