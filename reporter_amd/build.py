@@ -78,7 +78,11 @@ def build_otr(force=False, stamps=False, variant=None, defines=()):
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')]
     headers += [os.path.join(ROOT, 'include', f) for f in os.listdir(os.path.join(ROOT, 'include'))]
     objs, jobs = [], []
-    for src in ('otr_engine.hip', 'otr_sessions.hip', 'otr_tilestore.hip', 'otr_api.cpp', 'otr_service.cpp', 'otr_graph_build.cpp'):
+    # (every unit gets the variant's -D flags, though only otr_engine.hip reads them: otr_tiles.hip
+    # and otr_text.hip see none of OTR_FORCE_RETRY, OTR_FORCE_GENERAL, OTR_ND_*, OTR_PCAP* or
+    # OTR_E1PCAP, so their objects are the same code in all three builds)
+    for src in ('otr_engine.hip', 'otr_tiles.hip', 'otr_text.hip', 'otr_sessions.hip', 'otr_tilestore.hip',
+                'otr_api.cpp', 'otr_service.cpp', 'otr_graph_build.cpp'):
         s = os.path.join(CSRC, src)
         o = os.path.join(BUILD, src + suffix + '.o')
         objs.append(o)

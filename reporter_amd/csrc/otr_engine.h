@@ -1,6 +1,9 @@
-// otr_engine.h — host-side engine: HBM graph replica, per-matcher workspace and the
-// batched pipeline (K0..K8).  Internal C++ interface between otr_engine.hip and the
-// C-ABI in otr_api.cpp.
+// otr_engine.h — host-side engine: HBM graph replica, per-matcher workspace and the stages
+// that run on it.  Internal C++ interface between the C-ABI in otr_api.cpp and the units that
+// define Matcher's members: otr_engine.hip (configure, the workspace, the batched pipeline
+// K0..K9, K12, K13, report_lists_device), otr_tiles.hip (tile cull K10, keyed histogram),
+// otr_text.hip (probe ingest K11, stream formatter K16), otr_sessions.hip (K14, K17, K18) and
+// otr_tilestore.hip (K15, K19, K20).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +13,7 @@
 
 #include "../../include/otr.h"
 #include "otr_device.h"
+#include "otr_hostdev.h"
 #include "otr_tiers.h"
 
 namespace otr {
@@ -63,11 +67,6 @@ struct ReportLists {
 
 int report_lists_device(const ReportLists& h, std::string* err);
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
 // one tier of global-memory search slabs (otr_general.h), owned by a matcher
 struct GSlab {
   uint32_t* key = nullptr;
@@ -117,7 +116,7 @@ struct Matcher {
   SessionStore* ses = nullptr;  // the session store (otr_sessions_open), owned
   TileStore* tst = nullptr;     // the tile store (otr_tile_store_open), owned
   TileText* ttx = nullptr;      // the file texts of the last otr_tiles_text / flush_text, owned
-  std::vector<DevBuf> bufs;
+  DevPool pool{PoolOwner::matcher, nullptr, 0};  // the workspace slots (otr_slots.h), sized at first use
   GSlab gslab[2];
   std::vector<int32_t> h_turn;
   // host result storage (OTR_BATCH_COPY_OUT)
@@ -146,7 +145,9 @@ struct Matcher {
   std::vector<uint32_t> h_tr_edge, h_tr_way;
   std::vector<uint64_t> h_tr_seg;
   std::vector<double> h_tr_f0, h_tr_f1, h_tr_t0, h_tr_t1;
-  hipEvent_t ev[kEvents];  // 0..19 batch stages, 20..23 ingest, a pair per route tier slot, K12's and K13's pairs (otr_tiers.h)
+  // 0..19 the batch stages and, from kEvents' layout (otr_tiers.h), a pair per route tier slot and
+  // K12's and K13's pairs: otr_engine.hip; 20..23 ingest and the formatter: otr_text.hip
+  hipEvent_t ev[kEvents];
   bool ev_init = false;
 
   template <class T>
@@ -161,7 +162,7 @@ struct Matcher {
   bool release_optional();
   bool opt_busy = false;
   // entry points: a device allocation failure inside returns OTR_DEVICE_ERROR (no kernel
-  // runs on a missing buffer); the *_impl bodies do the work
+  // runs on a missing buffer): each body runs under guarded() (otr_hostdev.h)
   int run(const otr_trace_batch* in, const ModeParams& mp, otr_batch_result* out, std::string* err);
   int matched_points(otr_point_result* out, std::string* err) const;  // of the last run (host only)
   int edge_traversals(otr_traversal_result* out, std::string* err) const;  // of the last run (host only)
@@ -170,26 +171,14 @@ struct Matcher {
                  int64_t* n_out, std::string* err);
   int hist_reduce(const void* in, int64_t n, int memory, int rows_in, int privacy, const otr_hist_entry** out,
                   int64_t* n_out, std::string* err);
-  int run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch_result* out, std::string* err);
-  int tiles_cull_impl(const otr_tile_row* rows, int64_t n, int memory, int privacy, int rules,
-                      const otr_tile_row** out, int64_t* n_out, std::string* err);
   // sort + cull of rows already in HBM, results left in HBM (the tile store's flush)
   int cull_device(const otr_tile_row* d_in, int64_t n, int privacy, int rules, CulledRows* out, std::string* err);
-  int cull_device_impl(const otr_tile_row* d_in, int64_t n, int privacy, int rules, CulledRows* out,
-                       std::string* err);
-  int edge_observations_impl(int quantisation, otr_hist_entry** d_entries, int64_t* n, std::string* err);
-  int hist_reduce_impl(const void* in, int64_t n, int memory, int rows_in, int privacy, const otr_hist_entry** out,
-                       int64_t* n_out, std::string* err);
-  int ingest_impl(const char* text, int64_t len, int memory, const otr_ingest_format* fmt, otr_ingest_result* out,
-                  std::string* err);
   int copy_out(void* dst, const void* src, size_t bytes, int dst_memory, std::string* err);
   int ingest(const char* text, int64_t len, int memory, const otr_ingest_format* fmt, otr_ingest_result* out,
              std::string* err);
   // the stream formatter (K16, otr_formatter.h): raw messages → keyed points in HBM
   int format_messages(const otr_message_format* fmt, const otr_messages* msgs, otr_format_result* out,
                       std::string* err);
-  int format_messages_impl(const otr_message_format* fmt, const otr_messages* msgs, otr_format_result* out,
-                           std::string* err);
   // the session store (K14, otr_sessions.hip)
   // (uuid_bytes > 0: with the uuid directory, K18; names: non-null on such a store only)
   int sessions_open(const otr_session_config* cfg, int32_t uuid_bytes, std::string* err);

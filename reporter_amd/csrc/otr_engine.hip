@@ -1,7 +1,7 @@
-// otr_engine.hip — graph upload (flattened CSR + grid → HBM) and the batched
-// matching pipeline on one HIP stream.  Kernels: otr_kernels.h.
-#include <hipcub/hipcub.hpp>
-
+// otr_engine.hip — graph upload (flattened CSR + grid → HBM), the matcher's workspace and the
+// batched matching pipeline on one HIP stream (Batch, K0..K9, K12, K13), the edge observations of
+// K13's traversals and report_lists_device.  Kernels: otr_kernels.h.  The tile stages are in
+// otr_tiles.hip, probe ingest and the stream formatter in otr_text.hip.
 #include <cerrno>
 #include <cstdio>
 #include <cstring>
@@ -10,27 +10,18 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include "otr_devscan.h"
 #include "otr_engine.h"
 #include "otr_kernels.h"
 #include "otr_edge.h"
 #include "otr_edge1.h"
-#include "otr_ingest.h"
-#include "otr_formatter.h"
 #include "otr_launch.h"
 #include "otr_points.h"
+#include "otr_slots.h"
 #include "otr_traversals.h"
 
 namespace otr {
 static_assert(kTraceWaves == 4, "grid_trace_rows (otr_launch.h) assumes 4 traces per block");
-
-#define HIPCHK(x)                                                                        \
-  do {                                                                                   \
-    hipError_t e_ = (x);                                                                 \
-    if (e_ != hipSuccess) {                                                              \
-      if (err) *err = std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x;    \
-      return OTR_DEVICE_ERROR;                                                           \
-    }                                                                                    \
-  } while (0)
 
 void finalize_params(MatchParams* p) {
   p->inv2s2 = 1.0 / (p->sigma_z * p->sigma_z * 2.0);
@@ -398,141 +389,25 @@ int engine_configure(const Config& cfg, std::string* err) {
 // workspace slots
 // ---------------------------------------------------------------------------------
 
-enum Slot {
-  S_TRACE_OFF, S_LAT, S_LON, S_TIME, S_ACC, S_MODE,
-  S_STATE_CNT, S_TRACE_STATE_OFF, S_STATE_PROBE, S_STATE_TRACE,
-  S_CAND_EDGE, S_CAND_P, S_CAND_SQD, S_CAND_COUNT, S_CAND_RADIUS,
-  S_PREV, S_G, S_BOUND, S_FORCED, S_NTASK, S_NTRANS, S_TASK_OFF, S_TRANS_OFF, S_NTASK4, S_TASK4_OFF, S_NTASK8, S_TASK8_OFF, S_UNIT,
-  S_TASK_STATE, S_TASK_MASK, S_TASK_OVF, S_TRANS,
-  S_BP, S_BRK, S_END_WIN, S_WINNER, S_SUBPATH,
-  S_PATH_OFF, S_PATH_LEN, S_PATH, S_STEP_OVF,
-  S_CAP, S_CAP_OFF, S_POS, S_ACT, S_ENT, S_SUBA, S_SUBB, S_POR_E, S_POR_S0, S_POR_S1, S_POR_SA, S_GSTART,
-  S_ROUTE, S_ROUTE_N, S_SEG_ID, S_SEG_START, S_SEG_END, S_SEG_LEN, S_SEG_QUEUE, S_SEG_INTERNAL,
-  S_SEG_BSHAPE, S_SEG_ESHAPE, S_SEG_INDEX, S_SEG_N, S_SEG_WAY_N, S_SEG_WAY, S_WAY_N,
-  S_REP_ID, S_REP_NEXT, S_REP_T0, S_REP_T1, S_REP_LEN, S_REP_QUEUE, S_REP_SEG, S_REP_N,
-  S_SHAPE_USED, S_STATS, S_STATS_LEN, S_HIST, S_COUNTERS, S_SCAN_TMP, S_LIST, S_MISC,
-  S_HEUR, S_CPREP, S_ROW_CNT, S_ROW_OFF, S_ROWS, S_ROWS_IN, S_ROWS_OUT, S_ROWS_KEPT, S_IDX_A, S_IDX_B, S_KEY_A, S_KEY_B, S_POS_SCAN, S_RUN_KEEP, S_KEEP, S_FILE_HEAD, S_FILE_START, S_NFILES, S_SORT_TMP,
-  S_C_ROUTE_OFF, S_C_SEG_OFF, S_C_WAY_OFF, S_C_REP_OFF, S_C_ARGS, S_C_ROUTE, S_C_SEG_ID, S_C_SEG_START,
-  S_C_SEG_END, S_C_SEG_LEN, S_C_SEG_QUEUE, S_C_SEG_INTERNAL, S_C_SEG_BSHAPE, S_C_SEG_ESHAPE, S_C_SEG_WAY_N,
-  S_C_SEG_WAY, S_C_SEG_WAY_OFF, S_C_REP_ID, S_C_REP_NEXT, S_C_REP_T0, S_C_REP_T1, S_C_REP_LEN, S_C_REP_QUEUE,
-  S_TASK_REC, S_BT, S_CPREP_T, S_TRANS_TC, S_TURN, S_LIST2, S_GFLAG, S_HE_IN, S_HE_SORTED, S_HE_RED, S_HE_OUT, S_HE_RANGE, S_IN_TEXT, S_IN_CNT, S_IN_CSCAN, S_IN_NL, S_IN_HASH, S_IN_UOFF, S_IN_ULEN, S_IN_TIME, S_IN_LAT, S_IN_LON,
-  S_IN_ACC, S_IN_KEEP, S_IN_KPOS, S_IN_KIDX, S_IN_KEY_A, S_IN_KEY_B, S_IN_VAL_A, S_IN_VAL_B, S_IN_HEAD, S_IN_GID,
-  S_IN_GFIRST, S_IN_GKEY, S_IN_WS, S_IN_KLEN, S_IN_KFLAG, S_IN_POFF, S_IN_TPOS, S_IN_BAD, S_IN_TMP,
-  S_IN_T_OFF, S_IN_T_LAT, S_IN_T_LON, S_IN_T_TIME, S_IN_T_ACC, S_IN_T_MODE, S_IN_T_UOFF, S_IN_T_ULEN,
-  S_CLEN, S_CAND_NROOT, S_FLAGGED, S_HE_FIDX, S_HE_FHEAD, S_HE_PFILE, S_HE_FFIRST, S_HE_PKEY, S_QUEUE, S_PQUEUE,
-  S_E1DUMP0, S_E1DUMP1, S_TASK_DUMP, S_NDUMP0, S_NDUMP1, S_SORT_LIST, S_SORT_HIST,
-  S_PT_KIND, S_PT_EDGE, S_PT_FRAC, S_PT_LAT, S_PT_LON, S_PT_DIST, S_PT_STATE, S_PT_POS, S_PT_STATUS,
-  S_TR_CNT, S_TR_OFF, S_TR_EDGE, S_TR_WAY, S_TR_SEG, S_TR_FIRST, S_TR_F0, S_TR_F1, S_TR_S0, S_TR_S1, S_TR_T0, S_TR_T1,
-  S_TR_KEEP, S_TR_KEEP_OFF, S_TR_ENTRIES, S_TR_TMP,
-  S_FM_KEYS, S_FM_OFF, S_FM_TSIN, S_FM_WRONG, S_FM_STATUS, S_FM_P_LAT, S_FM_P_LON, S_FM_P_ACC, S_FM_FLAG,
-  S_FM_KEY, S_FM_LAT, S_FM_LON, S_FM_ACC, S_FM_TIME, S_FM_TS, S_FM_MSG, S_FM_UOFF, S_FM_ULEN,
-  S_NUM
-};
-
-// A device buffer that cannot be allocated ends the call: need() throws, the entry
-// points (run, tiles_cull, hist_reduce, ingest) catch it after draining the stream and
-// return OTR_DEVICE_ERROR naming the buffer — no kernel ever runs on a missing buffer.
-struct DeviceOom {
-  int slot;
-  size_t bytes;
-};
-
-static bool optional_slot(int s) {
-  return s == S_E1DUMP0 || s == S_E1DUMP1 || s == S_TASK_DUMP || s == S_NDUMP0 || s == S_NDUMP1 ||
-         s == S_SORT_LIST || s == S_SORT_HIST;
-}
-
-template <class T>
-T* Matcher::need(int slot, size_t n) {
-  if ((int)bufs.size() < S_NUM) bufs.resize(S_NUM);
-  DevBuf& b = bufs[slot];
-  size_t bytes = (n ? n : 1) * sizeof(T);
-  if (b.bytes < bytes) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-    size_t nb = bytes + bytes / 4;
-    bool ok = hipMalloc(&b.p, nb) == hipSuccess || hipMalloc(&b.p, bytes) == hipSuccess;
-    if (!ok && !optional_slot(slot) && release_optional()) {
-      (void)hipGetLastError();  // the optional workspace is gone: once more
-      nb = bytes;
-      ok = hipMalloc(&b.p, bytes) == hipSuccess;
-    }
-    if (!ok) {
-      (void)hipGetLastError();  // clear the sticky allocation error
-      b.p = nullptr;
-      throw DeviceOom{slot, bytes};
-    }
-    b.bytes = b.p ? nb : 0;
-  }
-  return (T*)b.p;
-}
-
-// the free device memory an optional buffer must leave (OTR_OPT_RESERVE_GB, default 8 GB or
-// an eighth of the device, whichever is more): the later stages' mandatory buffers
-static size_t opt_reserve() {
-  static const double gb = getenv("OTR_OPT_RESERVE_GB") ? atof(getenv("OTR_OPT_RESERVE_GB")) : -1.0;
-  if (gb >= 0) return (size_t)std::min(gb * (double)(1ll << 30), 1e18);
-  size_t fr = 0, tot = 0;
-  (void)hipMemGetInfo(&fr, &tot);
-  return std::max<size_t>(8ull << 30, tot / 8);
-}
-
-template <class T>
-T* Matcher::want(int slot, size_t n) {
-  if ((int)bufs.size() < S_NUM) bufs.resize(S_NUM);
-  DevBuf& b = bufs[slot];
-  const size_t bytes = (n ? n : 1) * sizeof(T);
-  if (b.bytes >= bytes) return (T*)b.p;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-  size_t fr = 0, tot = 0;
-  if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < bytes || fr - bytes < opt_reserve()) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
-  if (hipMalloc(&b.p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    b.p = nullptr;
-    return nullptr;
-  }
-  b.bytes = bytes;
-  return (T*)b.p;
-}
+// (the slots, need() and want(): otr_slots.h)
 
 bool Matcher::release_optional() {
   if (opt_busy) return false;
   bool any = false;
-  for (int s = 0; s < (int)bufs.size(); ++s)
-    if (optional_slot(s) && bufs[s].p) {
+  for (int s = 0; s < (int)pool.b.size(); ++s)
+    if (optional_slot(s) && pool.held(s, 0)) {
       if (!any && stream) (void)hipStreamSynchronize(stream);  // (no queued kernel still reads it)
       any = true;
-      (void)hipFree(bufs[s].p);
-      bufs[s].p = nullptr;
-      bufs[s].bytes = 0;
+      pool.drop(s);
     }
   return any;
-}
-
-static int oom_error(hipStream_t stream, const DeviceOom& o, std::string* err) {
-  if (stream) (void)hipStreamSynchronize(stream);  // nothing of this call still running
-  (void)hipGetLastError();
-  size_t fr = 0, tot = 0;
-  (void)hipMemGetInfo(&fr, &tot);
-  if (err)
-    *err = "out of device memory: buffer " + std::to_string(o.slot) + " needs " + std::to_string(o.bytes >> 20) +
-           " MiB (" + std::to_string(fr >> 20) + " of " + std::to_string(tot >> 20) +
-           " MiB free): split the batch";
-  return OTR_DEVICE_ERROR;
 }
 
 Matcher::~Matcher() {
   if (ses) sessions_destroy(ses);
   if (tst) tile_store_destroy(tst);
   if (ttx) tile_text_destroy(ttx);
-  for (auto& b : bufs)
-    if (b.p) (void)hipFree(b.p);
+  pool.release();
   for (auto& sl : gslab)
     for (void* q : {(void*)sl.key, (void*)sl.lab, (void*)sl.qmark, (void*)sl.fr, (void*)sl.touched})
       if (q) (void)hipFree(q);
@@ -738,8 +613,6 @@ __global__ __launch_bounds__(kCShards) void k_ctr_fold(const unsigned long long*
   }
 }
 
-static inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
-
 // the small-search tier's default size limit (keys of k_ntask's estimate; OTR_SMALL_KEYS)
 constexpr double kSmallKeys = 24.0;
 // the tiny-search tier's (eight searches per wave, at most 8 targets; OTR_TINY_KEYS)
@@ -753,21 +626,6 @@ static const std::vector<int>& route_tiers() {
   return t;
 }
 
-int Matcher::run(const otr_trace_batch* in, const ModeParams& mp, otr_batch_result* out, std::string* err) {
-  pts_have = false;  // (points() sets it once this batch's points exist)
-  pts = otr_point_result{};
-  trv_have = false;
-  trv = otr_traversal_result{};
-  try {
-    const int rc = run_impl(in, mp, out, err);
-    opt_busy = false;
-    return rc;
-  } catch (const DeviceOom& o) {
-    opt_busy = false;
-    return oom_error(stream, o, err);
-  }
-}
-
 // a persistent grid (work queues or a grid stride over a device-side list) of at most
 // `full` blocks, but never more than the list can hold (`units`, known on the host: tasks
 // or steps): a small batch does not launch thousands of workgroups that find nothing
@@ -779,7 +637,7 @@ static unsigned pgrid(unsigned full, int64_t units) {
 constexpr unsigned kCollectGrid = 512;  // blocks of a collect over the flagged tasks (a grid stride)
 
 // One batch on its way through the pipeline: what the stages share, and the stages in the
-// order run_impl calls them.  A stage returns OTR_OK or the code the batch ends with.
+// order Matcher::run calls them.  A stage returns OTR_OK or the code the batch ends with.
 struct Batch {
   Matcher& mat;
   const otr_trace_batch* in;
@@ -889,48 +747,56 @@ struct Batch {
   int retry_tier(int code, const RouteArgs& rb, unsigned long long* ctr_bank);
 };
 
-int Matcher::run_impl(const otr_trace_batch* in, const ModeParams& mp, otr_batch_result* out, std::string* err) {
-  GraphState& gs = graph_state();
-  std::shared_lock<std::shared_mutex> graph_lock(gs.mu);  // a reconfigure waits for this batch
-  if (!gs.ready) {
-    if (err) *err = "otr_configure has not been called";
-    return OTR_NOT_CONFIGURED;
-  }
-  HIPCHK(hipSetDevice(gs.device));
-  if (!stream) HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  if (!ev_init) {
-    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-    ev_init = true;
-  }
-  memset(out, 0, sizeof(*out));
-  out->n_traces = in->n_traces;
-  if (in->n_traces <= 0) {
-    pts_have = (in->flags & OTR_BATCH_MATCHED_POINTS) != 0;  // (no probe, no point)
-    if (in->flags & OTR_BATCH_EDGE_TRAVERSALS) {  // (no trace, no traversal: a trace_off of one zero)
-      trv.d_trace_off = need<int64_t>(S_TR_OFF, 1);
-      HIPCHK(hipMemsetAsync(trv.d_trace_off, 0, 8, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      if (in->flags & OTR_BATCH_COPY_OUT) {
-        h_tr_off.assign(1, 0);
-        trv.trace_off = h_tr_off.data();
-      }
-      trv_have = true;
+int Matcher::run(const otr_trace_batch* in, const ModeParams& mp, otr_batch_result* out, std::string* err) {
+  pts_have = false;  // (points() sets it once this batch's points exist)
+  pts = otr_point_result{};
+  trv_have = false;
+  trv = otr_traversal_result{};
+  const int rc = guarded(stream, err, [&]() -> int {
+    GraphState& gs = graph_state();
+    std::shared_lock<std::shared_mutex> graph_lock(gs.mu);  // a reconfigure waits for this batch
+    if (!gs.ready) {
+      if (err) *err = "otr_configure has not been called";
+      return OTR_NOT_CONFIGURED;
     }
-    return OTR_OK;
-  }
-  Batch c{*this, in, mp, out, err, gs.dg, stream, (in->flags & OTR_BATCH_TIMING) != 0};
-  c.T = in->n_traces;
-  c.want_points = (in->flags & OTR_BATCH_MATCHED_POINTS) != 0;
-  c.want_traversals = (in->flags & OTR_BATCH_EDGE_TRAVERSALS) != 0;
-  int rc;
-  if ((rc = c.upload()) || (rc = c.states()) || (rc = c.candidates()) || (rc = c.link()) || (rc = c.route_first()) ||
-      (rc = c.route_retry()) || (rc = c.route_edge()) || (rc = c.route_global()) || (rc = c.viterbi()) ||
-      (rc = c.paths()) || (rc = c.segments()) || (rc = c.points()) || (rc = c.traversals()) || (rc = c.drain()) ||
-      (rc = c.debug_fail()) || (rc = c.name_failed()))
-    return rc;
-  c.fold_counters();
-  if ((rc = c.copy_out()) || (rc = c.points_out())) return rc;
-  return c.traversals_out();
+    HIPCHK(hipSetDevice(gs.device));
+    if (!stream) HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    if (!ev_init) {
+      for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+      ev_init = true;
+    }
+    memset(out, 0, sizeof(*out));
+    out->n_traces = in->n_traces;
+    if (in->n_traces <= 0) {
+      pts_have = (in->flags & OTR_BATCH_MATCHED_POINTS) != 0;  // (no probe, no point)
+      if (in->flags & OTR_BATCH_EDGE_TRAVERSALS) {  // (no trace, no traversal: a trace_off of one zero)
+        trv.d_trace_off = need<int64_t>(S_TR_OFF, 1);
+        HIPCHK(hipMemsetAsync(trv.d_trace_off, 0, 8, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (in->flags & OTR_BATCH_COPY_OUT) {
+          h_tr_off.assign(1, 0);
+          trv.trace_off = h_tr_off.data();
+        }
+        trv_have = true;
+      }
+      return OTR_OK;
+    }
+    Batch c{*this, in, mp, out, err, gs.dg, stream, (in->flags & OTR_BATCH_TIMING) != 0};
+    c.T = in->n_traces;
+    c.want_points = (in->flags & OTR_BATCH_MATCHED_POINTS) != 0;
+    c.want_traversals = (in->flags & OTR_BATCH_EDGE_TRAVERSALS) != 0;
+    int rc;
+    if ((rc = c.upload()) || (rc = c.states()) || (rc = c.candidates()) || (rc = c.link()) || (rc = c.route_first()) ||
+        (rc = c.route_retry()) || (rc = c.route_edge()) || (rc = c.route_global()) || (rc = c.viterbi()) ||
+        (rc = c.paths()) || (rc = c.segments()) || (rc = c.points()) || (rc = c.traversals()) || (rc = c.drain()) ||
+        (rc = c.debug_fail()) || (rc = c.name_failed()))
+      return rc;
+    c.fold_counters();
+    if ((rc = c.copy_out()) || (rc = c.points_out())) return rc;
+    return c.traversals_out();
+  });
+  opt_busy = false;  // (on both paths: an allocation failure inside ends at the guard)
+  return rc;
 }
 
 // input upload (host batches), the batch-size check, the work counters
@@ -957,8 +823,7 @@ int Batch::upload() {
     b.mode = d_mode;
     b.acc = d_acc;
   } else {
-    HIPCHK(hipMemcpyAsync(&N, in->trace_offsets + T, 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
+    if (int rc = read_back(stream, err, fetch(&N, in->trace_offsets + T))) return rc;
     b.trace_off = in->trace_offsets;
     b.lat = in->lat;
     b.lon = in->lon;
@@ -987,19 +852,14 @@ int Batch::upload() {
 int Batch::scan(const int64_t* src, int64_t* dst_np1, int64_t n) {
   HIPCHK(hipMemsetAsync(dst_np1, 0, 8, stream));
   if (n == 0) return OTR_OK;
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, src, dst_np1 + 1, (int)n, stream));
-  void* tmp = need<char>(S_SCAN_TMP, tb > scan_bytes ? tb : scan_bytes);
-  scan_bytes = scan_bytes > tb ? scan_bytes : tb;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, src, dst_np1 + 1, (int)n, stream));
-  return OTR_OK;
+  Workspace tmp;
+  if (int rc = otr::scan_bytes(src, dst_np1 + 1, (int)n, &tmp.bytes, stream, err)) return rc;
+  scan_bytes = std::max(scan_bytes, tmp.bytes);  // (the slot keeps the batch's largest)
+  tmp.p = need<char>(S_SCAN_TMP, scan_bytes);
+  return inclusive_sum(tmp, src, dst_np1 + 1, (int)n, stream, err);
 }
 
-int Batch::read_i64(const int64_t* p, int64_t* v) {
-  HIPCHK(hipMemcpyAsync(v, p, 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  return OTR_OK;
-}
+int Batch::read_i64(const int64_t* p, int64_t* v) { return read_back(stream, err, fetch(v, p)); }
 
 // ---- K0: states
 int Batch::states() {
@@ -1007,15 +867,15 @@ int Batch::states() {
   int64_t* state_cnt = need<int64_t>(S_STATE_CNT, T);
   trace_state_off = need<int64_t>(S_TRACE_STATE_OFF, T + 1);
   tb(OTR_STAGE_STATES);
-  k_select_states<<<grid_for(T, 256), 256, 0, stream>>>(b, mp, state_cnt, nullptr, nullptr, nullptr);
+  k_select_states<<<grid_ceil(T, 256), 256, 0, stream>>>(b, mp, state_cnt, nullptr, nullptr, nullptr);
   te(OTR_STAGE_STATES);
   if ((rc = scan(state_cnt, trace_state_off, T))) return rc;
   if ((rc = read_i64(trace_state_off + T, &S))) return rc;
   out->n_states = S;
   state_probe = need<int64_t>(S_STATE_PROBE, S);
   state_trace = need<int32_t>(S_STATE_TRACE, S);
-  k_select_states<<<grid_for(T, 256), 256, 0, stream>>>(b, mp, state_cnt, trace_state_off, state_probe,
-                                                        state_trace);
+  k_select_states<<<grid_ceil(T, 256), 256, 0, stream>>>(b, mp, state_cnt, trace_state_off, state_probe,
+                                                         state_trace);
   return OTR_OK;
 }
 
@@ -1141,7 +1001,7 @@ int Batch::link() {
     sm.est_k = est_k;
     for (int m = 0; m < OTR_MODES; ++m) sm.est_v[m] = est_v[m];
     sm.small_keys = (float)small_keys;
-    k_ntask<<<grid_for(S, 256), 256, 0, stream>>>(S, sb.prev, pr.nroot, sb.ntask, sm);
+    k_ntask<<<grid_ceil(S, 256), 256, 0, stream>>>(S, sb.prev, pr.nroot, sb.ntask, sm);
   }
   if ((rc = scan(sb.ntask, task_off, S))) return rc;
   if (small_tier && (rc = scan(ntask4, task4_off, S))) return rc;
@@ -1150,8 +1010,7 @@ int Batch::link() {
   HIPCHK(hipMemcpyAsync(&NT, task_off + S, 8, hipMemcpyDeviceToHost, stream));
   if (small_tier) HIPCHK(hipMemcpyAsync(&NT4, task4_off + S, 8, hipMemcpyDeviceToHost, stream));
   if (tiny_tier) HIPCHK(hipMemcpyAsync(&NT8, task8_off + S, 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(&NTR, trans_off + S, 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
+  if ((rc = read_back(stream, err, fetch(&NTR, trans_off + S)))) return rc;
   NT += NT4 + NT8;
   task_ovf = need<int32_t>(S_TASK_OVF, NT);
   trans = need<uint32_t>(S_TRANS, NTR);
@@ -1225,7 +1084,7 @@ int Batch::slabs(int tier, GSlabs* out) {
       (void)hipGetLastError();
       for (void* q : p)
         if (q) (void)hipFree(q);
-      throw DeviceOom{S_NUM + tier, 28 * c};  // (the global-search slabs of this tier)
+      throw DeviceOom{PoolOwner::matcher, nullptr, S_NUM + tier, 28 * c};  // (the global-search slabs of this tier)
     }
     sl.key = (uint32_t*)p[0];
     sl.lab = (unsigned long long*)p[1];
@@ -1430,7 +1289,7 @@ int Batch::route_retry() {
   const std::vector<int>& tiers = route_tiers();
   const int ntier = (int)tiers.size();
   // the first tier's flagged tasks, once; every later collect scans only them
-  k_collect_flagged<<<grid_for(NT, 1024), 1024, 0, stream>>>(NT, task_ovf, flagged, cnt + C_FLAGGED);
+  k_collect_flagged<<<grid_ceil(NT, 1024), 1024, 0, stream>>>(NT, task_ovf, flagged, cnt + C_FLAGGED);
   // node dump slots: tier t writes buffer t % 2 and tier t + 1 resumes from it; slots for a
   // quarter of the tasks, at most OTR_NDUMP_GB (4) GB per buffer (C4: 4 % of the 1024-slot
   // searches outgrow it, 10 KB each); beyond them, or without the memory, searches restart
@@ -1543,9 +1402,9 @@ int Batch::route_edge() {
         while (bits < 32 && (g.n_edges >> bits) > 0u) ++bits;
         const int shift = bits > 12 ? bits - 12 : 0;
         HIPCHK(hipMemsetAsync(hist, 0, 4 * kSortBuckets, stream));
-        k_sort_hist<<<grid_for(NT, 1024), 1024, 0, stream>>>(list, c, task_rec, shift, hist);
+        k_sort_hist<<<grid_ceil(NT, 1024), 1024, 0, stream>>>(list, c, task_rec, shift, hist);
         k_sort_scan<<<1, 1024, 0, stream>>>(hist);
-        k_sort_place<<<grid_for(NT, 1024), 1024, 0, stream>>>(list, c, task_rec, shift, hist, list2);
+        k_sort_place<<<grid_ceil(NT, 1024), 1024, 0, stream>>>(list, c, task_rec, shift, hist, list2);
         rb.task_list = list2;
       }
       rb.list_count = c;
@@ -1652,7 +1511,7 @@ int Batch::paths() {
   int rc;
   path_off = need<int64_t>(S_PATH_OFF, S);
   path_len = need<int32_t>(S_PATH_LEN, S);
-  if (S > 0) k_fill_i32<<<grid_for(S, 256), 256, 0, stream>>>(path_len, S, 0);
+  if (S > 0) k_fill_i32<<<grid_ceil(S, 256), 256, 0, stream>>>(path_len, S, 0);
   {
     steps = need<int64_t>(S_LIST2, std::max<int64_t>(S, 1));
     nsteps_d = cnt + C_STEPS;
@@ -1682,13 +1541,11 @@ int Batch::paths() {
       pc.est4 = 8.f * est_k;  // (est_k = half the node density)
       pc.small_keys = (float)small_path_keys;
       HIPCHK(hipMemsetAsync(nsteps4_d, 0, 16, stream));
-      k_step_lists<<<grid_for(S, 256), 256, 0, stream>>>(S, sb.prev, va.brk, cb.count, pc, steps, nsteps4_d, nsteps_d,
+      k_step_lists<<<grid_ceil(S, 256), 256, 0, stream>>>(S, sb.prev, va.brk, cb.count, pc, steps, nsteps4_d, nsteps_d,
                                                           nall_d);
-      HIPCHK(hipMemcpyAsync(&h_nsteps[0], nsteps4_d, 8, hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipMemcpyAsync(&h_nsteps[1], nsteps_d, 8, hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
+      if ((rc = read_back(stream, err, fetch(&h_nsteps[0], nsteps4_d), fetch(&h_nsteps[1], nsteps_d)))) return rc;
     } else if (S > 0) {
-      k_step_list<<<grid_for(S, 1024), 1024, 0, stream>>>(S, sb.prev, va.brk, cb.count, steps, nsteps_d);
+      k_step_list<<<grid_ceil(S, 1024), 1024, 0, stream>>>(S, sb.prev, va.brk, cb.count, steps, nsteps_d);
     }
     // the retry collects' index range: every step index (front and back lists), or the list
     nscan_d = small_paths ? nall_d : nsteps_d;
@@ -1785,7 +1642,7 @@ int Batch::paths_attempt(int64_t capacity) {
   // launch's waves claim steps from its own per-XCD queue (XcdQueue)
   for (int tier = 0; tier < 3; ++tier) {
     unsigned long long* c = cnt + C_PATH_TIER + tier;
-    k_collect_tier_list<<<grid_for(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, 0x2u, list, c);
+    k_collect_tier_list<<<grid_ceil(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, 0x2u, list, c);
     PathArgs pb = pa;
     pb.queue = pq + tier * kPQWords;
     if (tier == 0) k_paths<512, 1><<<pgrid(16384, S), 64, 0, stream>>>(g, pb, list, c);
@@ -1796,7 +1653,7 @@ int Batch::paths_attempt(int64_t capacity) {
   if (turn_modes != 0u) {
     for (int et = 0; et < 2; ++et) {
       unsigned long long* c = cnt + C_EDGE_PATH + et;
-      k_collect_tier_list<<<grid_for(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, et == 0 ? 0x20u : 0x40u,
+      k_collect_tier_list<<<grid_ceil(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, et == 0 ? 0x20u : 0x40u,
                                                                    list, c);
       PathArgs pb = pa;
       pb.queue = pq + (3 + et) * kPQWords;
@@ -1815,7 +1672,7 @@ int Batch::paths_attempt(int64_t capacity) {
   ga.cap_flag = (int32_t*)(cnt + C_CAP_FLAG);
   for (int gt = 0; gt < 2; ++gt) {
     unsigned long long* c = cnt + C_PATH_GLOBAL + gt;
-    k_collect_tier_list<<<grid_for(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, gt == 0 ? 0xAu : 0x2u, list,
+    k_collect_tier_list<<<grid_ceil(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, gt == 0 ? 0xAu : 0x2u, list,
                                                                  c);
     GSlabs gs2;
     if ((rc = slabs(gt, &gs2))) return rc;
@@ -1827,7 +1684,7 @@ int Batch::paths_attempt(int64_t capacity) {
     k_general<<<pgrid(gs2.n, S), kGenThreads, 0, stream>>>(g, ga, gs2);
   }
   // steps still flagged (beyond a 1M-state slab): named after the final sync
-  k_collect_tier_list<<<grid_for(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, 0xAu, list, cnt + C_PATHS_LEFT);
+  k_collect_tier_list<<<grid_ceil(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, 0xAu, list, cnt + C_PATHS_LEFT);
   te(OTR_STAGE_PATHS_BIG);
   return OTR_OK;
 }
@@ -1837,7 +1694,7 @@ int Batch::segments() {
   int rc;
   int64_t* cap = need<int64_t>(S_CAP, T);
   cap_off = need<int64_t>(S_CAP_OFF, T + 1);
-  k_capacity<<<grid_for(T, 256), 256, 0, stream>>>(T, trace_state_off, cb.count, path_len, cap);
+  k_capacity<<<grid_ceil(T, 256), 256, 0, stream>>>(T, trace_state_off, cb.count, path_len, cap);
   if ((rc = scan(cap, cap_off, T))) return rc;
   if ((rc = read_i64(cap_off + T, &C))) return rc;
   sa.b = b;
@@ -2143,66 +2000,60 @@ int Matcher::edge_traversals(otr_traversal_result* out, std::string* err) const 
   return OTR_OK;
 }
 
-int Matcher::edge_observations(int quantisation, otr_hist_entry** d_entries, int64_t* n, std::string* err) {
-  try {
-    return edge_observations_impl(quantisation, d_entries, n, err);
-  } catch (const DeviceOom& o) {
-    return oom_error(stream, o, err);
-  }
-}
-
 // the speed entries of the last batch's complete traversals: keep flags, their scan, fill
-int Matcher::edge_observations_impl(int quantisation, otr_hist_entry** d_entries, int64_t* n, std::string* err) {
-  *d_entries = nullptr;
-  *n = 0;
-  if (!trv_have) {
-    if (err) *err = std::string("otr_edge_observations") + kNoTraversals;
-    return OTR_BAD_REQUEST;
-  }
-  const int64_t nt = trv.n_traversals;
-  if (nt <= 0) return OTR_OK;
-  if (nt >= (int64_t)INT32_MAX) {
-    if (err) *err = "too many traversals for one call";
-    return OTR_BAD_REQUEST;
-  }
-  GraphState& gs = graph_state();
-  std::shared_lock<std::shared_mutex> graph_lock(gs.mu);
-  HIPCHK(hipSetDevice(gs.device));
-  TravObsArgs oa{};
-  oa.n = nt;
-  oa.edge = trv.d_edge;
-  oa.first_state = trv.d_first_state;
-  oa.f0 = trv.d_f0;
-  oa.f1 = trv.d_f1;
-  oa.s0_mm = trv.d_s0_mm;
-  oa.s1_mm = trv.d_s1_mm;
-  oa.t_enter = trv.d_t_enter;
-  oa.t_exit = trv.d_t_exit;
-  oa.quantisation = quantisation > 0 ? quantisation : 3600;
-  oa.keep = need<int64_t>(S_TR_KEEP, (size_t)nt);
-  int64_t* keep_off = need<int64_t>(S_TR_KEEP_OFF, (size_t)nt + 1);
-  oa.keep_off = keep_off;
-  const unsigned grid = (unsigned)std::min<int64_t>(kTravObsGrid, (nt + 255) / 256);
-  k_trav_obs_keep<<<grid, 256, 0, stream>>>(oa);
-  HIPCHK(hipMemsetAsync(keep_off, 0, 8, stream));
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, oa.keep, keep_off + 1, (int)nt, stream));
-  void* tmp = need<char>(S_TR_TMP, tb);
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, oa.keep, keep_off + 1, (int)nt, stream));
-  int64_t ne = 0;
-  HIPCHK(hipMemcpyAsync(&ne, keep_off + nt, 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  if (ne < 0 || ne > nt) {
-    if (err) *err = "edge observations: the keep scan failed";
-    return OTR_DEVICE_ERROR;
-  }
-  oa.entries = need<otr_hist_entry>(S_TR_ENTRIES, (size_t)ne);
-  if (ne > 0) k_trav_obs_fill<<<grid, 256, 0, stream>>>(gs.dg, oa);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(stream));
-  *d_entries = oa.entries;
-  *n = ne;
-  return OTR_OK;
+int Matcher::edge_observations(int quantisation, otr_hist_entry** d_entries, int64_t* n, std::string* err) {
+  return guarded(stream, err, [&]() -> int {
+    *d_entries = nullptr;
+    *n = 0;
+    if (!trv_have) {
+      if (err) *err = std::string("otr_edge_observations") + kNoTraversals;
+      return OTR_BAD_REQUEST;
+    }
+    const int64_t nt = trv.n_traversals;
+    if (nt <= 0) return OTR_OK;
+    if (nt >= (int64_t)INT32_MAX) {
+      if (err) *err = "too many traversals for one call";
+      return OTR_BAD_REQUEST;
+    }
+    GraphState& gs = graph_state();
+    std::shared_lock<std::shared_mutex> graph_lock(gs.mu);
+    HIPCHK(hipSetDevice(gs.device));
+    TravObsArgs oa{};
+    oa.n = nt;
+    oa.edge = trv.d_edge;
+    oa.first_state = trv.d_first_state;
+    oa.f0 = trv.d_f0;
+    oa.f1 = trv.d_f1;
+    oa.s0_mm = trv.d_s0_mm;
+    oa.s1_mm = trv.d_s1_mm;
+    oa.t_enter = trv.d_t_enter;
+    oa.t_exit = trv.d_t_exit;
+    oa.quantisation = quantisation > 0 ? quantisation : 3600;
+    oa.keep = need<int64_t>(S_TR_KEEP, (size_t)nt);
+    int64_t* keep_off = need<int64_t>(S_TR_KEEP_OFF, (size_t)nt + 1);
+    oa.keep_off = keep_off;
+    int rc;
+    Workspace tmp;  // (sized before the first launch)
+    if ((rc = scan_bytes(oa.keep, keep_off + 1, (int)nt, &tmp.bytes, stream, err))) return rc;
+    tmp.p = need<char>(S_TR_TMP, tmp.bytes);
+    const unsigned grid = (unsigned)std::min<int64_t>(kTravObsGrid, (nt + 255) / 256);
+    k_trav_obs_keep<<<grid, 256, 0, stream>>>(oa);
+    HIPCHK(hipMemsetAsync(keep_off, 0, 8, stream));
+    if ((rc = inclusive_sum(tmp, oa.keep, keep_off + 1, (int)nt, stream, err))) return rc;
+    int64_t ne = 0;
+    if ((rc = read_back(stream, err, fetch(&ne, keep_off + nt)))) return rc;
+    if (ne < 0 || ne > nt) {
+      if (err) *err = "edge observations: the keep scan failed";
+      return OTR_DEVICE_ERROR;
+    }
+    oa.entries = need<otr_hist_entry>(S_TR_ENTRIES, (size_t)ne);
+    if (ne > 0) k_trav_obs_fill<<<grid, 256, 0, stream>>>(gs.dg, oa);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));
+    *d_entries = oa.entries;
+    *n = ne;
+    return OTR_OK;
+  });
 }
 
 // the work counters folded, the counts of what no tier could search and the per-trace
@@ -2531,7 +2382,7 @@ int report_lists_device(const ReportLists& h, std::string* err) {
     if (err) *err = "device allocation failed (report lists)";
     return OTR_DEVICE_ERROR;
   }
-  k_report_lists<<<grid_for(n, 128), 128>>>(d);
+  k_report_lists<<<grid_ceil(n, 128), 128>>>(d);
   hipError_t e = hipDeviceSynchronize();
   auto get = [&](void* dst, const void* src, size_t bytes) {
     if (e == hipSuccess && bytes) e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
@@ -2553,980 +2404,6 @@ int report_lists_device(const ReportLists& h, std::string* err) {
     return OTR_DEVICE_ERROR;
   }
   return OTR_OK;
-}
-
-// Tile stage: sort rows into simple_reporter's line order per file, then cull
-// (K10).  Result rows are copied to host (matcher-owned).
-int Matcher::tiles_cull(const otr_tile_row* rows, int64_t n, int memory, int privacy, int rules,
-                        const otr_tile_row** out, int64_t* n_out, std::string* err) {
-  try {
-    return tiles_cull_impl(rows, n, memory, privacy, rules, out, n_out, err);
-  } catch (const DeviceOom& o) {
-    return oom_error(stream, o, err);
-  }
-}
-
-int Matcher::tiles_cull_impl(const otr_tile_row* rows, int64_t n, int memory, int privacy, int rules,
-                        const otr_tile_row** out, int64_t* n_out, std::string* err) {
-  GraphState& gs = graph_state();
-  HIPCHK(hipSetDevice(gs.device));
-  if (!stream) HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  *n_out = 0;
-  *out = nullptr;
-  h_tile_rows.clear();
-  if (n <= 0) return OTR_OK;
-  if (n >= (int64_t)INT32_MAX) {
-    if (err) *err = "too many tile rows for one call";
-    return OTR_BAD_REQUEST;
-  }
-  // staging: a copy of the caller's rows
-  otr_tile_row* d_in = need<otr_tile_row>(S_ROWS_IN, n);
-  if (!d_in) {
-    if (err) *err = "device allocation failed (tiles)";
-    return OTR_DEVICE_ERROR;
-  }
-  HIPCHK(hipMemcpyAsync(d_in, rows, sizeof(otr_tile_row) * n,
-                        memory == OTR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
-  CulledRows c;
-  const int rc = cull_device_impl(d_in, n, privacy, rules, &c, err);
-  if (rc != OTR_OK) return rc;
-  const int64_t nk = c.n_kept;
-  h_tile_rows.resize(nk > 0 ? nk : 1);
-  if (nk > 0) HIPCHK(hipMemcpy(h_tile_rows.data(), c.kept, sizeof(otr_tile_row) * nk, hipMemcpyDeviceToHost));
-  HIPCHK(hipGetLastError());
-  *out = h_tile_rows.data();
-  *n_out = nk;
-  return OTR_OK;
-}
-
-int Matcher::cull_device(const otr_tile_row* d_in, int64_t n, int privacy, int rules, CulledRows* out,
-                         std::string* err) {
-  try {
-    return cull_device_impl(d_in, n, privacy, rules, out, err);
-  } catch (const DeviceOom& o) {
-    return oom_error(stream, o, err);
-  }
-}
-
-// The sort, run split, k_cull_runs and compaction over 0 < n < 2^31 rows in HBM (d_in: any
-// device memory but the cull slots below; it is only read).  Leaves the sorted rows, the
-// kept rows and the inclusive scan of the sorted rows' keep flags in the matcher's cull
-// slots, with the stream drained.
-int Matcher::cull_device_impl(const otr_tile_row* d_in, int64_t n, int privacy, int rules, CulledRows* out,
-                              std::string* err) {
-  // staging: sorted, kept; permutation + radix keys
-  otr_tile_row* d = need<otr_tile_row>(S_ROWS_OUT, n);
-  otr_tile_row* d_kept = need<otr_tile_row>(S_ROWS_KEPT, n);
-  int32_t* perm_a = need<int32_t>(S_IDX_A, n);
-  int32_t* perm_b = need<int32_t>(S_IDX_B, n);
-  unsigned long long* key_a = need<unsigned long long>(S_KEY_A, n);
-  unsigned long long* key_b = need<unsigned long long>(S_KEY_B, n);
-  int64_t* head = need<int64_t>(S_FILE_HEAD, n);
-  int64_t* keep = need<int64_t>(S_KEEP, n);
-  int64_t* pos = need<int64_t>(S_POS_SCAN, n);
-  int64_t* fstart = need<int64_t>(S_FILE_START, n);
-  if (!d || !d_kept || !perm_a || !perm_b || !key_a || !key_b || !head || !keep || !pos || !fstart) {
-    if (err) *err = "device allocation failed (tiles)";
-    return OTR_DEVICE_ERROR;
-  }
-  const int ni = (int)n;
-  size_t tb_sort = 0, tb_scan = 0;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, key_a, key_b, perm_a, perm_b, ni, 0, 64, stream));
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb_scan, head, pos, ni, stream));
-  void* tmp = need<char>(S_SORT_TMP, std::max(tb_sort, tb_scan));
-  if (!tmp) {
-    if (err) *err = "device allocation failed (tiles)";
-    return OTR_DEVICE_ERROR;
-  }
-  // LSD over the sort fields: stable radix passes, least significant field first (the
-  // identity start keeps arrival order within equal keys)
-  k_iota_i32<<<grid_for(n, 256), 256, 0, stream>>>(perm_a, n);
-  const bool pair_order = rules == OTR_TILE_RULES_STREAM;
-  for (int f = pair_order ? TF_NEXT : TF_COUNT - 1; f >= 0; --f) {
-    if (pair_order) k_pair_key<<<grid_for(n, 256), 256, 0, stream>>>(d_in, perm_a, n, f, key_a);
-    else k_line_key<<<grid_for(n, 256), 256, 0, stream>>>(d_in, perm_a, n, f, key_a);
-    size_t tb = tb_sort;
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key_a, key_b, perm_a, perm_b, ni, 0,
-                                              (f == TF_FILE || pair_order) ? 64 : 63, stream));
-    std::swap(perm_a, perm_b);
-  }
-  k_gather_rows<<<grid_for(n, 256), 256, 0, stream>>>(d_in, perm_a, n, d);
-  // runs of equal (file, id, next_id): heads → scan → run starts; per-run decision
-  k_run_heads<<<grid_for(n, 256), 256, 0, stream>>>(d, n, head);
-  size_t tb = tb_scan;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, head, pos, ni, stream));
-  k_scatter_index<<<grid_for(n, 256), 256, 0, stream>>>(head, pos, n, fstart);
-  int64_t nr = 0;
-  HIPCHK(hipMemcpyAsync(&nr, pos + (n - 1), 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  if (nr < 1 || nr > n) {
-    if (err) *err = "tile run split failed";
-    return OTR_DEVICE_ERROR;
-  }
-  uint8_t* run_keep = need<uint8_t>(S_RUN_KEEP, nr);
-  if (!run_keep) {
-    if (err) *err = "device allocation failed (tiles)";
-    return OTR_DEVICE_ERROR;
-  }
-  k_cull_runs<<<grid_for(nr, 256), 256, 0, stream>>>(d, n, fstart, nr, privacy, run_keep);
-  k_row_keep<<<grid_for(n, 256), 256, 0, stream>>>(pos, run_keep, n, keep);
-  tb = tb_scan;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, keep, head, ni, stream));  // head: reused as positions
-  std::swap(pos, head);
-  k_scatter_flagged<otr_tile_row><<<grid_for(n, 256), 256, 0, stream>>>(d, keep, pos, n, d_kept);
-  int64_t nk = 0;
-  HIPCHK(hipMemcpyAsync(&nk, pos + (n - 1), 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  if (nk < 0 || nk > n) {
-    if (err) *err = "tile cull compaction failed";
-    return OTR_DEVICE_ERROR;
-  }
-  out->sorted = d;
-  out->kept = d_kept;
-  out->kept_incl = pos;
-  out->n_kept = nk;
-  return OTR_OK;
-}
-
-// ---- keyed speed histogram (include/otr.h otr_hist_reduce) -----------------
-__global__ void k_rows_to_entries(const otr_tile_row* r, int64_t n, otr_hist_entry* e) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  otr_hist_entry x;
-  x.file = r[i].file;
-  x.id = r[i].id;
-  x.next_id = r[i].next_id;
-  x.speed_bin = (uint32_t)r[i].speed_bin;
-  x.count = 1u;
-  e[i] = x;
-}
-// key ranges of the entries, for the fewest radix-sort bits: OR of the ids and next ids
-// (their widths), min / max hour bucket, and whether every file is the one K9 derives
-// from its id (bucket << 25 | level << 22 | tile: then (file, id) order is (bucket,
-// level, tile, index) order, one packed key)
-struct EntryRange {
-  unsigned long long id_or, next_or, file_or, bmin, bmax, foreign;
-};
-// a fixed grid (kRangeBlocks x 1024) strides over the entries; one set of atomics per
-// block (one per wave queued ~23K atomics on a single line: 263 us for 244K entries)
-constexpr int kRangeBlocks = 128;
-__global__ __launch_bounds__(1024) void k_entry_range(const otr_hist_entry* e, int64_t n, EntryRange* r) {
-  unsigned long long v[6] = {0ull, 0ull, 0ull, ~0ull, 0ull, 0ull};  // id, next, file OR; bmin; bmax; foreign
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const otr_hist_entry x = e[i];
-    v[0] |= x.id;
-    v[1] |= x.next_id;
-    v[2] |= x.file;
-    const unsigned long long b = x.file >> 25;
-    v[3] = b < v[3] ? b : v[3];
-    v[4] = b > v[4] ? b : v[4];
-    v[5] |= (x.file & 0x1FFFFFFull) != (((x.id & 7ull) << 22) | ((x.id >> 3) & 0x3FFFFFull)) ? 1ull : 0ull;
-  }
-  for (int o = OTR_WAVE / 2; o > 0; o >>= 1) {
-    for (int q : {0, 1, 2, 5}) v[q] |= __shfl_xor(v[q], o);
-    const unsigned long long a = __shfl_xor(v[3], o), b = __shfl_xor(v[4], o);
-    v[3] = a < v[3] ? a : v[3];
-    v[4] = b > v[4] ? b : v[4];
-  }
-  __shared__ unsigned long long part[1024 / OTR_WAVE][6];
-  if (lane_id() == 0)
-    for (int q = 0; q < 6; ++q) part[threadIdx.x / OTR_WAVE][q] = v[q];
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < (int)(blockDim.x / OTR_WAVE); ++w) {
-      for (int q : {0, 1, 2, 5}) v[q] |= part[w][q];
-      v[3] = part[w][3] < v[3] ? part[w][3] : v[3];
-      v[4] = part[w][4] > v[4] ? part[w][4] : v[4];
-    }
-    atomicOr(&r->id_or, v[0]);
-    atomicOr(&r->next_or, v[1]);
-    atomicOr(&r->file_or, v[2]);
-    atomicMin(&r->bmin, v[3]);
-    atomicMax(&r->bmax, v[4]);
-    atomicOr(&r->foreign, v[5]);
-  }
-}
-static int bit_width(unsigned long long v) { return v ? 64 - __builtin_clzll(v) : 0; }
-// sort key of one LSD pass: 0 file, 1 id, 2 next id, 3 speed bin, 4 next id << 3 | bin,
-// 5 (bucket - bmin) << 46 | level << 43 | tile << 21 | index (K9 files, 46-bit ids)
-__global__ void k_entry_key(const otr_hist_entry* e, const int32_t* perm, int64_t n, int field,
-                            unsigned long long bmin, unsigned long long* key) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const otr_hist_entry& x = e[perm[i]];
-  unsigned long long k;
-  switch (field) {
-    case 0: k = x.file; break;
-    case 1: k = x.id; break;
-    case 2: k = x.next_id; break;
-    case 3: k = x.speed_bin; break;
-    case 4: k = (x.next_id << 3) | (x.speed_bin & 7u); break;
-    default:
-      k = (((x.file >> 25) - bmin) << 46) | ((x.id & 7ull) << 43) | (((x.id >> 3) & 0x3FFFFFull) << 21) |
-          ((x.id >> 25) & 0x1FFFFFull);
-  }
-  key[i] = k;
-}
-__global__ void k_gather_entries(const otr_hist_entry* in, const int32_t* idx, int64_t n, otr_hist_entry* out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = in[idx[i]];
-}
-// run heads over sorted entries: pair = 0 the full key, 1 the (file, id, next_id) pair
-__global__ void k_entry_heads(const otr_hist_entry* e, int64_t n, int pair, int64_t* head) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  bool h = i == 0;
-  if (!h) {
-    const otr_hist_entry &a = e[i - 1], &b = e[i];
-    h = a.file != b.file || a.id != b.id || a.next_id != b.next_id || (!pair && a.speed_bin != b.speed_bin);
-  }
-  head[i] = h ? 1 : 0;
-}
-__global__ void k_entry_counts(const otr_hist_entry* e, int64_t n, int64_t* c) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) c[i] = e[i].count;
-}
-// the last entry of every run carries its run's count sum: csum = inclusive scan of counts,
-// run r spans [start_r, next start); out[r] = entry at start_r with count = the sum
-__global__ void k_entry_reduce(const otr_hist_entry* e, int64_t n, const int64_t* run_start, int64_t n_runs,
-                               const int64_t* csum, otr_hist_entry* out) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n_runs) return;
-  const int64_t s = run_start[r], t = r + 1 < n_runs ? run_start[r + 1] : n;
-  otr_hist_entry x = e[s];
-  const int64_t tot = csum[t - 1] - (s > 0 ? csum[s - 1] : 0);
-  x.count = (uint32_t)(tot < 0xFFFFFFFFll ? tot : 0xFFFFFFFFll);
-  out[r] = x;
-}
-// The owner's privacy cull of simple_reporter.py:218-239 on keyed entries.  A pair's run
-// length in its file is its total count over the speed bins (one line per tile row); the
-// reference sorts a file's lines as strings, so its runs are in the string order of
-// (id, next_id) (dec_key), and the loop judges every run alone (kept iff >= privacy)
-// except that a trailing run of ONE line is judged together with the run before it (both
-// kept iff that run's length + 1 >= privacy).  Per file (files are
-// contiguous in the numeric entry order), one block finds the string-last and the
-// string-second pair (a top-2 reduction), then every entry gets its keep flag.
-struct PairFile {
-  unsigned long long s1, n1, s2, n2;  // dec_key of (id, next id): the string-last pair, the one before it
-  int64_t t1, t2;                     // their totals
-};
-__device__ inline bool pf_after(unsigned long long as, unsigned long long an, unsigned long long bs,
-                                unsigned long long bn) {
-  return as > bs || (as == bs && an > bn);
-}
-__device__ inline void pf_add(PairFile& T, unsigned long long s, unsigned long long n, int64_t t) {
-  if (pf_after(s, n, T.s1, T.n1)) {
-    T.s2 = T.s1;
-    T.n2 = T.n1;
-    T.t2 = T.t1;
-    T.s1 = s;
-    T.n1 = n;
-    T.t1 = t;
-  } else if (pf_after(s, n, T.s2, T.n2)) {
-    T.s2 = s;
-    T.n2 = n;
-    T.t2 = t;
-  }
-}
-__global__ void k_pair_file_heads(const otr_hist_entry* e, const int64_t* pair_start, int64_t n_pairs, int64_t* head) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p < n_pairs) head[p] = p == 0 || e[pair_start[p]].file != e[pair_start[p - 1]].file ? 1 : 0;
-}
-// every pair's string-order keys (dec_key of id and next id) and total, one thread per
-// pair: the per-file reduction below then only compares
-struct PairKey {
-  unsigned long long s, n;
-  int64_t t;
-};
-__global__ void k_pair_keys(const otr_hist_entry* e, const int64_t* pair_start, int64_t n_pairs, int64_t n,
-                            const int64_t* csum, PairKey* K) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n_pairs) return;
-  const int64_t s = pair_start[p], t = p + 1 < n_pairs ? pair_start[p + 1] : n;
-  const otr_hist_entry& x = e[s];
-  K[p] = PairKey{dec_key(x.id), dec_key(x.next_id), csum[t - 1] - (s > 0 ? csum[s - 1] : 0)};
-}
-// one 1024-thread block per file over its pairs [ffirst[f], ffirst[f + 1]): the top two pairs
-// by (dec_key(id), dec_key(next_id)) and their totals (dec_key > 0: 0 marks "none")
-__global__ __launch_bounds__(1024) void k_pair_file_top2(const PairKey* K, int64_t n_pairs, const int64_t* ffirst,
-                                                        int64_t nf, PairFile* F) {
-  const int64_t f = blockIdx.x;
-  const int64_t p0 = ffirst[f], p1 = f + 1 < nf ? ffirst[f + 1] : n_pairs;
-  PairFile T{0ull, 0ull, 0ull, 0ull, 0, 0};
-  for (int64_t p = p0 + threadIdx.x; p < p1; p += blockDim.x) {
-    const PairKey k = K[p];
-    pf_add(T, k.s, k.n, k.t);
-  }
-  __shared__ PairFile sh[1024];
-  sh[threadIdx.x] = T;
-  __syncthreads();
-  for (int w = 512; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      const PairFile U = sh[threadIdx.x + w];
-      if (U.s1) pf_add(T, U.s1, U.n1, U.t1);
-      if (U.s2) pf_add(T, U.s2, U.n2, U.t2);
-      sh[threadIdx.x] = T;
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) F[f] = T;
-}
-__global__ void k_entry_keep(const int64_t* pair_pos, int64_t n, const PairKey* K, const int64_t* fidx,
-                             const PairFile* F, int32_t privacy, int64_t* keep) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int64_t p = pair_pos[i] - 1;
-  const PairKey pk = K[p];
-  bool k = pk.t >= (int64_t)privacy;
-  const PairFile& f = F[fidx[p] - 1];
-  if (f.s2 != 0ull && f.t1 == 1) {  // the file's string-last run is one line: judged with the run before it
-    if ((pk.s == f.s1 && pk.n == f.n1) || (pk.s == f.s2 && pk.n == f.n2)) k = f.t2 + 1 >= (int64_t)privacy;
-  }
-  keep[i] = k ? 1 : 0;
-}
-
-int Matcher::copy_out(void* dst, const void* src, size_t bytes, int dst_memory, std::string* err) {
-  HIPCHK(hipMemcpyAsync(dst, src, bytes, dst_memory == OTR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                        stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  return OTR_OK;
-}
-
-int Matcher::hist_reduce(const void* in, int64_t n, int memory, int rows_in, int privacy, const otr_hist_entry** out,
-                         int64_t* n_out, std::string* err) {
-  try {
-    return hist_reduce_impl(in, n, memory, rows_in, privacy, out, n_out, err);
-  } catch (const DeviceOom& o) {
-    return oom_error(stream, o, err);
-  }
-}
-
-int Matcher::hist_reduce_impl(const void* in, int64_t n, int memory, int rows_in, int privacy, const otr_hist_entry** out,
-                         int64_t* n_out, std::string* err) {
-  GraphState& gs = graph_state();
-  HIPCHK(hipSetDevice(gs.device));
-  if (!stream) HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  *out = nullptr;
-  *n_out = 0;
-  if (n <= 0) return OTR_OK;
-  if (n >= (int64_t)INT32_MAX) {
-    if (err) *err = "too many histogram entries for one call";
-    return OTR_BAD_REQUEST;
-  }
-  auto fail = [&](const char* what) {
-    if (err) *err = what;
-    return OTR_DEVICE_ERROR;
-  };
-  otr_hist_entry* e_in = need<otr_hist_entry>(S_HE_IN, n);
-  otr_hist_entry* e_sorted = need<otr_hist_entry>(S_HE_SORTED, n);
-  otr_hist_entry* e_red = need<otr_hist_entry>(S_HE_RED, n);
-  otr_hist_entry* e_out = need<otr_hist_entry>(S_HE_OUT, n);
-  int32_t* perm_a = need<int32_t>(S_IDX_A, n);
-  int32_t* perm_b = need<int32_t>(S_IDX_B, n);
-  unsigned long long* key_a = need<unsigned long long>(S_KEY_A, n);
-  unsigned long long* key_b = need<unsigned long long>(S_KEY_B, n);
-  int64_t* head = need<int64_t>(S_FILE_HEAD, n);
-  int64_t* pos = need<int64_t>(S_POS_SCAN, n);
-  int64_t* rstart = need<int64_t>(S_FILE_START, n);
-  int64_t* csum = need<int64_t>(S_KEEP, n);
-  if (!e_in || !e_sorted || !e_red || !e_out || !perm_a || !perm_b || !key_a || !key_b || !head || !pos || !rstart ||
-      !csum)
-    return fail("device allocation failed (histogram)");
-  const hipMemcpyKind kind = memory == OTR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  if (rows_in) {
-    otr_tile_row* rows = need<otr_tile_row>(S_ROWS_IN, n);
-    if (!rows) return fail("device allocation failed (histogram)");
-    HIPCHK(hipMemcpyAsync(rows, in, sizeof(otr_tile_row) * n, kind, stream));
-    k_rows_to_entries<<<grid_for(n, 256), 256, 0, stream>>>(rows, n, e_in);
-  } else {
-    HIPCHK(hipMemcpyAsync(e_in, in, sizeof(otr_hist_entry) * n, kind, stream));
-  }
-  const int ni = (int)n;
-  size_t tb_sort = 0, tb_scan = 0;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, key_a, key_b, perm_a, perm_b, ni, 0, 64, stream));
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb_scan, head, pos, ni, stream));
-  void* tmp = need<char>(S_SORT_TMP, std::max(tb_sort, tb_scan));
-  if (!tmp) return fail("device allocation failed (histogram)");
-  // LSD over (file, id, next_id, speed_bin), stable passes over a permutation, each only
-  // as wide as the keys' range: typically two passes of ~49 bits (next id and bin) and
-  // ~47 bits (hour offset and the id in file order), instead of 3 + 3 x 64 bits
-  EntryRange* rng = need<EntryRange>(S_HE_RANGE, 1);
-  if (!rng) return fail("device allocation failed (histogram)");
-  EntryRange hr{0ull, 0ull, 0ull, ~0ull, 0ull, 0ull};
-  HIPCHK(hipMemcpyAsync(rng, &hr, sizeof(hr), hipMemcpyHostToDevice, stream));
-  k_entry_range<<<(unsigned)std::min<int64_t>(kRangeBlocks, (n + 1023) / 1024), 1024, 0, stream>>>(e_in, n, rng);
-  HIPCHK(hipMemcpyAsync(&hr, rng, sizeof(hr), hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  std::vector<std::pair<int, int>> passes;  // (field, end bit), least significant first
-  const int wn = bit_width(hr.next_or), wi = bit_width(hr.id_or), ws = bit_width(hr.bmax - hr.bmin);
-  if (wn + 3 <= 64) passes.push_back({4, wn + 3});
-  else passes.insert(passes.end(), {{3, 3}, {2, wn}});
-  if (!hr.foreign && wi <= 46 && ws + 46 <= 64) passes.push_back({5, std::max(46 + ws, 1)});
-  else passes.insert(passes.end(), {{1, std::max(wi, 1)}, {0, std::max(bit_width(hr.file_or), 1)}});
-  k_iota_i32<<<grid_for(n, 256), 256, 0, stream>>>(perm_a, n);
-  for (const auto& ps : passes) {
-    k_entry_key<<<grid_for(n, 256), 256, 0, stream>>>(e_in, perm_a, n, ps.first, hr.bmin, key_a);
-    size_t tb = tb_sort;
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key_a, key_b, perm_a, perm_b, ni, 0, ps.second, stream));
-    std::swap(perm_a, perm_b);
-  }
-  k_gather_entries<<<grid_for(n, 256), 256, 0, stream>>>(e_in, perm_a, n, e_sorted);
-  // runs of equal keys -> one entry each, counts summed
-  k_entry_heads<<<grid_for(n, 256), 256, 0, stream>>>(e_sorted, n, 0, head);
-  size_t tb = tb_scan;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, head, pos, ni, stream));
-  k_scatter_index<<<grid_for(n, 256), 256, 0, stream>>>(head, pos, n, rstart);
-  k_entry_counts<<<grid_for(n, 256), 256, 0, stream>>>(e_sorted, n, head);  // head reused: counts
-  tb = tb_scan;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, head, csum, ni, stream));
-  int64_t nr = 0;
-  HIPCHK(hipMemcpyAsync(&nr, pos + (n - 1), 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  if (nr < 1 || nr > n) return fail("histogram run split failed");
-  k_entry_reduce<<<grid_for(nr, 256), 256, 0, stream>>>(e_sorted, n, rstart, nr, csum, e_red);
-  otr_hist_entry* result = e_red;
-  int64_t nres = nr;
-  if (privacy > 1) {
-    // pairs over the reduced entries: heads, totals, keep flags, compaction
-    const int nri = (int)nr;
-    k_entry_heads<<<grid_for(nr, 256), 256, 0, stream>>>(e_red, nr, 1, head);
-    tb = tb_scan;
-    HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, head, pos, nri, stream));
-    k_scatter_index<<<grid_for(nr, 256), 256, 0, stream>>>(head, pos, nr, rstart);
-    int64_t np = 0;
-    HIPCHK(hipMemcpyAsync(&np, pos + (nr - 1), 8, hipMemcpyDeviceToHost, stream));
-    k_entry_counts<<<grid_for(nr, 256), 256, 0, stream>>>(e_red, nr, head);
-    tb = tb_scan;
-    HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, head, csum, nri, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    // per file: the string-last and string-second pairs (the reference loop's trailing run)
-    int64_t* fidx = need<int64_t>(S_HE_FIDX, std::max<int64_t>(np, 1));
-    int64_t* fhead = need<int64_t>(S_HE_FHEAD, std::max<int64_t>(np, 1));
-    if (!fidx || !fhead) return fail("device allocation failed (histogram)");
-    k_pair_file_heads<<<grid_for(np, 256), 256, 0, stream>>>(e_red, rstart, np, fhead);
-    tb = tb_scan;
-    HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, fhead, fidx, (int)np, stream));
-    int64_t nf = 0;
-    HIPCHK(hipMemcpyAsync(&nf, fidx + (np - 1), 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    PairFile* pf = need<PairFile>(S_HE_PFILE, std::max<int64_t>(nf, 1));
-    int64_t* ffirst = need<int64_t>(S_HE_FFIRST, std::max<int64_t>(nf, 1));
-    if (!pf || !ffirst) return fail("device allocation failed (histogram)");
-    PairKey* pkey = need<PairKey>(S_HE_PKEY, std::max<int64_t>(np, 1));
-    if (!pkey) return fail("device allocation failed (histogram)");
-    k_scatter_index<<<grid_for(np, 256), 256, 0, stream>>>(fhead, fidx, np, ffirst);
-    k_pair_keys<<<grid_for(np, 256), 256, 0, stream>>>(e_red, rstart, np, nr, csum, pkey);
-    k_pair_file_top2<<<(unsigned)nf, 1024, 0, stream>>>(pkey, np, ffirst, nf, pf);
-    int64_t* keep = head;  // counts no longer needed
-    k_entry_keep<<<grid_for(nr, 256), 256, 0, stream>>>(pos, nr, pkey, fidx, pf, privacy, keep);
-    int64_t* kpos = rstart;  // pair starts no longer needed after k_entry_keep
-    tb = tb_scan;
-    HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, keep, kpos, nri, stream));
-    k_scatter_flagged<otr_hist_entry><<<grid_for(nr, 256), 256, 0, stream>>>(e_red, keep, kpos, nr, e_out);
-    HIPCHK(hipMemcpyAsync(&nres, kpos + (nr - 1), 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    result = e_out;
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(stream));
-  *out = result;
-  *n_out = nres;
-  return OTR_OK;
-}
-
-// ---- K11 ingest (include/otr.h otr_ingest) ----------------------------------------------
-// The uuid grouping stage, shared by K11 and the stream formatter (K16): the M kept lines
-// (kidx, ascending) sorted by (hash, line), the stable sort keeping line order within a
-// hash, then group heads with a byte compare of every equal-hash neighbour: a collision
-// lands in *bad as (line << 8 | OTR_INGEST_E_COLLISION).
-static int uuid_group_heads(hipStream_t stream, const uint64_t* hash, const int32_t* kidx, int64_t M,
-                            const int64_t* uoff, const int32_t* ulen, const uint8_t* d_text, void* tmp, size_t tb_sort,
-                            uint64_t* key_a, uint64_t* key_b, int32_t* val_b, int64_t* head, unsigned long long* bad,
-                            std::string* err) {
-  k_gather_by<uint64_t><<<grid_for(M, 256), 256, 0, stream>>>(hash, kidx, M, key_a);
-  size_t tb = tb_sort;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key_a, key_b, kidx, val_b, (int)M, 0, 64, stream));
-  k_group_heads<<<grid_for(M, 256), 256, 0, stream>>>(key_b, val_b, M, uoff, ulen, d_text, head, bad);
-  return OTR_OK;
-}
-
-int Matcher::ingest(const char* text, int64_t len, int memory, const otr_ingest_format* fmt, otr_ingest_result* out,
-                    std::string* err) {
-  try {
-    return ingest_impl(text, len, memory, fmt, out, err);
-  } catch (const DeviceOom& o) {
-    return oom_error(stream, o, err);
-  }
-}
-
-int Matcher::ingest_impl(const char* text, int64_t len, int memory, const otr_ingest_format* fmt, otr_ingest_result* out,
-                    std::string* err) {
-  GraphState& gs = graph_state();
-  HIPCHK(hipSetDevice(gs.device));
-  if (!stream) HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  memset(out, 0, sizeof(*out));
-  out->bad_line = -1;
-  if (fmt->rules < OTR_INGEST_SHARD || fmt->rules > OTR_INGEST_JAVA_SV || fmt->mode < 0 || fmt->mode > 2 ||
-      fmt->inactivity < 0 || (fmt->rules != OTR_INGEST_SHARD && (fmt->separator < 1 || fmt->separator > 255))) {
-    if (err) *err = "bad ingest format";
-    return OTR_BAD_REQUEST;
-  }
-  for (int k : {fmt->uuid_index, fmt->time_index, fmt->lat_index, fmt->lon_index, fmt->accuracy_index})
-    if (fmt->rules != OTR_INGEST_SHARD && (k < 0 || k > 4096)) {
-      if (err) *err = "bad ingest field index";
-      return OTR_BAD_REQUEST;
-    }
-  out->batch.memory = OTR_MEM_DEVICE;
-  if (len <= 0) return OTR_OK;
-  if (len >= ((int64_t)1 << 40)) {
-    if (err) *err = "ingest text too large";
-    return OTR_BAD_REQUEST;
-  }
-  auto fail = [&](const char* what) {
-    if (err) *err = what;
-    return OTR_DEVICE_ERROR;
-  };
-  // text in HBM, zero-padded to whole 16-byte chunks
-  const int64_t n_chunks = (len + 15) / 16;
-  uint8_t* d_text = need<uint8_t>(S_IN_TEXT, 16 * n_chunks);
-  int64_t* cnt = need<int64_t>(S_IN_CNT, n_chunks);
-  int64_t* cscan = need<int64_t>(S_IN_CSCAN, n_chunks);
-  unsigned long long* bad = need<unsigned long long>(S_IN_BAD, 1);
-  if (!d_text || !cnt || !cscan || !bad) return fail("device allocation failed (ingest)");
-  HIPCHK(hipMemsetAsync(d_text + 16 * (n_chunks - 1), 0, 16, stream));
-  HIPCHK(hipMemcpyAsync(d_text, text, len, memory == OTR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                        stream));
-  HIPCHK(hipMemsetAsync(bad, 0xFF, 8, stream));
-  if (!ev_init) {
-    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-    ev_init = true;
-  }
-  HIPCHK(hipEventRecord(ev[20], stream));
-  size_t tb_scan = 0;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb_scan, cnt, cscan, (int)std::min<int64_t>(n_chunks, INT32_MAX),
-                                          stream));
-  if (n_chunks >= INT32_MAX) return fail("ingest text too large");
-  void* tmp = need<char>(S_IN_TMP, tb_scan);
-  if (!tmp) return fail("device allocation failed (ingest)");
-  k_nl_count<<<grid_for(n_chunks, 256), 256, 0, stream>>>(reinterpret_cast<const uint4*>(d_text), n_chunks, cnt);
-  size_t tb = tb_scan;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, cnt, cscan, (int)n_chunks, stream));
-  int64_t n_nl = 0;
-  uint8_t last = 0;
-  HIPCHK(hipMemcpyAsync(&n_nl, cscan + (n_chunks - 1), 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(&last, d_text + (len - 1), 1, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  // Python's file iteration: a final fragment without '\n' is a line too
-  const int64_t n_lines = n_nl + (last != '\n' ? 1 : 0);
-  out->n_lines = n_lines;
-  if (n_lines >= INT32_MAX) {
-    if (err) *err = "too many lines for one ingest";
-    return OTR_BAD_REQUEST;
-  }
-  const int64_t nL = std::max<int64_t>(n_lines, 1);
-  int64_t* nl = need<int64_t>(S_IN_NL, std::max<int64_t>(n_nl, 1));
-  IngestLines L{};
-  L.text = d_text;
-  L.len = len;
-  L.nl = nl;
-  L.n_nl = n_nl;
-  L.n_lines = n_lines;
-  L.hash = need<uint64_t>(S_IN_HASH, nL);
-  L.uoff = need<int64_t>(S_IN_UOFF, nL);
-  L.ulen = need<int32_t>(S_IN_ULEN, nL);
-  L.time = need<int64_t>(S_IN_TIME, nL);
-  L.lat = need<double>(S_IN_LAT, nL);
-  L.lon = need<double>(S_IN_LON, nL);
-  L.acc = need<float>(S_IN_ACC, nL);
-  L.keep = need<int64_t>(S_IN_KEEP, nL);
-  L.bad = bad;
-  int64_t* kpos = need<int64_t>(S_IN_KPOS, nL);
-  int32_t* kidx = need<int32_t>(S_IN_KIDX, nL);
-  if (!nl || !L.hash || !L.uoff || !L.ulen || !L.time || !L.lat || !L.lon || !L.acc || !L.keep || !kpos || !kidx)
-    return fail("device allocation failed (ingest)");
-  if (n_nl) k_nl_write<<<grid_for(n_chunks, 256), 256, 0, stream>>>(reinterpret_cast<const uint4*>(d_text), n_chunks,
-                                                                    cscan, nl);
-  IngestFmt f{};
-  f.rules = fmt->rules;
-  f.sep = fmt->separator;
-  f.tfmt = fmt->time_format;
-  f.use_bbox = fmt->use_bbox;
-  f.idx[0] = fmt->uuid_index;
-  f.idx[1] = fmt->time_index;
-  f.idx[2] = fmt->lat_index;
-  f.idx[3] = fmt->lon_index;
-  f.idx[4] = fmt->accuracy_index;
-  for (int k = 0; k < 4; ++k) f.bbox[k] = fmt->bbox[k];
-  HIPCHK(hipEventRecord(ev[21], stream));
-  k_ingest_parse<<<grid_for(n_lines, 256), 256, 0, stream>>>(L, f);
-  HIPCHK(hipEventRecord(ev[22], stream));
-  unsigned long long hbad = ~0ull;
-  HIPCHK(hipMemcpyAsync(&hbad, bad, 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  if (hbad != ~0ull) {
-    out->bad_line = (int64_t)(hbad >> 8);
-    out->bad_reason = (int32_t)(hbad & 0xFF);
-    if (err) *err = "malformed probe line " + std::to_string(out->bad_line);
-    return OTR_BAD_REQUEST;
-  }
-  // kept lines (bbox), in line order
-  const int nI = (int)n_lines;
-  size_t tb_sort = 0;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb_scan, L.keep, kpos, nI, stream));
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                            (const int32_t*)nullptr, (int32_t*)nullptr, nI, 0, 64, stream));
-  tmp = need<char>(S_IN_TMP, std::max(tb_scan, tb_sort));
-  if (!tmp) return fail("device allocation failed (ingest)");
-  tb = tb_scan;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, L.keep, kpos, nI, stream));
-  k_scatter_index32<<<grid_for(n_lines, 256), 256, 0, stream>>>(L.keep, kpos, n_lines, kidx);
-  int64_t M = 0;
-  HIPCHK(hipMemcpyAsync(&M, kpos + (n_lines - 1), 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  out->n_kept = M;
-  if (M == 0) return OTR_OK;
-  const int nM = (int)M;
-  uint64_t* key_a = need<uint64_t>(S_IN_KEY_A, M);
-  uint64_t* key_b = need<uint64_t>(S_IN_KEY_B, M);
-  int32_t* val_a = need<int32_t>(S_IN_VAL_A, M);
-  int32_t* val_b = need<int32_t>(S_IN_VAL_B, M);
-  int64_t* head = need<int64_t>(S_IN_HEAD, M);
-  int64_t* gid = need<int64_t>(S_IN_GID, M);
-  int32_t* gfirst = need<int32_t>(S_IN_GFIRST, M);
-  uint32_t* gkey = need<uint32_t>(S_IN_GKEY, nL);
-  if (!key_a || !key_b || !val_a || !val_b || !head || !gid || !gfirst || !gkey)
-    return fail("device allocation failed (ingest)");
-  // 1. group by uuid: sort (hash, line) — the stable sort keeps line order within a hash
-  int rc_groups = uuid_group_heads(stream, L.hash, kidx, M, L.uoff, L.ulen, d_text, tmp, tb_sort, key_a, key_b, val_b,
-                                   head, bad, err);
-  if (rc_groups != OTR_OK) return rc_groups;
-  tb = tb_scan;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, head, gid, nM, stream));
-  k_group_first<<<grid_for(M, 256), 256, 0, stream>>>(head, gid, val_b, M, gfirst);
-  k_group_key<<<grid_for(M, 256), 256, 0, stream>>>(gid, val_b, M, gfirst, gkey);
-  int64_t n_uuid = 0;
-  HIPCHK(hipMemcpyAsync(&n_uuid, gid + (M - 1), 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(&hbad, bad, 8, hipMemcpyDeviceToHost, stream));
-  // 2. final order (first appearance of the uuid, time, line): stable LSD passes
-  int64_t* tkey_a = reinterpret_cast<int64_t*>(key_a);
-  int64_t* tkey_b = reinterpret_cast<int64_t*>(key_b);
-  k_gather_by<int64_t><<<grid_for(M, 256), 256, 0, stream>>>(L.time, kidx, M, tkey_a);
-  tb = tb_sort;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, tkey_a, tkey_b, kidx, val_a, nM, 0, 64, stream));
-  uint32_t* gk_a = reinterpret_cast<uint32_t*>(key_a);
-  uint32_t* gk_b = reinterpret_cast<uint32_t*>(key_b);
-  k_gather_by<uint32_t><<<grid_for(M, 256), 256, 0, stream>>>(gkey, val_a, M, gk_a);
-  int end_bit = 1;
-  while (end_bit < 32 && ((int64_t)1 << end_bit) < n_lines) ++end_bit;
-  tb = tb_sort;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, gk_a, gk_b, val_a, val_b, nM, 0, end_bit, stream));
-  const int32_t* perm = val_b;
-  // 3. windows
-  k_win_heads<<<grid_for(M, 256), 256, 0, stream>>>(perm, M, gkey, L.time, fmt->inactivity, head);
-  tb = tb_scan;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, head, gid, nM, stream));  // gid: window ids now
-  int64_t n_win = 0;
-  HIPCHK(hipMemcpyAsync(&n_win, gid + (M - 1), 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  if (hbad != ~0ull) {
-    out->bad_line = (int64_t)(hbad >> 8);
-    out->bad_reason = (int32_t)(hbad & 0xFF);
-    if (err) *err = "uuid hash collision at line " + std::to_string(out->bad_line);
-    return OTR_BAD_REQUEST;
-  }
-  out->n_uuids = (int32_t)n_uuid;
-  int64_t* ws = need<int64_t>(S_IN_WS, n_win);
-  int64_t* klen = need<int64_t>(S_IN_KLEN, n_win);
-  int64_t* kflag = need<int64_t>(S_IN_KFLAG, n_win);
-  int64_t* poff = need<int64_t>(S_IN_POFF, n_win);
-  int64_t* tpos = need<int64_t>(S_IN_TPOS, n_win);
-  if (!ws || !klen || !kflag || !poff || !tpos) return fail("device allocation failed (ingest)");
-  k_scatter_index<<<grid_for(M, 256), 256, 0, stream>>>(head, gid, M, ws);
-  k_win_len<<<grid_for(n_win, 256), 256, 0, stream>>>(ws, n_win, M, klen, kflag);
-  tb = tb_scan;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, klen, poff, (int)n_win, stream));
-  tb = tb_scan;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, kflag, tpos, (int)n_win, stream));
-  int64_t n_tr = 0, n_pr = 0;
-  HIPCHK(hipMemcpyAsync(&n_tr, tpos + (n_win - 1), 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(&n_pr, poff + (n_win - 1), 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  out->n_traces = (int32_t)n_tr;
-  out->n_probes = n_pr;
-  if (n_tr == 0) return OTR_OK;
-  IngestOut o{};
-  o.trace_off = need<int64_t>(S_IN_T_OFF, n_tr + 1);
-  o.lat = need<double>(S_IN_T_LAT, n_pr);
-  o.lon = need<double>(S_IN_T_LON, n_pr);
-  o.time = need<int64_t>(S_IN_T_TIME, n_pr);
-  o.acc = need<float>(S_IN_T_ACC, n_pr);
-  o.mode = need<uint8_t>(S_IN_T_MODE, n_tr);
-  o.uoff = need<int64_t>(S_IN_T_UOFF, n_tr);
-  o.ulen = need<int32_t>(S_IN_T_ULEN, n_tr);
-  if (!o.trace_off || !o.lat || !o.lon || !o.time || !o.acc || !o.mode || !o.uoff || !o.ulen)
-    return fail("device allocation failed (ingest)");
-  k_win_emit<<<grid_for(M, 256), 256, 0, stream>>>(perm, M, gid, ws, klen, poff, tpos, (int32_t)n_tr, L,
-                                                   (uint8_t)fmt->mode, o);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(ev[23], stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  HIPCHK(hipEventElapsedTime(&out->parse_ms, ev[21], ev[22]));
-  HIPCHK(hipEventElapsedTime(&out->total_ms, ev[20], ev[23]));
-  otr_trace_batch& b = out->batch;
-  b.n_traces = (int32_t)n_tr;
-  b.memory = OTR_MEM_DEVICE;
-  b.trace_offsets = o.trace_off;
-  b.lat = o.lat;
-  b.lon = o.lon;
-  b.time = o.time;
-  b.accuracy = o.acc;
-  b.mode = o.mode;
-  out->d_trace_uuid_off = o.uoff;
-  out->d_trace_uuid_len = o.ulen;
-  return OTR_OK;
-}
-
-// ---- K16 stream formatter (include/otr.h otr_format_messages) ---------------------------
-int Matcher::format_messages(const otr_message_format* fmt, const otr_messages* msgs, otr_format_result* out,
-                             std::string* err) {
-  try {
-    return format_messages_impl(fmt, msgs, out, err);
-  } catch (const DeviceOom& o) {
-    return oom_error(stream, o, err);
-  }
-}
-
-int Matcher::format_messages_impl(const otr_message_format* fmt, const otr_messages* msgs, otr_format_result* out,
-                                  std::string* err) {
-  GraphState& gs = graph_state();
-  HIPCHK(hipSetDevice(gs.device));
-  if (!stream) HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  memset(out, 0, sizeof(*out));
-  out->first_bad = -1;
-  out->points.memory = OTR_MEM_DEVICE;
-  auto refuse = [&](const char* what) {
-    if (err) *err = what;
-    return OTR_BAD_REQUEST;
-  };
-  // the format
-  MsgFmt f{};
-  f.type = fmt->type;
-  f.sep = fmt->separator;
-  f.tfmt = fmt->time_format;
-  f.idx[FM_UUID] = fmt->uuid_index;
-  f.idx[FM_TIME] = fmt->time_index;
-  f.idx[FM_LAT] = fmt->lat_index;
-  f.idx[FM_LON] = fmt->lon_index;
-  f.idx[FM_ACC] = fmt->accuracy_index;
-  if ((f.type != OTR_FORMAT_SV && f.type != OTR_FORMAT_JSON) ||
-      (f.tfmt != OTR_TIME_EPOCH && f.tfmt != OTR_TIME_YMDHMS))
-    return refuse("bad message format");
-  uint8_t h_keys[5 * 64] = {0};
-  if (f.type == OTR_FORMAT_SV) {
-    if (f.sep < 1 || f.sep > 255) return refuse("bad message format: separator");
-    for (int k = 0; k < 5; ++k)
-      if (f.idx[k] < 0 || f.idx[k] > 4096) return refuse("bad message field index");
-  } else {
-    const char* keys[5];
-    keys[FM_UUID] = fmt->uuid_key;
-    keys[FM_TIME] = fmt->time_key;
-    keys[FM_LAT] = fmt->lat_key;
-    keys[FM_LON] = fmt->lon_key;
-    keys[FM_ACC] = fmt->accuracy_key;
-    for (int k = 0; k < 5; ++k) {
-      if (!keys[k]) return refuse("bad message format: null key");
-      const size_t n = strnlen(keys[k], 65);
-      if (n < 1 || n > 64 || memchr(keys[k], '"', n) || memchr(keys[k], '\\', n))
-        return refuse("bad message key: 1..64 bytes, no quote, no backslash");
-      f.klen[k] = (int)n;
-      memcpy(h_keys + 64 * k, keys[k], n);
-    }
-  }
-  // the messages
-  const int64_t len = msgs->len;
-  const bool given = msgs->msg_off != nullptr;
-  if (len < 0 || (len > 0 && !msgs->text) || (given && msgs->n_messages < 0)) return refuse("bad messages");
-  if (len >= ((int64_t)1 << 40)) return refuse("message text too large");
-  if (given && msgs->n_messages >= INT32_MAX) return refuse("too many messages for one call");
-  const hipMemcpyKind kind = msgs->memory == OTR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  auto fail = [&](const char* what) {
-    if (err) *err = what;
-    return OTR_DEVICE_ERROR;
-  };
-  const int64_t n_chunks = std::max<int64_t>((len + 15) / 16, 1);
-  if (n_chunks >= INT32_MAX) return refuse("message text too large");
-  uint8_t* d_text = need<uint8_t>(S_IN_TEXT, 16 * n_chunks);
-  unsigned long long* bad = need<unsigned long long>(S_IN_BAD, 1);
-  uint8_t* d_keys = need<uint8_t>(S_FM_KEYS, sizeof(h_keys));
-  if (!d_text || !bad || !d_keys) return fail("device allocation failed (formatter)");
-  f.keys = d_keys;
-  HIPCHK(hipMemsetAsync(d_text + 16 * (n_chunks - 1), 0, 16, stream));
-  if (len > 0) HIPCHK(hipMemcpyAsync(d_text, msgs->text, len, kind, stream));
-  HIPCHK(hipMemcpyAsync(d_keys, h_keys, sizeof(h_keys), hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemsetAsync(bad, 0xFF, 8, stream));
-  if (!ev_init) {
-    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-    ev_init = true;
-  }
-  HIPCHK(hipEventRecord(ev[20], stream));
-  // message bounds: the given offsets, or K11's newline index
-  int64_t n = 0, n_nl = 0;
-  const int64_t* d_off = nullptr;
-  const int64_t* nl = nullptr;
-  size_t tb_scan = 0;
-  void* tmp = nullptr;
-  if (given) {
-    n = msgs->n_messages;
-    int64_t* off = need<int64_t>(S_FM_OFF, n + 1);
-    int32_t* wrong = need<int32_t>(S_FM_WRONG, 1);
-    if (!off || !wrong) return fail("device allocation failed (formatter)");
-    HIPCHK(hipMemcpyAsync(off, msgs->msg_off, 8 * (n + 1), kind, stream));
-    HIPCHK(hipMemsetAsync(wrong, 0, 4, stream));
-    k_format_check_off<<<grid_for(n + 1, 256), 256, 0, stream>>>(off, n, len, wrong);
-    int32_t h_wrong = 0;
-    HIPCHK(hipMemcpyAsync(&h_wrong, wrong, 4, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    if (h_wrong) return refuse("message offsets must ascend from >= 0 to <= len");
-    d_off = off;
-  } else if (len > 0) {
-    int64_t* cnt = need<int64_t>(S_IN_CNT, n_chunks);
-    int64_t* cscan = need<int64_t>(S_IN_CSCAN, n_chunks);
-    if (!cnt || !cscan) return fail("device allocation failed (formatter)");
-    HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb_scan, cnt, cscan, (int)n_chunks, stream));
-    tmp = need<char>(S_IN_TMP, tb_scan);
-    if (!tmp) return fail("device allocation failed (formatter)");
-    k_nl_count<<<grid_for(n_chunks, 256), 256, 0, stream>>>(reinterpret_cast<const uint4*>(d_text), n_chunks, cnt);
-    size_t tb = tb_scan;
-    HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, cnt, cscan, (int)n_chunks, stream));
-    uint8_t last = 0;
-    HIPCHK(hipMemcpyAsync(&n_nl, cscan + (n_chunks - 1), 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(&last, d_text + (len - 1), 1, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    n = n_nl + (last != '\n' ? 1 : 0);  // a final fragment without '\n' is a message too
-    if (n >= INT32_MAX) return refuse("too many messages for one call");
-    int64_t* nlw = need<int64_t>(S_IN_NL, std::max<int64_t>(n_nl, 1));
-    if (!nlw) return fail("device allocation failed (formatter)");
-    if (n_nl) k_nl_write<<<grid_for(n_chunks, 256), 256, 0, stream>>>(reinterpret_cast<const uint4*>(d_text), n_chunks,
-                                                                      cscan, nlw);
-    nl = nlw;
-  }
-  out->n_messages = n;
-  if (n == 0) return OTR_OK;
-  const int64_t* ts_in = nullptr;
-  if (msgs->timestamp) {
-    if (kind == hipMemcpyHostToDevice) {
-      int64_t* t = need<int64_t>(S_FM_TSIN, n);
-      if (!t) return fail("device allocation failed (formatter)");
-      HIPCHK(hipMemcpyAsync(t, msgs->timestamp, 8 * n, kind, stream));
-      ts_in = t;
-    } else {
-      ts_in = msgs->timestamp;
-    }
-  }
-  FormatMsgs M{};
-  M.text = d_text;
-  M.len = len;
-  M.nl = nl;
-  M.n_nl = n_nl;
-  M.off = d_off;
-  M.n = n;
-  M.status = need<int32_t>(S_FM_STATUS, n);
-  M.hash = need<uint64_t>(S_IN_HASH, n);
-  M.uoff = need<int64_t>(S_IN_UOFF, n);
-  M.ulen = need<int32_t>(S_IN_ULEN, n);
-  M.time = need<int64_t>(S_IN_TIME, n);
-  M.lat = need<float>(S_FM_P_LAT, n);
-  M.lon = need<float>(S_FM_P_LON, n);
-  M.acc = need<int32_t>(S_FM_P_ACC, n);
-  M.flag = need<int64_t>(S_FM_FLAG, n);
-  M.bad = bad;
-  int64_t* scan = need<int64_t>(S_IN_KPOS, n);
-  if (!M.status || !M.hash || !M.uoff || !M.ulen || !M.time || !M.lat || !M.lon || !M.acc || !M.flag || !scan)
-    return fail("device allocation failed (formatter)");
-  const int nI = (int)n;
-  size_t tb_sort = 0;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb_scan, M.flag, scan, nI, stream));
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                            (const int32_t*)nullptr, (int32_t*)nullptr, nI, 0, 64, stream));
-  tmp = need<char>(S_IN_TMP, std::max(tb_scan, tb_sort));
-  if (!tmp) return fail("device allocation failed (formatter)");
-  // parse → flag → scan → emit
-  HIPCHK(hipEventRecord(ev[21], stream));
-  k_format_parse<<<grid_for(n, 256), 256, 0, stream>>>(M, f);
-  HIPCHK(hipEventRecord(ev[22], stream));
-  size_t tb = tb_scan;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, M.flag, scan, nI, stream));
-  int64_t total = 0;
-  unsigned long long hbad = ~0ull;
-  HIPCHK(hipMemcpyAsync(&total, scan + (n - 1), 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(&hbad, bad, 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  const int64_t P = total & 0xFFFFFFFFll, n_drop = total >> 32;
-  const int64_t first_bad = hbad == ~0ull ? -1 : (int64_t)(hbad >> 8);
-  const int32_t first_reason = hbad == ~0ull ? 0 : (int32_t)(hbad & 0xFF);
-  const int64_t nP = std::max<int64_t>(P, 1);
-  FormatOut o{};
-  o.key = need<unsigned long long>(S_FM_KEY, nP);
-  o.lat = need<float>(S_FM_LAT, nP);
-  o.lon = need<float>(S_FM_LON, nP);
-  o.acc = need<int32_t>(S_FM_ACC, nP);
-  o.time = need<int64_t>(S_FM_TIME, nP);
-  o.ts = need<int64_t>(S_FM_TS, nP);
-  o.msg = need<int64_t>(S_FM_MSG, nP);
-  o.uoff = need<int64_t>(S_FM_UOFF, nP);
-  o.ulen = need<int32_t>(S_FM_ULEN, nP);
-  o.kidx = need<int32_t>(S_IN_KIDX, nP);
-  if (!o.key || !o.lat || !o.lon || !o.acc || !o.time || !o.ts || !o.msg || !o.uoff || !o.ulen || !o.kidx)
-    return fail("device allocation failed (formatter)");
-  if (P > 0) {
-    k_format_emit<<<grid_for(n, 256), 256, 0, stream>>>(M, scan, ts_in, msgs->timestamp_all, o);
-    // two different uuids of the chunk under one hash: K11's stage, K11's refusal
-    uint64_t* key_a = need<uint64_t>(S_IN_KEY_A, P);
-    uint64_t* key_b = need<uint64_t>(S_IN_KEY_B, P);
-    int32_t* val_b = need<int32_t>(S_IN_VAL_B, P);
-    int64_t* head = need<int64_t>(S_IN_HEAD, P);
-    if (!key_a || !key_b || !val_b || !head) return fail("device allocation failed (formatter)");
-    HIPCHK(hipMemsetAsync(bad, 0xFF, 8, stream));
-    const int rc = uuid_group_heads(stream, M.hash, o.kidx, P, M.uoff, M.ulen, d_text, tmp, tb_sort, key_a, key_b,
-                                    val_b, head, bad, err);
-    if (rc != OTR_OK) return rc;
-    HIPCHK(hipMemcpyAsync(&hbad, bad, 8, hipMemcpyDeviceToHost, stream));
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(ev[23], stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  if (P > 0 && hbad != ~0ull) {
-    out->first_bad = (int64_t)(hbad >> 8);
-    out->first_bad_reason = (int32_t)(hbad & 0xFF);
-    if (err) *err = "uuid hash collision at message " + std::to_string(out->first_bad);
-    return OTR_BAD_REQUEST;
-  }
-  HIPCHK(hipEventElapsedTime(&out->parse_ms, ev[21], ev[22]));
-  HIPCHK(hipEventElapsedTime(&out->total_ms, ev[20], ev[23]));
-  out->n_points = P;
-  out->n_dropped = n_drop;
-  out->n_unsupported = n - P - n_drop;
-  out->first_bad = first_bad;
-  out->first_bad_reason = first_reason;
-  out->points.n = P;
-  out->points.key = (const uint64_t*)o.key;
-  out->points.lat = o.lat;
-  out->points.lon = o.lon;
-  out->points.accuracy = o.acc;
-  out->points.time = o.time;
-  out->points.timestamp = o.ts;
-  fmt_text = d_text;
-  fmt_text_len = len;
-  out->d_message = o.msg;
-  out->d_uuid_off = o.uoff;
-  out->d_uuid_len = o.ulen;
-  out->d_status = M.status;
-  return OTR_OK;
-}
-
-// K11's uuid_hash on the host: the key of a changelog record (otr_uuid_key)
-uint64_t uuid_key_host(const char* uuid, int64_t len) {
-  return uuid_hash(reinterpret_cast<const uint8_t*>(uuid), 0, len > 0 ? len : 0);
 }
 
 }  // namespace otr

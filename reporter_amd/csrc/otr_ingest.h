@@ -530,17 +530,6 @@ __global__ void k_ingest_parse(IngestLines L, IngestFmt f) {
   L.keep[i] = 1;
 }
 
-template <class T>
-__global__ void k_gather_by(const T* src, const int32_t* idx, int64_t n, T* dst) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = src[idx[i]];
-}
-
-__global__ void k_scatter_index32(const int64_t* flag, const int64_t* pos, int64_t n, int32_t* out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && flag[i]) out[pos[i] - 1] = (int32_t)i;
-}
-
 // uuid groups over lines sorted by (hash, line): heads, and a string check of every
 // equal-hash neighbour (a collision is refused, never merged)
 __global__ void k_group_heads(const uint64_t* hash, const int32_t* line, int64_t m, const int64_t* uoff,

@@ -2,9 +2,6 @@
 // device memory, the passes of a chunk (insert, assign, group), the rounds (advance, gather,
 // match, commit), punctuate and the snapshot; restore, export as records and take (K17).
 // include/otr.h otr_sessions_* for the rules.
-#include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -12,29 +9,14 @@
 #include <type_traits>
 #include <vector>
 
+#include "otr_devscan.h"
 #include "otr_engine.h"
 #include "otr_launch.h"
 #include "otr_sessions.h"
 
-#define HIPCHK(x)                                                                        \
-  do {                                                                                   \
-    hipError_t e_ = (x);                                                                 \
-    if (e_ != hipSuccess) {                                                              \
-      if (err) *err = std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x;    \
-      return OTR_DEVICE_ERROR;                                                           \
-    }                                                                                    \
-  } while (0)
-
 namespace otr {
 
 namespace {
-
-struct SesOom {
-  const char* name;
-  size_t bytes;
-};
-
-unsigned ses_grid(int64_t n, int threads) { return (unsigned)std::max<int64_t>(1, (n + threads - 1) / threads); }
 
 // growable buffers of a chunk, a round and a result
 enum SesBuf {
@@ -67,7 +49,8 @@ const char* const kBufName[B_NUM] = {
 
 }  // namespace
 
-struct SessionStore {
+struct SessionStore : DevPool {  // the growable buffers: the pool's slots, by SesBuf
+  SessionStore() : DevPool(PoolOwner::sessions, kBufName, B_NUM) {}
   otr_session_config cfg{};
   hipStream_t stream = nullptr;
   std::vector<void*> fixed;
@@ -79,10 +62,6 @@ struct SessionStore {
   int32_t n_rebuilds = 0;
   hipEvent_t ev[2];
   bool ev_init = false;
-  struct {
-    void* p = nullptr;
-    size_t bytes = 0;
-  } b[B_NUM];
   // the chunk and the round
   SesChunk ch{};
   int32_t n_seg = 0, W = 0, n_list = 0;
@@ -122,36 +101,22 @@ struct SessionStore {
   int32_t live() const { return cfg.max_sessions - h_cnt[SES_NFREE]; }
 
   template <class T>
-  T* buf(int slot, size_t n) {
-    const size_t bytes = (n ? n : 1) * sizeof(T);
-    if (b[slot].bytes < bytes) {
-      if (b[slot].p) (void)hipFree(b[slot].p);
-      b[slot].p = nullptr;
-      b[slot].bytes = 0;
-      const size_t nb = bytes + bytes / 4;
-      if (hipMalloc(&b[slot].p, nb) != hipSuccess) {
-        (void)hipGetLastError();
-        b[slot].p = nullptr;
-        throw SesOom{kBufName[slot], nb};
-      }
-      b[slot].bytes = nb;
-    }
-    return (T*)b[slot].p;
-  }
-  template <class T>
   T* fix(size_t n, const char* name) {
     void* p = nullptr;
     const size_t bytes = (n ? n : 1) * sizeof(T);
     if (hipMalloc(&p, bytes) != hipSuccess) {
       (void)hipGetLastError();
-      throw SesOom{name, bytes};
+      throw DeviceOom{PoolOwner::sessions, name, -1, bytes};
     }
     fixed.push_back(p);
     return (T*)p;
   }
 
-  int scan32(const int32_t* in, int32_t* out, int64_t n, std::string* err);
-  int scan64(const int64_t* in, int64_t* out, int64_t n, std::string* err);
+  // inclusive sum of 32- or 64-bit counts, the workspace in B_TMP
+  template <class T>
+  int scan(const T* in, T* out, int64_t n, std::string* err) {
+    return pool_scan(*this, B_TMP, in, out, n, stream, err);
+  }
   int alloc(std::string* err);
   int rebuild(std::string* err);
   int chunk_begin(const otr_session_points* pts, const SesNamesIn* nm, std::string* err);
@@ -178,27 +143,10 @@ void sessions_destroy(SessionStore* s) {
   if (!s) return;
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   for (void* p : s->fixed) (void)hipFree(p);
-  for (auto& x : s->b)
-    if (x.p) (void)hipFree(x.p);
+  s->release();
   if (s->ev_init)
     for (auto& e : s->ev) (void)hipEventDestroy(e);
   delete s;
-}
-
-int SessionStore::scan32(const int32_t* in, int32_t* out, int64_t n, std::string* err) {
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, in, out, (int)n, stream));
-  void* tmp = buf<char>(B_TMP, tb);
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, in, out, (int)n, stream));
-  return OTR_OK;
-}
-
-int SessionStore::scan64(const int64_t* in, int64_t* out, int64_t n, std::string* err) {
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, in, out, (int)n, stream));
-  void* tmp = buf<char>(B_TMP, tb);
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, in, out, (int)n, stream));
-  return OTR_OK;
 }
 
 int SessionStore::alloc(std::string* err) {
@@ -251,7 +199,7 @@ int SessionStore::alloc(std::string* err) {
 int SessionStore::rebuild(std::string* err) {
   HIPCHK(hipMemsetAsync(spare.key, 0xFF, 8 * (size_t)spare.cap, stream));
   HIPCHK(hipMemsetAsync(spare.slot, 0xFF, 4 * (size_t)spare.cap, stream));
-  k_ses_rebuild<<<ses_grid(tab.cap, 256), 256, 0, stream>>>(tab, spare, st);
+  k_ses_rebuild<<<grid_ceil1(tab.cap, 256), 256, 0, stream>>>(tab, spare, st);
   HIPCHK(hipGetLastError());
   std::swap(tab, spare);
   h_cnt[SES_DEAD] = 0;
@@ -279,9 +227,9 @@ int SessionStore::names_in(const otr_session_names* names, int64_t n, int memory
     out->len = names->len;
     return OTR_OK;
   }
-  uint8_t* bytes = buf<uint8_t>(B_NM_BYTES, names->n_bytes);
-  int64_t* off = buf<int64_t>(B_NM_OFF, n);
-  int32_t* len = buf<int32_t>(B_NM_LEN, n);
+  uint8_t* bytes = get<uint8_t>(B_NM_BYTES, names->n_bytes);
+  int64_t* off = get<int64_t>(B_NM_OFF, n);
+  int32_t* len = get<int32_t>(B_NM_LEN, n);
   if (names->n_bytes > 0)
     HIPCHK(hipMemcpyAsync(bytes, names->bytes, (size_t)names->n_bytes, hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(off, names->off, 8 * (size_t)n, hipMemcpyHostToDevice, stream));
@@ -302,23 +250,23 @@ int SessionStore::chunk_begin(const otr_session_points* pts, const SesNamesIn* n
     return OTR_BAD_REQUEST;
   }
   if (h_cnt[SES_DEAD] > 0 && live() + h_cnt[SES_DEAD] > cfg.max_sessions && (rc = rebuild(err))) return rc;
-  unsigned long long* key = buf<unsigned long long>(B_KEY, n);
-  float* lat = buf<float>(B_LAT, n);
-  float* lon = buf<float>(B_LON, n);
-  int32_t* acc = buf<int32_t>(B_ACC, n);
-  int64_t* time = buf<int64_t>(B_TIME, n);
-  int64_t* ts = buf<int64_t>(B_TS, n);
-  int32_t* entry = buf<int32_t>(B_ENTRY, n);
-  int32_t* fresh = buf<int32_t>(B_NEW, n);
-  int32_t* rank = buf<int32_t>(B_RANK, n);
-  uint32_t* lane_slot = buf<uint32_t>(B_LANE_SLOT, n);
-  int32_t* idx = buf<int32_t>(B_IDX, n);
-  uint32_t* sorted_slot = buf<uint32_t>(B_SORT_SLOT, n);
-  int32_t* sorted_idx = buf<int32_t>(B_SORT_IDX, n);
-  int32_t* head = buf<int32_t>(B_HEAD, n);
-  int32_t* seg_incl = buf<int32_t>(B_SEG_INCL, n);
-  int32_t* trip = buf<int32_t>(B_TRIP, n);
-  buf<int32_t>(B_TRIP_INCL, n);
+  unsigned long long* key = get<unsigned long long>(B_KEY, n);
+  float* lat = get<float>(B_LAT, n);
+  float* lon = get<float>(B_LON, n);
+  int32_t* acc = get<int32_t>(B_ACC, n);
+  int64_t* time = get<int64_t>(B_TIME, n);
+  int64_t* ts = get<int64_t>(B_TS, n);
+  int32_t* entry = get<int32_t>(B_ENTRY, n);
+  int32_t* fresh = get<int32_t>(B_NEW, n);
+  int32_t* rank = get<int32_t>(B_RANK, n);
+  uint32_t* lane_slot = get<uint32_t>(B_LANE_SLOT, n);
+  int32_t* idx = get<int32_t>(B_IDX, n);
+  uint32_t* sorted_slot = get<uint32_t>(B_SORT_SLOT, n);
+  int32_t* sorted_idx = get<int32_t>(B_SORT_IDX, n);
+  int32_t* head = get<int32_t>(B_HEAD, n);
+  int32_t* seg_incl = get<int32_t>(B_SEG_INCL, n);
+  int32_t* trip = get<int32_t>(B_TRIP, n);
+  get<int32_t>(B_TRIP_INCL, n);
   const hipMemcpyKind kind = pts->memory == OTR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   HIPCHK(hipMemcpyAsync(key, pts->key, 8 * n, kind, stream));
   HIPCHK(hipMemcpyAsync(lat, pts->lat, 4 * n, kind, stream));
@@ -327,23 +275,21 @@ int SessionStore::chunk_begin(const otr_session_points* pts, const SesNamesIn* n
   HIPCHK(hipMemcpyAsync(time, pts->time, 8 * n, kind, stream));
   HIPCHK(hipMemcpyAsync(ts, pts->timestamp, 8 * n, kind, stream));
   ch = SesChunk{n, key, lat, lon, acc, time, ts};
-  const unsigned g = ses_grid(n, 256);
+  const unsigned g = grid_ceil1(n, 256);
   // 1. keys into the table
   HIPCHK(hipMemsetAsync(cnt + SES_FLAGS, 0, 4, stream));
   k_ses_insert<<<g, 256, 0, stream>>>(tab, ch, entry, fresh, cnt);
-  if ((rc = scan32(fresh, rank, n, err))) return rc;
+  if ((rc = scan(fresh, rank, n, err))) return rc;
   int32_t n_new = 0, flags = 0;
   unsigned long long h_bad = kSesNoBad;
   if (nm) {  // K18: the names against the directory, read back with the chunk's own refusals
-    unsigned long long* bad = buf<unsigned long long>(B_RS_BAD, 1);
+    unsigned long long* bad = get<unsigned long long>(B_RS_BAD, 1);
     HIPCHK(hipMemsetAsync(bad, 0xFF, 8, stream));
     k_ses_name_first<<<g, 256, 0, stream>>>(tab, n, entry, name_first);
     k_ses_name_check<<<g, 256, 0, stream>>>(tab, dir, *nm, n, entry, name_first, bad);
     HIPCHK(hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, stream));
   }
-  HIPCHK(hipMemcpyAsync(&n_new, rank + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(&flags, cnt + SES_FLAGS, 4, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
+  if ((rc = read_back(stream, err, fetch(&n_new, rank + (n - 1)), fetch(&flags, cnt + SES_FLAGS)))) return rc;
   const bool own = flags || n_new > h_cnt[SES_NFREE];
   if (own || h_bad != kSesNoBad) {
     if (nm) k_ses_name_unmark<<<g, 256, 0, stream>>>(n, entry, fresh, name_first);
@@ -373,19 +319,13 @@ int SessionStore::chunk_begin(const otr_session_points* pts, const SesNamesIn* n
   k_ses_lane_slot<<<g, 256, 0, stream>>>(tab, n, entry, lane_slot, idx);
   int bits = 1;
   while (bits < 32 && ((int64_t)1 << bits) < (int64_t)cfg.max_sessions) ++bits;
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, lane_slot, sorted_slot, idx, sorted_idx, (int)n, 0, bits,
-                                            stream));
-  void* tmp = buf<char>(B_TMP, tb);
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, lane_slot, sorted_slot, idx, sorted_idx, (int)n, 0, bits,
-                                            stream));
+  if ((rc = pool_sort(*this, B_TMP, lane_slot, sorted_slot, idx, sorted_idx, n, 0, bits, stream, err))) return rc;
   k_ses_heads<<<g, 256, 0, stream>>>(sorted_slot, n, head);
-  if ((rc = scan32(head, seg_incl, n, err))) return rc;
-  HIPCHK(hipMemcpyAsync(&n_seg, seg_incl + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  int32_t* seg_slot = buf<int32_t>(B_SEG_SLOT, n_seg);
-  int32_t* seg_cur = buf<int32_t>(B_SEG_CUR, n_seg);
-  int32_t* seg_end = buf<int32_t>(B_SEG_END, n_seg);
+  if ((rc = scan(head, seg_incl, n, err))) return rc;
+  if ((rc = read_back(stream, err, fetch(&n_seg, seg_incl + (n - 1))))) return rc;
+  int32_t* seg_slot = get<int32_t>(B_SEG_SLOT, n_seg);
+  int32_t* seg_cur = get<int32_t>(B_SEG_CUR, n_seg);
+  int32_t* seg_end = get<int32_t>(B_SEG_END, n_seg);
   k_ses_segments<<<g, 256, 0, stream>>>(sorted_slot, seg_incl, n, seg_slot, seg_cur, seg_end);
   HIPCHK(hipMemsetAsync(trip, 0, 4 * n, stream));
   HIPCHK(hipGetLastError());
@@ -394,7 +334,7 @@ int SessionStore::chunk_begin(const otr_session_points* pts, const SesNamesIn* n
 }
 
 int SessionStore::release_list(const int32_t* list, int32_t n, std::string* err) {
-  k_ses_release<<<ses_grid(n, 256), 256, 0, stream>>>(n, list, tab, st, free_list, cnt);
+  k_ses_release<<<grid_ceil1(n, 256), 256, 0, stream>>>(n, list, tab, st, free_list, cnt);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
@@ -404,9 +344,9 @@ int SessionStore::release_list(const int32_t* list, int32_t n, std::string* err)
 // offsets, then one wave per window (win_slot / win_n of W windows are in place)
 int SessionStore::gather(std::string* err) {
   int rc;
-  int64_t* off = buf<int64_t>(B_G_OFF, (size_t)W + 1);
+  int64_t* off = get<int64_t>(B_G_OFF, (size_t)W + 1);
   HIPCHK(hipMemsetAsync(off, 0, 8, stream));
-  if ((rc = scan64((int64_t*)b[B_W_N].p, off + 1, W, err))) return rc;
+  if ((rc = scan((int64_t*)b[B_W_N].p, off + 1, W, err))) return rc;
   w_key.resize(W);
   w_trig.resize(W);
   w_n.resize(W);
@@ -415,11 +355,11 @@ int SessionStore::gather(std::string* err) {
   HIPCHK(hipMemcpyAsync(w_trig.data(), b[B_W_TRIG].p, 8 * (size_t)W, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipMemcpyAsync(w_n.data(), b[B_W_N].p, 8 * (size_t)W, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
-  double* lat = buf<double>(B_G_LAT, P);
-  double* lon = buf<double>(B_G_LON, P);
-  int64_t* time = buf<int64_t>(B_G_TIME, P);
-  float* acc = buf<float>(B_G_ACC, P);
-  uint8_t* mode = buf<uint8_t>(B_G_MODE, W);
+  double* lat = get<double>(B_G_LAT, P);
+  double* lon = get<double>(B_G_LON, P);
+  int64_t* time = get<int64_t>(B_G_TIME, P);
+  float* acc = get<float>(B_G_ACC, P);
+  uint8_t* mode = get<uint8_t>(B_G_MODE, W);
   k_ses_gather<false><<<(unsigned)W, 64, 0, stream>>>(W, (const int32_t*)b[B_W_SLOT].p, off, st, lat, lon, time, acc,
                                                       mode, (uint8_t)cfg.mode, nullptr, nullptr, nullptr);
   HIPCHK(hipGetLastError());
@@ -436,22 +376,21 @@ int SessionStore::round(std::string* err) {
   int32_t* trip = (int32_t*)b[B_TRIP].p;
   int32_t* trip_incl = (int32_t*)b[B_TRIP_INCL].p;
   const SesGate gate{cfg.report_dist, cfg.report_count, cfg.report_time};
-  k_ses_advance<<<ses_grid(n_seg, 64), 64, 0, stream>>>(n_seg, (const int32_t*)b[B_SEG_SLOT].p,
-                                                        (int32_t*)b[B_SEG_CUR].p, (const int32_t*)b[B_SEG_END].p,
-                                                        (const int32_t*)b[B_SORT_IDX].p, ch, st, gate, trip, cnt);
-  if ((rc = scan32(trip, trip_incl, n, err))) return rc;
-  HIPCHK(hipMemcpyAsync(&W, trip_incl + (n - 1), 4, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
+  k_ses_advance<<<grid_ceil1(n_seg, 64), 64, 0, stream>>>(n_seg, (const int32_t*)b[B_SEG_SLOT].p,
+                                                          (int32_t*)b[B_SEG_CUR].p, (const int32_t*)b[B_SEG_END].p,
+                                                          (const int32_t*)b[B_SORT_IDX].p, ch, st, gate, trip, cnt);
+  if ((rc = scan(trip, trip_incl, n, err))) return rc;
+  if ((rc = read_back(stream, err, fetch(&W, trip_incl + (n - 1))))) return rc;
   if (W == 0) {  // the chunk is consumed: sessions left empty are deleted
     chunk_open = false;
     return release_list((const int32_t*)b[B_SEG_SLOT].p, n_seg, err);
   }
-  int32_t* win_slot = buf<int32_t>(B_W_SLOT, W);
-  int64_t* win_trig = buf<int64_t>(B_W_TRIG, W);
-  int64_t* win_n = buf<int64_t>(B_W_N, W);
-  unsigned long long* win_key = buf<unsigned long long>(B_W_KEY, W);
-  k_ses_windows<<<ses_grid(n, 256), 256, 0, stream>>>(n, trip, trip_incl, (const uint32_t*)b[B_LANE_SLOT].p, st,
-                                                      win_slot, win_trig, win_n, win_key);
+  int32_t* win_slot = get<int32_t>(B_W_SLOT, W);
+  int64_t* win_trig = get<int64_t>(B_W_TRIG, W);
+  int64_t* win_n = get<int64_t>(B_W_N, W);
+  unsigned long long* win_key = get<unsigned long long>(B_W_KEY, W);
+  k_ses_windows<<<grid_ceil1(n, 256), 256, 0, stream>>>(n, trip, trip_incl, (const uint32_t*)b[B_LANE_SLOT].p, st,
+                                                        win_slot, win_trig, win_n, win_key);
   if ((rc = gather(err))) return rc;
   pending = true;
   return OTR_OK;
@@ -476,10 +415,10 @@ void SessionStore::fill_batch(otr_trace_batch* bt) {
 }
 
 int SessionStore::commit(const int32_t* su, const int32_t* status, int memory, std::string* err) {
-  int32_t* d_su = buf<int32_t>(B_W_SU, W);
-  int32_t* d_status = buf<int32_t>(B_W_STATUS, W);
-  int32_t* d_su_out = buf<int32_t>(B_W_SU_OUT, W);
-  int32_t* d_trim = buf<int32_t>(B_W_TRIM, W);
+  int32_t* d_su = get<int32_t>(B_W_SU, W);
+  int32_t* d_status = get<int32_t>(B_W_STATUS, W);
+  int32_t* d_su_out = get<int32_t>(B_W_SU_OUT, W);
+  int32_t* d_trim = get<int32_t>(B_W_TRIM, W);
   const hipMemcpyKind kind = memory == OTR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   HIPCHK(hipMemcpyAsync(d_su, su, 4 * (size_t)W, kind, stream));
   HIPCHK(hipMemcpyAsync(d_status, status, 4 * (size_t)W, kind, stream));
@@ -539,7 +478,7 @@ int SessionStore::match(Matcher& m, std::string* err) {
     if (w0 > 0 || w1 < W) {  // offsets from zero for this part
       sub.assign(1, 0);
       for (int32_t w = w0; w < w1; ++w) sub.push_back(sub.back() + w_n[w]);
-      int64_t* d_sub = buf<int64_t>(B_SUB_OFF, sub.size());
+      int64_t* d_sub = get<int64_t>(B_SUB_OFF, sub.size());
       HIPCHK(hipMemcpyAsync(d_sub, sub.data(), 8 * sub.size(), hipMemcpyHostToDevice, stream));
       HIPCHK(hipStreamSynchronize(stream));
       bt.trace_offsets = d_sub;
@@ -606,7 +545,7 @@ int SessionStore::result_end(otr_session_result* out, bool with_device, std::str
   if (!with_device) return OTR_OK;
   auto up = [&](int slot, auto& v, auto** dst) -> int {
     using T = typename std::remove_reference_t<decltype(v)>::value_type;
-    T* d = buf<T>(slot, v.size());
+    T* d = get<T>(slot, v.size());
     if (!v.empty()) HIPCHK(hipMemcpyAsync(d, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, stream));
     *dst = d;
     return OTR_OK;
@@ -651,8 +590,8 @@ bool sessions_last_reports(SessionStore* s, SessionReports* out) {
 // in B_L_KEY2 / B_L_SLOT2
 int SessionStore::list_sessions(int stale_only, int64_t ts, std::string* err) {
   const int32_t ms = cfg.max_sessions;
-  int32_t* flag = buf<int32_t>(B_FLAG, ms);
-  k_ses_flag<<<ses_grid(ms, 256), 256, 0, stream>>>(st, stale_only, ts, cfg.session_gap, flag);
+  int32_t* flag = get<int32_t>(B_FLAG, ms);
+  k_ses_flag<<<grid_ceil1(ms, 256), 256, 0, stream>>>(st, stale_only, ts, cfg.session_gap, flag);
   return list_flagged(err);
 }
 
@@ -661,20 +600,16 @@ int SessionStore::list_flagged(std::string* err) {
   int rc;
   const int32_t ms = cfg.max_sessions;
   int32_t* flag = (int32_t*)b[B_FLAG].p;
-  int32_t* incl = buf<int32_t>(B_FLAG_INCL, ms);
-  if ((rc = scan32(flag, incl, ms, err))) return rc;
-  HIPCHK(hipMemcpyAsync(&n_list, incl + (ms - 1), 4, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
+  int32_t* incl = get<int32_t>(B_FLAG_INCL, ms);
+  if ((rc = scan(flag, incl, ms, err))) return rc;
+  if ((rc = read_back(stream, err, fetch(&n_list, incl + (ms - 1))))) return rc;
   if (n_list == 0) return OTR_OK;
-  unsigned long long* key = buf<unsigned long long>(B_L_KEY, n_list);
-  int32_t* slot = buf<int32_t>(B_L_SLOT, n_list);
-  unsigned long long* key2 = buf<unsigned long long>(B_L_KEY2, n_list);
-  int32_t* slot2 = buf<int32_t>(B_L_SLOT2, n_list);
-  k_ses_list<<<ses_grid(ms, 256), 256, 0, stream>>>(st, flag, incl, key, slot);
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key, key2, slot, slot2, n_list, 0, 64, stream));
-  void* tmp = buf<char>(B_TMP, tb);
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key2, slot, slot2, n_list, 0, 64, stream));
+  unsigned long long* key = get<unsigned long long>(B_L_KEY, n_list);
+  int32_t* slot = get<int32_t>(B_L_SLOT, n_list);
+  unsigned long long* key2 = get<unsigned long long>(B_L_KEY2, n_list);
+  int32_t* slot2 = get<int32_t>(B_L_SLOT2, n_list);
+  k_ses_list<<<grid_ceil1(ms, 256), 256, 0, stream>>>(st, flag, incl, key, slot);
+  if ((rc = pool_sort(*this, B_TMP, key, key2, slot, slot2, n_list, 0, 64, stream, err))) return rc;
   HIPCHK(hipGetLastError());
   return OTR_OK;
 }
@@ -686,8 +621,8 @@ int SessionStore::names_list(std::string* err) {
   const int32_t ns = n_list;
   nl_off.assign((size_t)ns + 1, 0);
   nl_bytes.clear();
-  int64_t* off = buf<int64_t>(B_NL_OFF, (size_t)ns + 1);
-  buf<uint8_t>(B_NL_BYTES, 0);
+  int64_t* off = get<int64_t>(B_NL_OFF, (size_t)ns + 1);
+  get<uint8_t>(B_NL_BYTES, 0);
   HIPCHK(hipMemsetAsync(off, 0, 8, stream));
   names_have = true;
   if (ns == 0) {
@@ -695,14 +630,14 @@ int SessionStore::names_list(std::string* err) {
     return OTR_OK;
   }
   const int32_t* list = (const int32_t*)b[B_L_SLOT2].p;
-  int64_t* len = buf<int64_t>(B_NL_LEN, ns);
-  k_ses_name_len<<<ses_grid(ns, 256), 256, 0, stream>>>(ns, list, dir, len);
-  if ((rc = scan64(len, off + 1, ns, err))) return rc;
+  int64_t* len = get<int64_t>(B_NL_LEN, ns);
+  k_ses_name_len<<<grid_ceil1(ns, 256), 256, 0, stream>>>(ns, list, dir, len);
+  if ((rc = scan(len, off + 1, ns, err))) return rc;
   HIPCHK(hipMemcpyAsync(nl_off.data(), off, 8 * ((size_t)ns + 1), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
   const int64_t nb = nl_off[ns];
-  uint8_t* bytes = buf<uint8_t>(B_NL_BYTES, nb);
-  k_ses_name_gather<<<ses_grid(ns, 256), 256, 0, stream>>>(ns, list, off, dir, bytes);
+  uint8_t* bytes = get<uint8_t>(B_NL_BYTES, nb);
+  k_ses_name_gather<<<grid_ceil1(ns, 256), 256, 0, stream>>>(ns, list, off, dir, bytes);
   HIPCHK(hipGetLastError());
   nl_bytes.resize((size_t)nb);
   if (nb > 0) HIPCHK(hipMemcpyAsync(nl_bytes.data(), bytes, (size_t)nb, hipMemcpyDeviceToHost, stream));
@@ -714,23 +649,23 @@ int SessionStore::names_list(std::string* err) {
 // key order): stable LSD passes over a permutation, the length first, then the sort words of
 // the rows from the last to the first
 int SessionStore::name_order(std::string* err) {
+  int rc;
   const int32_t ns = n_list;
   if (ns < 2) return OTR_OK;
-  const unsigned g = ses_grid(ns, 256);
-  unsigned long long* key = buf<unsigned long long>(B_NS_KEY, ns);
-  unsigned long long* key2 = buf<unsigned long long>(B_NS_KEY2, ns);
-  int32_t* perm = buf<int32_t>(B_NS_PERM, ns);
-  int32_t* perm2 = buf<int32_t>(B_NS_PERM2, ns);
+  const unsigned g = grid_ceil1(ns, 256);
+  unsigned long long* key = get<unsigned long long>(B_NS_KEY, ns);
+  unsigned long long* key2 = get<unsigned long long>(B_NS_KEY2, ns);
+  int32_t* perm = get<int32_t>(B_NS_PERM, ns);
+  int32_t* perm2 = get<int32_t>(B_NS_PERM2, ns);
   int32_t* list = (int32_t*)b[B_L_SLOT2].p;
   unsigned long long* lkey = (unsigned long long*)b[B_L_KEY2].p;
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key, key2, perm, perm2, ns, 0, 64, stream));
-  void* tmp = buf<char>(B_TMP, tb);
+  Workspace tmp;  // one for every pass, sized before the first launch
+  if ((rc = sort_bytes(key, key2, perm, perm2, ns, 0, 64, &tmp.bytes, stream, err))) return rc;
+  tmp.p = get<char>(B_TMP, tmp.bytes);
   k_ses_iota<<<g, 256, 0, stream>>>(ns, perm);
   for (int32_t w = -1, pass = 0; pass <= name_sort_words(dir.uuid_bytes); ++pass) {
     k_ses_name_sort_key<<<g, 256, 0, stream>>>(ns, list, perm, dir, w, key);
-    size_t tb2 = tb;
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb2, key, key2, perm, perm2, ns, 0, w < 0 ? 9 : 64, stream));
+    if ((rc = sort_pairs(tmp, key, key2, perm, perm2, ns, 0, w < 0 ? 9 : 64, stream, err))) return rc;
     std::swap(perm, perm2);
     w = w < 0 ? name_sort_words(dir.uuid_bytes) - 1 : w - 1;
   }
@@ -754,13 +689,13 @@ int SessionStore::snapshot_list(otr_session_snapshot* out, std::string* err) {
   if (named() && (rc = names_list(err))) return rc;
   if (ns == 0) return OTR_OK;
   const int32_t* list = (const int32_t*)b[B_L_SLOT2].p;
-  int32_t* rep = buf<int32_t>(B_L_REP, ns);
-  int64_t* cnt_n = buf<int64_t>(B_L_N, ns);
+  int32_t* rep = get<int32_t>(B_L_REP, ns);
+  int64_t* cnt_n = get<int64_t>(B_L_N, ns);
   // (B_SUB_OFF, not the batch's offsets: an advance's empty batch stays what it is)
-  int64_t* off = buf<int64_t>(B_SUB_OFF, (size_t)ns + 1);
-  k_ses_evict_gate<<<ses_grid(ns, 256), 256, 0, stream>>>(ns, list, st, rep, cnt_n);
+  int64_t* off = get<int64_t>(B_SUB_OFF, (size_t)ns + 1);
+  k_ses_evict_gate<<<grid_ceil1(ns, 256), 256, 0, stream>>>(ns, list, st, rep, cnt_n);
   HIPCHK(hipMemsetAsync(off, 0, 8, stream));
-  if ((rc = scan64(cnt_n, off + 1, ns, err))) return rc;
+  if ((rc = scan(cnt_n, off + 1, ns, err))) return rc;
   const size_t ms = (size_t)cfg.max_sessions;
   s_key.resize(ns);
   s_slot.resize(ns);
@@ -773,10 +708,10 @@ int SessionStore::snapshot_list(otr_session_snapshot* out, std::string* err) {
   HIPCHK(hipMemcpyAsync(all_last.data(), st.last, 8 * ms, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
   const int64_t np = s_off[ns];
-  float* lat = buf<float>(B_S_LAT, np);
-  float* lon = buf<float>(B_S_LON, np);
-  int32_t* acc = buf<int32_t>(B_S_ACC, np);
-  int64_t* time = buf<int64_t>(B_G_TIME, np);
+  float* lat = get<float>(B_S_LAT, np);
+  float* lon = get<float>(B_S_LON, np);
+  int32_t* acc = get<int32_t>(B_S_ACC, np);
+  int64_t* time = get<int64_t>(B_G_TIME, np);
   k_ses_gather<true><<<(unsigned)ns, 64, 0, stream>>>(ns, list, off, st, nullptr, nullptr, time, nullptr, nullptr, 0,
                                                       lat, lon, acc);
   HIPCHK(hipGetLastError());
@@ -815,22 +750,20 @@ int SessionStore::restore(SesGiven g, const SesNamesIn* nm, otr_session_restore_
   out->n_live = live();
   if (n == 0) return OTR_OK;
   if (h_cnt[SES_DEAD] > 0 && live() + h_cnt[SES_DEAD] > cfg.max_sessions && (rc = rebuild(err))) return rc;
-  int32_t* entry = buf<int32_t>(B_ENTRY, n);
-  int32_t* fresh = buf<int32_t>(B_NEW, n);
-  unsigned long long* bad = buf<unsigned long long>(B_RS_BAD, 1);
+  int32_t* entry = get<int32_t>(B_ENTRY, n);
+  int32_t* fresh = get<int32_t>(B_NEW, n);
+  unsigned long long* bad = get<unsigned long long>(B_RS_BAD, 1);
   int32_t* first = spare.slot;  // scratch: the spare table is only used inside a rebuild
   HIPCHK(hipMemsetAsync(first, 0x7F, 4 * (size_t)spare.cap, stream));
   HIPCHK(hipMemsetAsync(bad, 0xFF, 8, stream));
   HIPCHK(hipMemsetAsync(cnt + SES_FLAGS, 0, 4, stream));
-  const unsigned grid = ses_grid(n, 256);
+  const unsigned grid = grid_ceil1(n, 256);
   k_ses_restore_check<REC><<<grid, 256, 0, stream>>>(tab, g, cfg.max_points, first, entry, fresh, bad, cnt);
   if (nm) k_ses_restore_name_check<<<grid, 256, 0, stream>>>(dir, *nm, n, bad);
   HIPCHK(hipGetLastError());
   unsigned long long h_bad = kSesNoBad;
   int32_t flags = 0;
-  HIPCHK(hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(&flags, cnt + SES_FLAGS, 4, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
+  if ((rc = read_back(stream, err, fetch(&h_bad, bad), fetch(&flags, cnt + SES_FLAGS)))) return rc;
   if (flags) {
     // more keys than the table has room for (a refusal either way): lanes that found no entry
     // could not see each other, so the occurrences of a key are counted here
@@ -883,6 +816,8 @@ int SessionStore::restore(SesGiven g, const SesNamesIn* nm, otr_session_restore_
 
 namespace {
 
+// the session calls' preconditions, then the shared guard (an allocation failure of the store's
+// pool or of the matcher's, which the rounds and the formatter reach into, ends here)
 template <class F>
 int guarded(Matcher& m, std::string* err, bool need_store, F&& f, bool keep_names = false) {
   if (need_store && !m.ses) {
@@ -890,16 +825,7 @@ int guarded(Matcher& m, std::string* err, bool need_store, F&& f, bool keep_name
     return OTR_BAD_REQUEST;
   }
   if (m.ses && !keep_names) m.ses->names_have = false;  // a listing's names last until the next session call
-  try {
-    return f();
-  } catch (const SesOom& o) {
-    if (m.stream) (void)hipStreamSynchronize(m.stream);
-    (void)hipGetLastError();
-    if (err)
-      *err = std::string("out of device memory: session buffer '") + o.name + "' needs " +
-             std::to_string((o.bytes >> 20) + 1) + " MiB";
-    return OTR_DEVICE_ERROR;
-  }
+  return otr::guarded(m.stream, err, f);
 }
 
 int bad(std::string* err, const char* what) {
@@ -969,7 +895,7 @@ int Matcher::sessions_advance(const otr_session_points* pts, const otr_session_n
     s.W = 0;
     if (s.chunk_open && (rc = s.round(err))) return rc;
     if (s.W == 0) {
-      int64_t* off = s.buf<int64_t>(B_G_OFF, 1);
+      int64_t* off = s.get<int64_t>(B_G_OFF, 1);
       HIPCHK(hipMemsetAsync(off, 0, 8, stream));
       HIPCHK(hipStreamSynchronize(stream));
     }
@@ -1047,19 +973,18 @@ int Matcher::sessions_punctuate(int64_t ts, otr_session_result* out, std::string
     const int32_t ne = s.n_list;
     if (ne > 0) {
       const int32_t* list = (const int32_t*)s.b[B_L_SLOT2].p;
-      int32_t* rep = s.buf<int32_t>(B_L_REP, ne);
-      int32_t* rep_incl = s.buf<int32_t>(B_L_REP_INCL, ne);
-      int64_t* cnt_n = s.buf<int64_t>(B_L_N, ne);
-      k_ses_evict_gate<<<ses_grid(ne, 256), 256, 0, stream>>>(ne, list, s.st, rep, cnt_n);
-      if ((rc = s.scan32(rep, rep_incl, ne, err))) return rc;
-      HIPCHK(hipMemcpyAsync(&s.W, rep_incl + (ne - 1), 4, hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
+      int32_t* rep = s.get<int32_t>(B_L_REP, ne);
+      int32_t* rep_incl = s.get<int32_t>(B_L_REP_INCL, ne);
+      int64_t* cnt_n = s.get<int64_t>(B_L_N, ne);
+      k_ses_evict_gate<<<grid_ceil1(ne, 256), 256, 0, stream>>>(ne, list, s.st, rep, cnt_n);
+      if ((rc = s.scan(rep, rep_incl, ne, err))) return rc;
+      if ((rc = read_back(stream, err, fetch(&s.W, rep_incl + (ne - 1))))) return rc;
       if (s.W > 0) {
-        int32_t* win_slot = s.buf<int32_t>(B_W_SLOT, s.W);
-        int64_t* win_trig = s.buf<int64_t>(B_W_TRIG, s.W);
-        int64_t* win_n = s.buf<int64_t>(B_W_N, s.W);
-        unsigned long long* win_key = s.buf<unsigned long long>(B_W_KEY, s.W);
-        k_ses_evict_windows<<<ses_grid(ne, 256), 256, 0, stream>>>(
+        int32_t* win_slot = s.get<int32_t>(B_W_SLOT, s.W);
+        int64_t* win_trig = s.get<int64_t>(B_W_TRIG, s.W);
+        int64_t* win_n = s.get<int64_t>(B_W_N, s.W);
+        unsigned long long* win_key = s.get<unsigned long long>(B_W_KEY, s.W);
+        k_ses_evict_windows<<<grid_ceil1(ne, 256), 256, 0, stream>>>(
             ne, list, (const unsigned long long*)s.b[B_L_KEY2].p, rep, rep_incl, cnt_n, win_slot, win_trig, win_n,
             win_key);
         if ((rc = s.gather(err))) return rc;
@@ -1071,7 +996,7 @@ int Matcher::sessions_punctuate(int64_t ts, otr_session_result* out, std::string
         }
         s.result_round();
       }
-      k_ses_clear<<<ses_grid(ne, 256), 256, 0, stream>>>(ne, list, s.st);
+      k_ses_clear<<<grid_ceil1(ne, 256), 256, 0, stream>>>(ne, list, s.st);
       if ((rc = s.release_list(list, ne, err))) return rc;
       s.r_evicted = ne;
     }
@@ -1137,14 +1062,14 @@ int Matcher::sessions_restore(const otr_session_snapshot* snap, const otr_sessio
       g.acc = snap->accuracy;
       g.time = snap->time;
     } else {
-      unsigned long long* key = s.buf<unsigned long long>(B_RS_KEY, n);
-      int64_t* off = s.buf<int64_t>(B_RS_OFF, (size_t)n + 1);
-      float* sep = s.buf<float>(B_RS_SEP, n);
-      int64_t* last = s.buf<int64_t>(B_RS_LAST, n);
-      float* lat = s.buf<float>(B_LAT, np);
-      float* lon = s.buf<float>(B_LON, np);
-      int32_t* acc = s.buf<int32_t>(B_ACC, np);
-      int64_t* time = s.buf<int64_t>(B_TIME, np);
+      unsigned long long* key = s.get<unsigned long long>(B_RS_KEY, n);
+      int64_t* off = s.get<int64_t>(B_RS_OFF, (size_t)n + 1);
+      float* sep = s.get<float>(B_RS_SEP, n);
+      int64_t* last = s.get<int64_t>(B_RS_LAST, n);
+      float* lat = s.get<float>(B_LAT, np);
+      float* lon = s.get<float>(B_LON, np);
+      int32_t* acc = s.get<int32_t>(B_ACC, np);
+      int64_t* time = s.get<int64_t>(B_TIME, np);
       HIPCHK(hipMemcpyAsync(key, snap->key, 8 * (size_t)n, hipMemcpyHostToDevice, stream));
       HIPCHK(hipMemcpyAsync(off, snap->point_off, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, stream));
       HIPCHK(hipMemcpyAsync(sep, snap->max_sep, 4 * (size_t)n, hipMemcpyHostToDevice, stream));
@@ -1199,9 +1124,9 @@ int Matcher::sessions_restore_records(const otr_session_records* recs, const otr
       g.off = recs->rec_off;
       g.bytes = recs->bytes;
     } else {
-      unsigned long long* key = s.buf<unsigned long long>(B_RS_KEY, n);
-      int64_t* off = s.buf<int64_t>(B_RS_OFF, (size_t)n + 1);
-      uint8_t* bytes = s.buf<uint8_t>(B_RS_BYTES, nb);
+      unsigned long long* key = s.get<unsigned long long>(B_RS_KEY, n);
+      int64_t* off = s.get<int64_t>(B_RS_OFF, (size_t)n + 1);
+      uint8_t* bytes = s.get<uint8_t>(B_RS_BYTES, nb);
       HIPCHK(hipMemcpyAsync(key, recs->key, 8 * (size_t)n, hipMemcpyHostToDevice, stream));
       HIPCHK(hipMemcpyAsync(off, recs->rec_off, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, stream));
       if (nb > 0) HIPCHK(hipMemcpyAsync(bytes, recs->bytes, (size_t)nb, hipMemcpyHostToDevice, stream));
@@ -1234,7 +1159,7 @@ int Matcher::sessions_export_records(otr_session_records* out, std::string* err)
     if ((rc = s.list_sessions(0, 0, err))) return rc;
     const int32_t ns = s.n_list;
     s.x_off.assign((size_t)ns + 1, 0);
-    int64_t* off = s.buf<int64_t>(B_X_OFF, (size_t)ns + 1);
+    int64_t* off = s.get<int64_t>(B_X_OFF, (size_t)ns + 1);
     HIPCHK(hipMemsetAsync(off, 0, 8, stream));
     out->rec_off = s.x_off.data();
     out->d_rec_off = off;
@@ -1244,15 +1169,15 @@ int Matcher::sessions_export_records(otr_session_records* out, std::string* err)
       return OTR_OK;
     }
     const int32_t* list = (const int32_t*)s.b[B_L_SLOT2].p;
-    int64_t* len = s.buf<int64_t>(B_X_LEN, ns);
-    k_ses_record_len<<<ses_grid(ns, 256), 256, 0, stream>>>(ns, list, s.st, len);
-    if ((rc = s.scan64(len, off + 1, ns, err))) return rc;
+    int64_t* len = s.get<int64_t>(B_X_LEN, ns);
+    k_ses_record_len<<<grid_ceil1(ns, 256), 256, 0, stream>>>(ns, list, s.st, len);
+    if ((rc = s.scan(len, off + 1, ns, err))) return rc;
     s.s_key.resize(ns);
     HIPCHK(hipMemcpyAsync(s.x_off.data(), off, 8 * ((size_t)ns + 1), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipMemcpyAsync(s.s_key.data(), s.b[B_L_KEY2].p, 8 * (size_t)ns, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     const int64_t nb = s.x_off[ns];
-    uint8_t* bytes = s.buf<uint8_t>(B_X_BYTES, nb);
+    uint8_t* bytes = s.get<uint8_t>(B_X_BYTES, nb);
     k_ses_encode<<<(unsigned)ns, 64, 0, stream>>>(ns, list, off, s.st, bytes);
     HIPCHK(hipGetLastError());
     s.x_bytes.resize((size_t)nb);
@@ -1276,13 +1201,13 @@ int Matcher::sessions_take(int n_parts, int part, int remove, otr_session_snapsh
     if (s.pending || s.chunk_open) return bad(err, "an advance / commit sequence is open");
     if (n_parts < 1 || part < 0 || part >= n_parts) return bad(err, "part out of range");
     const int32_t ms = s.cfg.max_sessions;
-    int32_t* flag = s.buf<int32_t>(B_FLAG, ms);
-    k_ses_flag_part<<<ses_grid(ms, 256), 256, 0, stream>>>(s.st, (uint32_t)n_parts, (uint32_t)part, flag);
+    int32_t* flag = s.get<int32_t>(B_FLAG, ms);
+    k_ses_flag_part<<<grid_ceil1(ms, 256), 256, 0, stream>>>(s.st, (uint32_t)n_parts, (uint32_t)part, flag);
     if ((rc = s.list_flagged(err))) return rc;
     if ((rc = s.snapshot_list(out, err))) return rc;
     if (remove && s.n_list > 0) {  // deleted as an eviction deletes, without a report
       const int32_t* list = (const int32_t*)s.b[B_L_SLOT2].p;
-      k_ses_clear<<<ses_grid(s.n_list, 256), 256, 0, stream>>>(s.n_list, list, s.st);
+      k_ses_clear<<<grid_ceil1(s.n_list, 256), 256, 0, stream>>>(s.n_list, list, s.st);
       if ((rc = s.release_list(list, s.n_list, err))) return rc;
     }
     return OTR_OK;

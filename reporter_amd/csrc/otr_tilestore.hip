@@ -4,39 +4,23 @@
 // otr_tiletext.h): lengths, scans, one emit pass, and of the store's snapshot, restore and
 // changelog records (K20, otr_tile_records.h).  include/otr.h otr_tile_store_* and
 // otr_tiles_text for the rules.
-#include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
+#include "otr_devscan.h"
 #include "otr_engine.h"
 #include "otr_tilestore.h"
 #include "otr_tiletext.h"
 #include "otr_tile_records.h"
 
-#define HIPCHK(x)                                                                        \
-  do {                                                                                   \
-    hipError_t e_ = (x);                                                                 \
-    if (e_ != hipSuccess) {                                                              \
-      if (err) *err = std::string("HIP error: ") + hipGetErrorString(e_) + " at " #x;    \
-      return OTR_DEVICE_ERROR;                                                           \
-    }                                                                                    \
-  } while (0)
-
 namespace otr {
 
 namespace {
 
-struct TstOom {
-  const char* name;
-  size_t bytes;
-};
-
-unsigned tst_grid(int64_t n, int threads) { return (unsigned)std::max<int64_t>(1, (n + threads - 1) / threads); }
+DeviceOom tst_oom(const char* name, size_t bytes) { return DeviceOom{PoolOwner::tile_store, name, -1, bytes}; }
 
 constexpr int64_t kTstMaxRows = (int64_t)1 << 27;
 
@@ -74,35 +58,16 @@ const char* const kTstName[T_NUM] = {
 
 }  // namespace
 
-// the growable buffers, the stream they are used on and a pair of events
-struct TstBufs {
+// the growable buffers (the pool's slots, by TstBuf), the stream they are used on and a pair
+// of events
+struct TstBufs : DevPool {
+  TstBufs() : DevPool(PoolOwner::tile_store, kTstName, T_NUM) {}
   hipStream_t stream = nullptr;
   hipEvent_t ev[2];
   bool ev_init = false;
-  struct {
-    void* p = nullptr;
-    size_t bytes = 0;
-  } b[T_NUM];
-
-  template <class T>
-  T* buf(int slot, size_t n) {
-    const size_t bytes = (n ? n : 1) * sizeof(T);
-    if (b[slot].bytes < bytes) {
-      if (b[slot].p) (void)hipFree(b[slot].p);
-      b[slot].p = nullptr;
-      b[slot].bytes = 0;
-      const size_t nb = bytes + bytes / 4;
-      if (hipMalloc(&b[slot].p, nb) != hipSuccess) {
-        (void)hipGetLastError();
-        b[slot].p = nullptr;
-        throw TstOom{kTstName[slot], nb};
-      }
-      b[slot].bytes = nb;
-    }
-    return (T*)b[slot].p;
+  int scan64(const int64_t* in, int64_t* out, int64_t n, std::string* err) {
+    return pool_scan(*this, T_TMP, in, out, n, stream, err);
   }
-
-  int scan64(const int64_t* in, int64_t* out, int64_t n, std::string* err);
   int events(std::string* err) {
     if (ev_init) return OTR_OK;
     for (auto& e : ev) HIPCHK(hipEventCreate(&e));
@@ -112,8 +77,7 @@ struct TstBufs {
   int finish(float* device_ms, std::string* err);
   void release() {
     if (stream) (void)hipStreamSynchronize(stream);
-    for (auto& x : b)
-      if (x.p) (void)hipFree(x.p);
+    DevPool::release();
     if (ev_init)
       for (auto& e : ev) (void)hipEventDestroy(e);
   }
@@ -185,31 +149,23 @@ void tile_store_destroy(TileStore* s) {
   delete s;
 }
 
-int TstBufs::scan64(const int64_t* in, int64_t* out, int64_t n, std::string* err) {
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, in, out, (int)n, stream));
-  void* tmp = buf<char>(T_TMP, tb);
-  HIPCHK(hipcub::DeviceScan::InclusiveSum(tmp, tb, in, out, (int)n, stream));
-  return OTR_OK;
-}
-
 int TileStore::alloc(std::string* err) {
   const size_t bytes = sizeof(otr_tile_row) * (size_t)cfg.max_rows;
   if (hipMalloc((void**)&rows, bytes) != hipSuccess) {
     (void)hipGetLastError();
     rows = nullptr;
-    throw TstOom{"tile store rows", bytes};
+    throw tst_oom("tile store rows", bytes);
   }
   if (hipMalloc((void**)&counters, 8 * TST_WORDS) != hipSuccess) {
     (void)hipGetLastError();
     counters = nullptr;
-    throw TstOom{"tile store counters", 8 * TST_WORDS};
+    throw tst_oom("tile store counters", 8 * TST_WORDS);
   }
   if (timed()) {
     const size_t tb = sizeof(double) * (size_t)cfg.max_rows;
     if (hipMalloc((void**)&t0, tb) != hipSuccess || hipMalloc((void**)&t1, tb) != hipSuccess) {
       (void)hipGetLastError();
-      throw TstOom{"tile store times", 2 * tb};
+      throw tst_oom("tile store times", 2 * tb);
     }
   }
   return events(err);
@@ -238,14 +194,14 @@ int TileStore::add(const StoreArgs& in, int64_t n_reports, otr_tile_add_result* 
   const int64_t W = in.n_windows;
   StoreArgs a = in;
   a.quantisation = cfg.quantisation;
-  a.row_cnt = buf<int64_t>(T_CNT, W);
-  int64_t* off = buf<int64_t>(T_ROW_OFF, (size_t)W + 1);
+  a.row_cnt = get<int64_t>(T_CNT, W);
+  int64_t* off = get<int64_t>(T_ROW_OFF, (size_t)W + 1);
   a.counters = counters;
   a.row_off = off;
   a.rows = rows + n_rows;
   a.row_t0 = timed() ? t0 + n_rows : nullptr;
   a.row_t1 = timed() ? t1 + n_rows : nullptr;
-  const unsigned blocks = tst_grid(W, kStoreWaves);
+  const unsigned blocks = grid_ceil1(W, kStoreWaves);
   HIPCHK(hipMemsetAsync(counters, 0, 8 * TST_WORDS, stream));
   HIPCHK(hipMemsetAsync(off, 0, 8, stream));
   k_store_rows<false><<<blocks, 256, 0, stream>>>(a);
@@ -292,19 +248,12 @@ int bad(std::string* err, const std::string& what) {
   return OTR_BAD_REQUEST;
 }
 
+// the tile store calls' precondition, then the shared guard (an allocation failure of the
+// store's pool or of the matcher's, which the flush reaches into, ends here)
 template <class F>
 int guarded(Matcher& m, std::string* err, bool need_store, F&& f) {
   if (need_store && !m.tst) return bad(err, "no tile store: call otr_tile_store_open first");
-  try {
-    return f();
-  } catch (const TstOom& o) {
-    if (m.stream) (void)hipStreamSynchronize(m.stream);
-    (void)hipGetLastError();
-    if (err)
-      *err = std::string("out of device memory: tile store buffer '") + o.name + "' needs " +
-             std::to_string((o.bytes >> 20) + 1) + " MiB";
-    return OTR_DEVICE_ERROR;
-  }
+  return otr::guarded(m.stream, err, f);
 }
 
 }  // namespace
@@ -355,15 +304,12 @@ int Matcher::tile_store_add_session(otr_tile_add_result* out, std::string* err) 
     }
     HIPCHK(hipEventRecord(s.ev[0], stream));
     // the forward order: a stable sort of the windows by trigger (an eviction's by rank)
-    unsigned long long* key_a = s.buf<unsigned long long>(T_KEY_A, W);
-    unsigned long long* key_b = s.buf<unsigned long long>(T_KEY_B, W);
-    int32_t* idx_a = s.buf<int32_t>(T_IDX_A, W);
-    int32_t* idx_b = s.buf<int32_t>(T_IDX_B, W);
-    k_store_order_key<<<tst_grid(W, 256), 256, 0, stream>>>(sr.trigger, W, key_a, idx_a);
-    size_t tb = 0;
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key_a, key_b, idx_a, idx_b, (int)W, 0, 64, stream));
-    void* tmp = s.buf<char>(T_TMP, tb);
-    HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key_a, key_b, idx_a, idx_b, (int)W, 0, 64, stream));
+    unsigned long long* key_a = s.get<unsigned long long>(T_KEY_A, W);
+    unsigned long long* key_b = s.get<unsigned long long>(T_KEY_B, W);
+    int32_t* idx_a = s.get<int32_t>(T_IDX_A, W);
+    int32_t* idx_b = s.get<int32_t>(T_IDX_B, W);
+    k_store_order_key<<<grid_ceil1(W, 256), 256, 0, stream>>>(sr.trigger, W, key_a, idx_a);
+    if ((rc = s.sort_pairs(key_a, key_b, idx_a, idx_b, W, err))) return rc;
     StoreArgs a{};
     a.n_windows = W;
     a.order = idx_b;
@@ -416,13 +362,13 @@ int Matcher::tile_store_add_reports(int64_t n_windows, const int64_t* rep_off, c
       n_reports = rep_off[W];
       if (n_reports > 0 && (!id || !next_id || !t0 || !t1 || !length || !queue_length)) return bad(err, "null argument");
       const size_t nr = (size_t)n_reports;
-      int64_t* d_off = s.buf<int64_t>(T_OFF, (size_t)W + 1);
-      unsigned long long* d_id = s.buf<unsigned long long>(T_ID, nr);
-      unsigned long long* d_next = s.buf<unsigned long long>(T_NEXT, nr);
-      double* d_t0 = s.buf<double>(T_T0, nr);
-      double* d_t1 = s.buf<double>(T_T1, nr);
-      int32_t* d_len = s.buf<int32_t>(T_LEN, nr);
-      int32_t* d_queue = s.buf<int32_t>(T_QUEUE, nr);
+      int64_t* d_off = s.get<int64_t>(T_OFF, (size_t)W + 1);
+      unsigned long long* d_id = s.get<unsigned long long>(T_ID, nr);
+      unsigned long long* d_next = s.get<unsigned long long>(T_NEXT, nr);
+      double* d_t0 = s.get<double>(T_T0, nr);
+      double* d_t1 = s.get<double>(T_T1, nr);
+      int32_t* d_len = s.get<int32_t>(T_LEN, nr);
+      int32_t* d_queue = s.get<int32_t>(T_QUEUE, nr);
       HIPCHK(hipEventRecord(s.ev[0], stream));
       HIPCHK(hipMemcpyAsync(d_off, rep_off, 8 * ((size_t)W + 1), hipMemcpyHostToDevice, stream));
       if (nr) {
@@ -487,7 +433,7 @@ int TileStore::flush(Matcher& m, TileText* text, int flags, otr_tile_flush_resul
   s.h_file.clear();
   s.h_unclean.clear();
   s.h_row_off.assign(1, 0);
-  int64_t* d_row_off = s.buf<int64_t>(T_F_ROW_OFF, 1);
+  int64_t* d_row_off = s.get<int64_t>(T_F_ROW_OFF, 1);
   out->row_off = s.h_row_off.data();
   if (n == 0) {
     HIPCHK(hipMemsetAsync(d_row_off, 0, 8, stream));
@@ -501,35 +447,33 @@ int TileStore::flush(Matcher& m, TileText* text, int flags, otr_tile_flush_resul
   CulledRows c;
   if ((rc = m.cull_device(s.rows, n, s.cfg.privacy, OTR_TILE_RULES_STREAM, &c, err))) return rc;
   // the files of the sorted rows, and which of them kept rows
-  const unsigned g = tst_grid(n, 256);
-  int64_t* head = s.buf<int64_t>(T_F_HEAD, n);
-  int64_t* head_incl = s.buf<int64_t>(T_F_INCL, n);
+  const unsigned g = grid_ceil1(n, 256);
+  int64_t* head = s.get<int64_t>(T_F_HEAD, n);
+  int64_t* head_incl = s.get<int64_t>(T_F_INCL, n);
   k_store_file_heads<<<g, 256, 0, stream>>>(c.sorted, n, head);
   if ((rc = s.scan64(head, head_incl, n, err))) return rc;
   int64_t nf = 0;
-  HIPCHK(hipMemcpyAsync(&nf, head_incl + (n - 1), 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
+  if ((rc = read_back(stream, err, fetch(&nf, head_incl + (n - 1))))) return rc;
   if (nf < 1 || nf > n) {
     if (err) *err = "tile store file split failed";
     return OTR_DEVICE_ERROR;
   }
-  int64_t* start = s.buf<int64_t>(T_F_START, nf);
-  int64_t* listed = s.buf<int64_t>(T_F_LISTED, nf);
-  int64_t* listed_incl = s.buf<int64_t>(T_F_LINCL, nf);
+  int64_t* start = s.get<int64_t>(T_F_START, nf);
+  int64_t* listed = s.get<int64_t>(T_F_LISTED, nf);
+  int64_t* listed_incl = s.get<int64_t>(T_F_LINCL, nf);
   k_store_file_starts<<<g, 256, 0, stream>>>(head, head_incl, n, start);
-  const unsigned gf = tst_grid(nf, 256);
+  const unsigned gf = grid_ceil1(nf, 256);
   k_store_file_listed<<<gf, 256, 0, stream>>>(start, nf, n, c.kept_incl, listed);
   if ((rc = s.scan64(listed, listed_incl, nf, err))) return rc;
   int64_t nl = 0;
-  HIPCHK(hipMemcpyAsync(&nl, listed_incl + (nf - 1), 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
+  if ((rc = read_back(stream, err, fetch(&nl, listed_incl + (nf - 1))))) return rc;
   if (nl < 0 || nl > nf || nl > c.n_kept || (nl == 0) != (c.n_kept == 0)) {
     if (err) *err = "tile store file table failed";
     return OTR_DEVICE_ERROR;
   }
-  unsigned long long* d_file = s.buf<unsigned long long>(T_F_FILE, nl);
-  d_row_off = s.buf<int64_t>(T_F_ROW_OFF, (size_t)nl + 1);
-  int64_t* d_unclean = s.buf<int64_t>(T_F_UNCLEAN, nl);
+  unsigned long long* d_file = s.get<unsigned long long>(T_F_FILE, nl);
+  d_row_off = s.get<int64_t>(T_F_ROW_OFF, (size_t)nl + 1);
+  int64_t* d_unclean = s.get<int64_t>(T_F_UNCLEAN, nl);
   k_store_file_table<<<gf, 256, 0, stream>>>(c.sorted, start, nf, n, c.kept_incl, listed, listed_incl, d_file,
                                              d_row_off, d_unclean);
   HIPCHK(hipGetLastError());
@@ -580,23 +524,22 @@ int Matcher::tile_store_flush(otr_tile_flush_result* out, std::string* err) {
 int TileText::table(const otr_tile_row* d_rows, int64_t n, const unsigned long long** d_file,
                     const int64_t** d_row_off, int64_t* n_files, std::string* err) {
   int rc;
-  const unsigned g = tst_grid(n, 256);
-  int64_t* head = buf<int64_t>(T_F_HEAD, n);
-  int64_t* head_incl = buf<int64_t>(T_F_INCL, n);
+  const unsigned g = grid_ceil1(n, 256);
+  int64_t* head = get<int64_t>(T_F_HEAD, n);
+  int64_t* head_incl = get<int64_t>(T_F_INCL, n);
   k_store_file_heads<<<g, 256, 0, stream>>>(d_rows, n, head);
   if ((rc = scan64(head, head_incl, n, err))) return rc;
   int64_t nf = 0;
-  HIPCHK(hipMemcpyAsync(&nf, head_incl + (n - 1), 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
+  if ((rc = read_back(stream, err, fetch(&nf, head_incl + (n - 1))))) return rc;
   if (nf < 1 || nf > n || nf >= (int64_t)INT32_MAX) {
     if (err) *err = "tile text file split failed";
     return OTR_DEVICE_ERROR;
   }
-  int64_t* start = buf<int64_t>(T_F_START, nf);
-  unsigned long long* file = buf<unsigned long long>(T_F_FILE, nf);
-  int64_t* row_off = buf<int64_t>(T_F_ROW_OFF, (size_t)nf + 1);
+  int64_t* start = get<int64_t>(T_F_START, nf);
+  unsigned long long* file = get<unsigned long long>(T_F_FILE, nf);
+  int64_t* row_off = get<int64_t>(T_F_ROW_OFF, (size_t)nf + 1);
   k_store_file_starts<<<g, 256, 0, stream>>>(head, head_incl, n, start);
-  k_tile_text_table<<<tst_grid(nf + 1, 256), 256, 0, stream>>>(d_rows, start, nf, n, file, row_off);
+  k_tile_text_table<<<grid_ceil1(nf + 1, 256), 256, 0, stream>>>(d_rows, start, nf, n, file, row_off);
   HIPCHK(hipGetLastError());
   *d_file = file;
   *d_row_off = row_off;
@@ -616,26 +559,24 @@ int TileText::write(const otr_tile_row* d_rows, int64_t n, const unsigned long l
   HIPCHK(hipEventRecord(ev[0], stream));
   const int64_t nf = n_files;
   const int32_t tag_len = (int32_t)h_tag.size();
-  int64_t* off = buf<int64_t>(T_X_OFF, (size_t)n + 1);
-  int64_t* text_off = buf<int64_t>(T_X_TEXT_OFF, (size_t)nf + 1);
-  int64_t* name_off = buf<int64_t>(T_X_NAME_OFF, (size_t)nf + 1);
-  uint8_t* tag = buf<uint8_t>(T_X_TAG, kTileTextTagMax);
+  int64_t* off = get<int64_t>(T_X_OFF, (size_t)n + 1);
+  int64_t* text_off = get<int64_t>(T_X_TEXT_OFF, (size_t)nf + 1);
+  int64_t* name_off = get<int64_t>(T_X_NAME_OFF, (size_t)nf + 1);
+  uint8_t* tag = get<uint8_t>(T_X_TAG, kTileTextTagMax);
   HIPCHK(hipMemsetAsync(off, 0, 8, stream));
   HIPCHK(hipMemsetAsync(text_off, 0, 8, stream));
   HIPCHK(hipMemsetAsync(name_off, 0, 8, stream));
   int64_t total[2] = {0, 0};  // text bytes, name bytes
   if (n > 0) {
-    int64_t* len = buf<int64_t>(T_X_LEN, n);
-    int64_t* name_len = buf<int64_t>(T_X_NAME_LEN, nf);
+    int64_t* len = get<int64_t>(T_X_LEN, n);
+    int64_t* name_len = get<int64_t>(T_X_NAME_LEN, nf);
     HIPCHK(hipMemcpyAsync(tag, h_tag.data(), (size_t)tag_len, hipMemcpyHostToDevice, stream));
-    k_tile_text_len<<<tst_grid(n, 256), 256, 0, stream>>>(d_rows, n, rules, tag_len, len);
+    k_tile_text_len<<<grid_ceil1(n, 256), 256, 0, stream>>>(d_rows, n, rules, tag_len, len);
     if ((rc = scan64(len, off + 1, n, err))) return rc;
-    k_tile_text_files<<<tst_grid(nf + 1, 256), 256, 0, stream>>>(d_file, d_row_off, off, nf, quantisation, text_off,
-                                                                 name_len);
+    k_tile_text_files<<<grid_ceil1(nf + 1, 256), 256, 0, stream>>>(d_file, d_row_off, off, nf, quantisation, text_off,
+                                                                   name_len);
     if ((rc = scan64(name_len, name_off + 1, nf, err))) return rc;
-    HIPCHK(hipMemcpyAsync(&total[0], off + n, 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(&total[1], name_off + nf, 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
+    if ((rc = read_back(stream, err, fetch(&total[0], off + n), fetch(&total[1], name_off + nf)))) return rc;
     // (a row is at least 17 bytes and at most 122 + the tag, a name 8 to 20 + 1 + 20 + 1 + 1 + 1 + 7)
     if (total[0] < 17 * n || total[0] > n * (int64_t)(122 + kTileTextTagMax + kTileTextHeader + 1) || total[1] < 8 * nf ||
         total[1] > 51 * nf) {
@@ -643,11 +584,11 @@ int TileText::write(const otr_tile_row* d_rows, int64_t n, const unsigned long l
       return OTR_DEVICE_ERROR;
     }
   }
-  uint8_t* text = buf<uint8_t>(T_X_TEXT, (size_t)total[0]);
-  uint8_t* names = buf<uint8_t>(T_X_NAMES, (size_t)total[1]);
+  uint8_t* text = get<uint8_t>(T_X_TEXT, (size_t)total[0]);
+  uint8_t* names = get<uint8_t>(T_X_NAMES, (size_t)total[1]);
   if (n > 0) {
-    k_tile_text_emit<<<tst_grid(n, kTtRows), kTtRows, kTtLds, stream>>>(d_rows, n, rules, tag, tag_len, off, text);
-    k_tile_text_names<<<tst_grid(nf, 256), 256, 0, stream>>>(d_file, name_off, nf, quantisation, names);
+    k_tile_text_emit<<<grid_ceil1(n, kTtRows), kTtRows, kTtLds, stream>>>(d_rows, n, rules, tag, tag_len, off, text);
+    k_tile_text_names<<<grid_ceil1(nf, 256), 256, 0, stream>>>(d_file, name_off, nf, quantisation, names);
     HIPCHK(hipGetLastError());
   }
   const bool host = !(flags & OTR_TILE_TEXT_NO_HOST);
@@ -733,11 +674,11 @@ int Matcher::tiles_text(const otr_tile_row* rows, int64_t n, int memory, int qua
     t.h_tag = tag;
     const otr_tile_row* d_rows = rows;
     const unsigned long long* d_file = nullptr;
-    const int64_t* d_row_off = t.buf<int64_t>(T_F_ROW_OFF, 1);
+    const int64_t* d_row_off = t.get<int64_t>(T_F_ROW_OFF, 1);
     int64_t nf = 0;
     if (n > 0) {
       if (memory != OTR_MEM_DEVICE) {
-        otr_tile_row* d = t.buf<otr_tile_row>(T_X_ROWS, n);
+        otr_tile_row* d = t.get<otr_tile_row>(T_X_ROWS, n);
         HIPCHK(hipMemcpyAsync(d, rows, sizeof(otr_tile_row) * (size_t)n, hipMemcpyHostToDevice, stream));
         d_rows = d;
       }
@@ -780,11 +721,7 @@ const char* const kTileRestoreReason[] = {"",      "layout", "key",  "count", "s
 
 int TileStore::sort_pairs(const unsigned long long* k_in, unsigned long long* k_out, const int32_t* v_in,
                           int32_t* v_out, int64_t n, std::string* err) {
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k_in, k_out, v_in, v_out, (int)n, 0, 64, stream));
-  void* tmp = buf<char>(T_TMP, tb);
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, k_in, k_out, v_in, v_out, (int)n, 0, 64, stream));
-  return OTR_OK;
+  return pool_sort(*this, T_TMP, k_in, k_out, v_in, v_out, n, 0, 64, stream, err);
 }
 
 int TileStore::snapshot(int sflags, otr_tile_snapshot* out, std::string* err) {
@@ -795,7 +732,7 @@ int TileStore::snapshot(int sflags, otr_tile_snapshot* out, std::string* err) {
   out->n_rows = n_rows;
   if (n == 0) return OTR_OK;
   const bool host = !(sflags & OTR_TILE_SNAPSHOT_NO_HOST);
-  otr_tile_row* d_rows = buf<otr_tile_row>(T_S_ROWS, n);
+  otr_tile_row* d_rows = get<otr_tile_row>(T_S_ROWS, n);
   HIPCHK(hipMemcpyAsync(d_rows, rows, sizeof(otr_tile_row) * n, hipMemcpyDeviceToDevice, stream));
   out->d_rows = d_rows;
   if (host) {
@@ -804,8 +741,8 @@ int TileStore::snapshot(int sflags, otr_tile_snapshot* out, std::string* err) {
     out->rows = h_snap_rows.data();
   }
   if (timed()) {
-    double* d_t0 = buf<double>(T_S_T0, n);
-    double* d_t1 = buf<double>(T_S_T1, n);
+    double* d_t0 = get<double>(T_S_T0, n);
+    double* d_t1 = get<double>(T_S_T1, n);
     HIPCHK(hipMemcpyAsync(d_t0, t0, 8 * n, hipMemcpyDeviceToDevice, stream));
     HIPCHK(hipMemcpyAsync(d_t1, t1, 8 * n, hipMemcpyDeviceToDevice, stream));
     out->d_t0 = d_t0;
@@ -837,9 +774,9 @@ int TileStore::restore(const otr_tile_snapshot* snap, int memory, otr_tile_resto
   const double *d_t0 = snap->t0, *d_t1 = snap->t1;
   if (timed()) {
     if (memory != OTR_MEM_DEVICE) {  // staged: nothing reaches the store before the check has passed
-      otr_tile_row* r = buf<otr_tile_row>(T_S_ROWS, n);
-      double* a = buf<double>(T_S_T0, n);
-      double* b = buf<double>(T_S_T1, n);
+      otr_tile_row* r = get<otr_tile_row>(T_S_ROWS, n);
+      double* a = get<double>(T_S_T0, n);
+      double* b = get<double>(T_S_T1, n);
       HIPCHK(hipMemcpyAsync(r, snap->rows, sizeof(otr_tile_row) * (size_t)n, hipMemcpyHostToDevice, stream));
       HIPCHK(hipMemcpyAsync(a, snap->t0, 8 * (size_t)n, hipMemcpyHostToDevice, stream));
       HIPCHK(hipMemcpyAsync(b, snap->t1, 8 * (size_t)n, hipMemcpyHostToDevice, stream));
@@ -847,13 +784,12 @@ int TileStore::restore(const otr_tile_snapshot* snap, int memory, otr_tile_resto
       d_t0 = a;
       d_t1 = b;
     }
-    unsigned long long* verdict = buf<unsigned long long>(T_S_VERDICT, 1);
+    unsigned long long* verdict = get<unsigned long long>(T_S_VERDICT, 1);
     unsigned long long h_verdict = 0;
     HIPCHK(hipMemsetAsync(verdict, 0xFF, 8, stream));
-    k_tilerec_check_rows<<<tst_grid(n, 256), 256, 0, stream>>>(d_rows, d_t0, d_t1, n, cfg.quantisation, verdict);
+    k_tilerec_check_rows<<<grid_ceil1(n, 256), 256, 0, stream>>>(d_rows, d_t0, d_t1, n, cfg.quantisation, verdict);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&h_verdict, verdict, 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
+    if ((rc = read_back(stream, err, fetch(&h_verdict, verdict)))) return rc;
     if (h_verdict != kTileRecNone) {
       out->bad_slice = (int64_t)h_verdict;
       out->bad_reason = OTR_TILE_RESTORE_E_ROW;
@@ -889,72 +825,68 @@ int TileStore::export_records(int32_t slice_size, otr_tile_records* out, std::st
   out->slice_size = slice_size;
   out->memory = OTR_MEM_HOST;
   HIPCHK(hipEventRecord(ev[0], stream));
-  int64_t* rec_off = buf<int64_t>(T_E_REC_OFF, 1);
-  int64_t* name_off = buf<int64_t>(T_E_NAME_OFF, 1);
+  int64_t* rec_off = get<int64_t>(T_E_REC_OFF, 1);
+  int64_t* name_off = get<int64_t>(T_E_NAME_OFF, 1);
   int64_t nf = 0, ns = 0, total[2] = {0, 0};
   int64_t *start = nullptr, *tile = nullptr;
   int32_t* slice = nullptr;
   uint32_t* map_words = nullptr;
   if (n > 0) {
-    const unsigned g = tst_grid(n, 256);
-    unsigned long long* key_a = buf<unsigned long long>(T_KEY_A, n);
-    unsigned long long* key_b = buf<unsigned long long>(T_KEY_B, n);
-    int32_t* idx_a = buf<int32_t>(T_IDX_A, n);
-    int32_t* idx_b = buf<int32_t>(T_IDX_B, n);
+    const unsigned g = grid_ceil1(n, 256);
+    unsigned long long* key_a = get<unsigned long long>(T_KEY_A, n);
+    unsigned long long* key_b = get<unsigned long long>(T_KEY_B, n);
+    int32_t* idx_a = get<int32_t>(T_IDX_A, n);
+    int32_t* idx_b = get<int32_t>(T_IDX_B, n);
     // arrival order within a file: a stable sort by `file` alone
     k_tilerec_keys<<<g, 256, 0, stream>>>(rows, n, key_a, idx_a);
     if ((rc = sort_pairs(key_a, key_b, idx_a, idx_b, n, err))) return rc;
-    int64_t* head = buf<int64_t>(T_F_HEAD, n);
-    int64_t* head_incl = buf<int64_t>(T_F_INCL, n);
+    int64_t* head = get<int64_t>(T_F_HEAD, n);
+    int64_t* head_incl = get<int64_t>(T_F_INCL, n);
     k_tilerec_heads<<<g, 256, 0, stream>>>(key_b, n, head);
     if ((rc = scan64(head, head_incl, n, err))) return rc;
-    HIPCHK(hipMemcpyAsync(&nf, head_incl + (n - 1), 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
+    if ((rc = read_back(stream, err, fetch(&nf, head_incl + (n - 1))))) return rc;
     if (nf < 1 || nf > n) {
       if (err) *err = "tile export file split failed";
       return OTR_DEVICE_ERROR;
     }
-    int64_t* fstart = buf<int64_t>(T_F_START, nf);
-    int64_t* shead = buf<int64_t>(T_E_SHEAD, n);
-    int64_t* shead_incl = buf<int64_t>(T_E_SINCL, n);
+    int64_t* fstart = get<int64_t>(T_F_START, nf);
+    int64_t* shead = get<int64_t>(T_E_SHEAD, n);
+    int64_t* shead_incl = get<int64_t>(T_E_SINCL, n);
     k_store_file_starts<<<g, 256, 0, stream>>>(head, head_incl, n, fstart);
     k_tilerec_slice_heads<<<g, 256, 0, stream>>>(head_incl, fstart, n, S, shead);
     if ((rc = scan64(shead, shead_incl, n, err))) return rc;
-    HIPCHK(hipMemcpyAsync(&ns, shead_incl + (n - 1), 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
+    if ((rc = read_back(stream, err, fetch(&ns, shead_incl + (n - 1))))) return rc;
     if (ns < nf || ns > n) {
       if (err) *err = "tile export slice split failed";
       return OTR_DEVICE_ERROR;
     }
-    int64_t* pos = buf<int64_t>(T_E_POS, (size_t)ns + 1);
-    start = buf<int64_t>(T_E_START, ns);
-    tile = buf<int64_t>(T_E_TILE, ns);
-    slice = buf<int32_t>(T_E_SLICE, ns);
-    map_words = buf<uint32_t>(T_E_MAP, 5 * (size_t)nf);
-    int64_t* rec_len = buf<int64_t>(T_E_REC_LEN, ns);
-    int64_t* name_len = buf<int64_t>(T_E_NAME_LEN, ns);
-    rec_off = buf<int64_t>(T_E_REC_OFF, (size_t)ns + 1);
-    name_off = buf<int64_t>(T_E_NAME_OFF, (size_t)ns + 1);
+    int64_t* pos = get<int64_t>(T_E_POS, (size_t)ns + 1);
+    start = get<int64_t>(T_E_START, ns);
+    tile = get<int64_t>(T_E_TILE, ns);
+    slice = get<int32_t>(T_E_SLICE, ns);
+    map_words = get<uint32_t>(T_E_MAP, 5 * (size_t)nf);
+    int64_t* rec_len = get<int64_t>(T_E_REC_LEN, ns);
+    int64_t* name_len = get<int64_t>(T_E_NAME_LEN, ns);
+    rec_off = get<int64_t>(T_E_REC_OFF, (size_t)ns + 1);
+    name_off = get<int64_t>(T_E_NAME_OFF, (size_t)ns + 1);
     k_tilerec_table<<<g, 256, 0, stream>>>(key_b, head, head_incl, fstart, nf, shead, shead_incl, n, ns, S, q, pos,
                                            start, tile, slice, map_words);
-    k_tilerec_lens<<<tst_grid(ns, 256), 256, 0, stream>>>(pos, start, tile, slice, ns, rec_len, name_len);
+    k_tilerec_lens<<<grid_ceil1(ns, 256), 256, 0, stream>>>(pos, start, tile, slice, ns, rec_len, name_len);
     HIPCHK(hipMemsetAsync(rec_off, 0, 8, stream));
     HIPCHK(hipMemsetAsync(name_off, 0, 8, stream));
     if ((rc = scan64(rec_len, rec_off + 1, ns, err))) return rc;
     if ((rc = scan64(name_len, name_off + 1, ns, err))) return rc;
-    HIPCHK(hipMemcpyAsync(&total[0], rec_off + ns, 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(&total[1], name_off + ns, 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
+    if ((rc = read_back(stream, err, fetch(&total[0], rec_off + ns), fetch(&total[1], name_off + ns)))) return rc;
     if (total[0] != kTileRecHeader * ns + kTileRecSegment * n || total[1] < 5 * ns || total[1] > kTileKeyMax * ns) {
       if (err) *err = "tile export lengths failed";
       return OTR_DEVICE_ERROR;
     }
-    uint8_t* bytes = buf<uint8_t>(T_E_BYTES, (size_t)total[0]);
-    uint8_t* names = buf<uint8_t>(T_E_NAMES, (size_t)total[1]);
+    uint8_t* bytes = get<uint8_t>(T_E_BYTES, (size_t)total[0]);
+    uint8_t* names = get<uint8_t>(T_E_NAMES, (size_t)total[1]);
     const int64_t n_words = total[0] / 4;
-    k_tilerec_emit<<<tst_grid(n_words, kTileRecEmit), kTileRecEmit, 0, stream>>>(rows, t0, t1, idx_b, pos, rec_off, ns,
-                                                                                 n_words, (uint32_t*)bytes);
-    k_tilerec_names<<<tst_grid(ns, 256), 256, 0, stream>>>(start, tile, slice, name_off, ns, names);
+    k_tilerec_emit<<<grid_ceil1(n_words, kTileRecEmit), kTileRecEmit, 0, stream>>>(rows, t0, t1, idx_b, pos, rec_off,
+                                                                                   ns, n_words, (uint32_t*)bytes);
+    k_tilerec_names<<<grid_ceil1(ns, 256), 256, 0, stream>>>(start, tile, slice, name_off, ns, names);
     HIPCHK(hipGetLastError());
     h_bytes.resize((size_t)total[0]);
     h_names.resize((size_t)total[1]);
@@ -1027,11 +959,11 @@ int TileStore::restore_records(const otr_tile_records* in, otr_tile_restore_resu
     a.rec_off = in->rec_off;
     a.bytes = in->bytes;
   } else {
-    int64_t* st = buf<int64_t>(T_I_START, n);
-    int64_t* ti = buf<int64_t>(T_I_TILE, n);
-    int32_t* sl = buf<int32_t>(T_I_SLICE, n);
-    int64_t* of = buf<int64_t>(T_I_OFF, (size_t)n + 1);
-    uint8_t* by = buf<uint8_t>(T_I_BYTES, (size_t)nb);
+    int64_t* st = get<int64_t>(T_I_START, n);
+    int64_t* ti = get<int64_t>(T_I_TILE, n);
+    int32_t* sl = get<int32_t>(T_I_SLICE, n);
+    int64_t* of = get<int64_t>(T_I_OFF, (size_t)n + 1);
+    uint8_t* by = get<uint8_t>(T_I_BYTES, (size_t)nb);
     if (n > 0) {
       HIPCHK(hipMemcpyAsync(st, in->start, 8 * (size_t)n, hipMemcpyHostToDevice, stream));
       HIPCHK(hipMemcpyAsync(ti, in->tile_id, 8 * (size_t)n, hipMemcpyHostToDevice, stream));
@@ -1040,7 +972,7 @@ int TileStore::restore_records(const otr_tile_records* in, otr_tile_restore_resu
     HIPCHK(hipMemcpyAsync(of, in->rec_off, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, stream));
     if (nb > 0) HIPCHK(hipMemcpyAsync(by, in->bytes, (size_t)nb, hipMemcpyHostToDevice, stream));
     if (nt > 0) {
-      uint8_t* mp = buf<uint8_t>(T_I_MAP, (size_t)(kTileMapEntry * nt));
+      uint8_t* mp = get<uint8_t>(T_I_MAP, (size_t)(kTileMapEntry * nt));
       HIPCHK(hipMemcpyAsync(mp, in->map_bytes, (size_t)(kTileMapEntry * nt), hipMemcpyHostToDevice, stream));
       d_map = mp;
     }
@@ -1051,24 +983,24 @@ int TileStore::restore_records(const otr_tile_records* in, otr_tile_restore_resu
     a.bytes = by;
   }
   // words: the records' verdict, the map's verdict, then the TRC_* counters
-  unsigned long long* words = buf<unsigned long long>(T_I_WORDS, 2 + TRC_WORDS);
+  unsigned long long* words = get<unsigned long long>(T_I_WORDS, 2 + TRC_WORDS);
   unsigned long long h_words[2 + TRC_WORDS];
   HIPCHK(hipMemsetAsync(words, 0xFF, 16, stream));
   HIPCHK(hipMemsetAsync(words + 2, 0, 8 * TRC_WORDS, stream));
-  int32_t* count = buf<int32_t>(T_I_COUNT, n);
-  int32_t* key_ok = buf<int32_t>(T_I_KEY_OK, n);
-  unsigned long long* file_key = buf<unsigned long long>(T_I_FILE, n);
-  unsigned long long* file_a = buf<unsigned long long>(T_I_FILE_A, n);
-  unsigned long long* file_b = buf<unsigned long long>(T_I_FILE_B, n);
-  unsigned long long* slice_key = buf<unsigned long long>(T_I_SLICE_KEY, n);
-  unsigned long long* slice_b = buf<unsigned long long>(T_I_SLICE_B, n);
-  int32_t* idx_a = buf<int32_t>(T_I_IDX_A, n);
-  int32_t* idx_b = buf<int32_t>(T_I_IDX_B, n);
-  int32_t* order = buf<int32_t>(T_I_IDX_C, n);
+  int32_t* count = get<int32_t>(T_I_COUNT, n);
+  int32_t* key_ok = get<int32_t>(T_I_KEY_OK, n);
+  unsigned long long* file_key = get<unsigned long long>(T_I_FILE, n);
+  unsigned long long* file_a = get<unsigned long long>(T_I_FILE_A, n);
+  unsigned long long* file_b = get<unsigned long long>(T_I_FILE_B, n);
+  unsigned long long* slice_key = get<unsigned long long>(T_I_SLICE_KEY, n);
+  unsigned long long* slice_b = get<unsigned long long>(T_I_SLICE_B, n);
+  int32_t* idx_a = get<int32_t>(T_I_IDX_A, n);
+  int32_t* idx_b = get<int32_t>(T_I_IDX_B, n);
+  int32_t* order = get<int32_t>(T_I_IDX_C, n);
   if (n > 0) {
-    const unsigned g = tst_grid(n, 256);
-    k_tilerec_validate<<<tst_grid(n, 256 / OTR_WAVE), 256, 0, stream>>>(a, count, key_ok, file_key, slice_key, idx_a,
-                                                                        words);
+    const unsigned g = grid_ceil1(n, 256);
+    k_tilerec_validate<<<grid_ceil1(n, 256 / OTR_WAVE), 256, 0, stream>>>(a, count, key_ok, file_key, slice_key, idx_a,
+                                                                          words);
     HIPCHK(hipGetLastError());
     // (file, slice) order, stable: by slice, then by file
     if ((rc = sort_pairs(slice_key, slice_b, idx_a, idx_b, n, err))) return rc;
@@ -1077,14 +1009,14 @@ int TileStore::restore_records(const otr_tile_records* in, otr_tile_restore_resu
     k_tilerec_duplicates<<<g, 256, 0, stream>>>(file_b, order, slice_key, key_ok, n, words);
     HIPCHK(hipGetLastError());
   }
-  unsigned long long* map_b = buf<unsigned long long>(T_M_FILE_B, nt > 0 ? nt : 1);
-  int32_t* map_order = buf<int32_t>(T_M_IDX_B, nt > 0 ? nt : 1);
-  int32_t* map_value = buf<int32_t>(T_M_VALUE, nt > 0 ? nt : 1);
+  unsigned long long* map_b = get<unsigned long long>(T_M_FILE_B, nt > 0 ? nt : 1);
+  int32_t* map_order = get<int32_t>(T_M_IDX_B, nt > 0 ? nt : 1);
+  int32_t* map_value = get<int32_t>(T_M_VALUE, nt > 0 ? nt : 1);
   if (nt > 0) {
-    unsigned long long* map_a = buf<unsigned long long>(T_M_FILE_A, nt);
-    int32_t* map_idx = buf<int32_t>(T_M_IDX_A, nt);
-    int32_t* map_ok = buf<int32_t>(T_M_OK, nt);
-    const unsigned gm = tst_grid(nt, 256);
+    unsigned long long* map_a = get<unsigned long long>(T_M_FILE_A, nt);
+    int32_t* map_idx = get<int32_t>(T_M_IDX_A, nt);
+    int32_t* map_ok = get<int32_t>(T_M_OK, nt);
+    const unsigned gm = grid_ceil1(nt, 256);
     k_tilerec_map_keys<<<gm, 256, 0, stream>>>(d_map, nt, a.q, map_a, map_idx, map_value, map_ok, words + 1,
                                                words + 2);
     if ((rc = sort_pairs(map_a, map_b, map_idx, map_order, nt, err))) return rc;
@@ -1106,12 +1038,12 @@ int TileStore::restore_records(const otr_tile_records* in, otr_tile_restore_resu
                         ": invalid key, negative value or repeated key");
   }
   if (n > 0) {
-    int64_t* ref = buf<int64_t>(T_I_REF, n);
-    int64_t* row_off = buf<int64_t>(T_I_ROW_OFF, (size_t)n + 1);
+    int64_t* ref = get<int64_t>(T_I_REF, n);
+    int64_t* row_off = get<int64_t>(T_I_ROW_OFF, (size_t)n + 1);
     HIPCHK(hipMemsetAsync(row_off, 0, 8, stream));
     // (the slice keys' sorted copy is free again: the join reads the keys in input order)
-    k_tilerec_join<<<tst_grid(n, 256), 256, 0, stream>>>(file_b, order, slice_key, count, n, map_b, map_order,
-                                                         map_value, nt, ref, words + 2);
+    k_tilerec_join<<<grid_ceil1(n, 256), 256, 0, stream>>>(file_b, order, slice_key, count, n, map_b, map_order,
+                                                           map_value, nt, ref, words + 2);
     HIPCHK(hipGetLastError());
     if ((rc = scan64(ref, row_off + 1, n, err))) return rc;
     HIPCHK(hipMemcpyAsync(h_words, words, sizeof(h_words), hipMemcpyDeviceToHost, stream));
@@ -1124,9 +1056,9 @@ int TileStore::restore_records(const otr_tile_records* in, otr_tile_restore_resu
                           std::to_string(cfg.max_rows) + ")");
     }
     if (total > 0) {
-      k_tilerec_write<<<tst_grid(n, 256 / OTR_WAVE), 256, 0, stream>>>(a, order, ref, row_off, rows + n_rows,
-                                                                       timed() ? t0 + n_rows : nullptr,
-                                                                       timed() ? t1 + n_rows : nullptr);
+      k_tilerec_write<<<grid_ceil1(n, 256 / OTR_WAVE), 256, 0, stream>>>(a, order, ref, row_off, rows + n_rows,
+                                                                         timed() ? t0 + n_rows : nullptr,
+                                                                         timed() ? t1 + n_rows : nullptr);
       HIPCHK(hipGetLastError());
     }
     if ((rc = finish(&out->device_ms, err))) return rc;

@@ -1,9 +1,9 @@
-"""Hand-built entry sets for otr_hist_reduce (the keyed speed histogram, otr_engine.hip
-hist_reduce_impl).  A helper module (no tests, no fixtures): tests/test_hist_cases_cpu.py pins
+"""Hand-built entry sets for otr_hist_reduce (the keyed speed histogram, otr_tiles.hip
+Matcher::hist_reduce).  A helper module (no tests, no fixtures): tests/test_hist_cases_cpu.py pins
 the branch every family takes and that its reduction is not trivial, tests/test_gpu_hist_keyed.py
 runs them on the device against oracle/hist.reduce.
 
-hist_reduce_impl sorts by (file, id, next id, speed bin) with LSD radix passes chosen from the
+Matcher::hist_reduce sorts by (file, id, next id, speed bin) with LSD radix passes chosen from the
 data (k_entry_range: OR of the ids and of the next ids, min / max bucket, whether every file is
 the one K9 derives from its id):
   low passes   'combined' one pass over next id << 3 | bin when bit_width(next OR) + 3 <= 64,
@@ -18,7 +18,7 @@ than 1024 pairs.  k_entry_range strides a fixed grid of 128 x 1024 threads: the 
 keep the entry that alone decides the bucket spread at the last index.
 
 Every set is seeded, shuffled and has keys repeated in all 8 speed bins.  An id of more than
-18 decimal digits keys on its leading 18 in the device's string order (otr_kernels.h dec_key):
+18 decimal digits keys on its leading 18 in the device's string order (otr_tile_kernels.h dec_key):
 the wide ids here differ within those (checked by _leading18)."""
 import numpy as np
 
@@ -49,7 +49,7 @@ def bit_width(v):
 
 
 def pass_choice(e):
-    """(low passes, high passes, [(field, end bit)]) of hist_reduce_impl for the entries e."""
+    """(low passes, high passes, [(field, end bit)]) of Matcher::hist_reduce for the entries e."""
     nor = ior = fo = 0
     for v in e['next_id'].tolist():
         nor |= v

@@ -1,4 +1,4 @@
-"""Edge cases of the probe ingest (K11, reporter_amd/csrc/otr_ingest.h and Matcher::ingest_impl):
+"""Edge cases of the probe ingest (K11, reporter_amd/csrc/otr_ingest.h and Matcher::ingest):
 numerals whose path through the number parsers is known, and hand-built texts, each named for
 the one edge it is there for.  tests/test_ingest_cases_cpu.py pins what they reach;
 tests/test_gpu_ingest_edges.py runs them on the device.  TEST INFRASTRUCTURE ONLY.

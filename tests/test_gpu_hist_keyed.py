@@ -3,7 +3,7 @@ restatement oracle/hist.py: device tile rows (K9) sort-reduced by (file, id, nex
 speed bin), pair cull at privacy p; entries merged across inputs (the owner's side of
 the exchange); the single-GPU end of the exchange (all entries owned by rank 0); and the
 hand-built entry sets of tests/hist_cases.py, one for every choice of radix passes
-hist_reduce_impl makes from the data, for files of more than 1024 pairs and for the sizes around
+Matcher::hist_reduce makes from the data, for files of more than 1024 pairs and for the sizes around
 k_entry_range's blocks and grid."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""The entry sets of tests/hist_cases.py take the branches of hist_reduce_impl they are named for,
+"""The entry sets of tests/hist_cases.py take the branches of Matcher::hist_reduce they are named for,
 and their reductions are not trivial (CPU only).  Requirements on the inputs of the family tests
 in tests/test_gpu_hist_keyed.py: when a set or the pass choice changes, this file says which
 branch the GPU tests lost."""
