@@ -46,6 +46,34 @@ int scan_sort_bytes(In in, Out out, const K* k_in, K* k_out, const V* v_in, V* v
   return OTR_OK;
 }
 
+// column loaders of tuple_sums (below): K arrays as they are, or each behind a leading zero (the
+// exclusive offsets and the total of every column, as shifted_input gives for one array); a null
+// array is a column of zeros
+template <int K, bool SHIFT>
+struct ArrayColumns {
+  const int64_t* p[K];
+  __host__ __device__ int64_t operator()(int q, int64_t i) const {
+    if (!p[q]) return 0;
+    if (SHIFT) return i > 0 ? p[q][i - 1] : 0;
+    return p[q][i];
+  }
+};
+
+// The input 0, src[0], src[1], ..: an inclusive sum of its first n + 1 values is the exclusive
+// offsets of src[0, n) with the total behind them (dst[0] = 0 .. dst[n]), in one scan and with no
+// fill of the leading zero.
+template <class T>
+struct ShiftedLoad {
+  const T* src;
+  __host__ __device__ T operator()(int64_t i) const { return i > 0 ? src[i - 1] : T(0); }
+};
+template <class T>
+using ShiftedInput = hipcub::TransformInputIterator<T, ShiftedLoad<T>, hipcub::CountingInputIterator<int64_t>>;
+template <class T>
+ShiftedInput<T> shifted_input(const T* src) {
+  return ShiftedInput<T>(hipcub::CountingInputIterator<int64_t>(0), ShiftedLoad<T>{src});
+}
+
 // out[i] = in[0] + .. + in[i]; ws of at least scan_bytes
 template <class In, class Out>
 int inclusive_sum(Workspace ws, In in, Out out, int n, hipStream_t stream, std::string* err) {
@@ -58,6 +86,81 @@ template <class K, class V>
 int sort_pairs(Workspace ws, const K* k_in, K* k_out, const V* v_in, V* v_out, int n, int begin_bit, int end_bit,
                hipStream_t stream, std::string* err) {
   HIPCHK(hipcub::DeviceRadixSort::SortPairs(ws.p, ws.bytes, k_in, k_out, v_in, v_out, n, begin_bit, end_bit, stream));
+  return OTR_OK;
+}
+
+// ---- K inclusive sums over the same n in ONE scan: the sums of a K-tuple.  Column q of element
+// i comes from a loader, load(q, i) -> int64; its running sum goes to out[q][i] (a null out[q]
+// drops the column).  Integer sums: the same values as K separate scans, in two launches
+// instead of 2 K.
+template <int K>
+struct TupleK {
+  int64_t v[K];
+};
+template <int K>
+struct TupleAdd {
+  __host__ __device__ TupleK<K> operator()(const TupleK<K>& a, const TupleK<K>& b) const {
+    TupleK<K> r;
+    for (int q = 0; q < K; ++q) r.v[q] = a.v[q] + b.v[q];
+    return r;
+  }
+};
+template <int K, class Load>
+struct TupleLoad {
+  Load load;
+  __host__ __device__ TupleK<K> operator()(int64_t i) const {
+    TupleK<K> r;
+    for (int q = 0; q < K; ++q) r.v[q] = load(q, i);
+    return r;
+  }
+};
+// the output side: an iterator whose references store a tuple's columns into K arrays
+template <int K>
+struct TupleOut {
+  int64_t* out[K];
+  int64_t at;
+  struct Ref {
+    int64_t* out[K];
+    int64_t i;
+    __host__ __device__ const Ref& operator=(const TupleK<K>& x) const {
+      for (int q = 0; q < K; ++q)
+        if (out[q]) out[q][i] = x.v[q];
+      return *this;
+    }
+  };
+  using iterator_category = std::random_access_iterator_tag;
+  using value_type = TupleK<K>;
+  using difference_type = int64_t;
+  using pointer = void;
+  using reference = Ref;
+  __host__ __device__ Ref operator[](int64_t n) const {
+    Ref r;
+    for (int q = 0; q < K; ++q) r.out[q] = out[q];
+    r.i = at + n;
+    return r;
+  }
+  __host__ __device__ Ref operator*() const { return (*this)[0]; }
+  __host__ __device__ TupleOut operator+(int64_t n) const {
+    TupleOut r = *this;
+    r.at += n;
+    return r;
+  }
+  __host__ __device__ TupleOut& operator+=(int64_t n) {
+    at += n;
+    return *this;
+  }
+};
+template <int K, class Load>
+using TupleInput = hipcub::TransformInputIterator<TupleK<K>, TupleLoad<K, Load>, hipcub::CountingInputIterator<int64_t>>;
+
+// ws.p null: the size query (into ws->bytes); else the scan
+template <int K, class Load>
+int tuple_sums(Workspace* ws, Load load, int64_t* const (&out)[K], int n, hipStream_t stream, std::string* err) {
+  TupleInput<K, Load> in(hipcub::CountingInputIterator<int64_t>(0), TupleLoad<K, Load>{load});
+  TupleOut<K> o{};
+  for (int q = 0; q < K; ++q) o.out[q] = out[q];
+  o.at = 0;
+  HIPCHK(hipcub::DeviceScan::InclusiveScan(ws->p, ws->bytes, in, o, TupleAdd<K>(), n, stream));
   return OTR_OK;
 }
 

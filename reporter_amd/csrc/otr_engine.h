@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
 #include <shared_mutex>
 #include <string>
 #include <vector>
@@ -118,7 +119,30 @@ struct Matcher {
   TileText* ttx = nullptr;      // the file texts of the last otr_tiles_text / flush_text, owned
   DevPool pool{PoolOwner::matcher, nullptr, 0};  // the workspace slots (otr_slots.h), sized at first use
   GSlab gslab[2];
+  // the turn cost tables last uploaded and the device buffer that holds them: a batch with the
+  // same parameters and the same buffer uploads nothing
   std::vector<int32_t> h_turn;
+  const int32_t* turn_dev = nullptr;
+  // the same for K7's arguments, which k_compact reads from device memory (copy-out only)
+  std::vector<char> seg_args;
+  const void* seg_args_dev = nullptr;
+  // The pinned mailbox (mapped host memory, allocated once, one per matcher so that streams
+  // stay independent): every scalar the host reads of a batch or of a histogram reduce
+  // arrives here, one record per host wait.  post_wait gathers the runs (8-byte words, eight
+  // runs at most, kMailWords in all) with k_post, waits for the stream and leaves them back to
+  // back in mail[]; post only queues the gather, into dst.  Nothing is copied into pageable
+  // memory, and no wait has more than one device-to-host operation.
+  static constexpr int kMailWords = 512;
+  unsigned long long* mail = nullptr;
+  struct MailRun {
+    const void* src;
+    int words;
+  };
+  int post(std::initializer_list<MailRun> runs, unsigned long long* dst, std::string* err);
+  int post_wait(std::initializer_list<MailRun> runs, std::string* err);
+  // pinned host copy of the batch's drain slab (per-trace output counts, folded counters)
+  unsigned long long* h_drain = nullptr;
+  size_t h_drain_words = 0;
   // host result storage (OTR_BATCH_COPY_OUT)
   std::vector<int64_t> h_trace_state_off, h_state_probe, h_trace_route_off, h_trace_seg_off, h_seg_way_off,
       h_trace_rep_off;

@@ -19,6 +19,7 @@
 #include "otr_points.h"
 #include "otr_slots.h"
 #include "otr_traversals.h"
+#include "otr_util_kernels.h"
 
 namespace otr {
 static_assert(kTraceWaves == 4, "grid_trace_rows (otr_launch.h) assumes 4 traces per block");
@@ -408,12 +409,41 @@ Matcher::~Matcher() {
   if (tst) tile_store_destroy(tst);
   if (ttx) tile_text_destroy(ttx);
   pool.release();
+  if (mail) (void)hipHostFree(mail);
+  if (h_drain) (void)hipHostFree(h_drain);
   for (auto& sl : gslab)
     for (void* q : {(void*)sl.key, (void*)sl.lab, (void*)sl.qmark, (void*)sl.fr, (void*)sl.touched})
       if (q) (void)hipFree(q);
   if (ev_init)
     for (auto& e : ev) (void)hipEventDestroy(e);
   if (stream) (void)hipStreamDestroy(stream);
+}
+
+// the runs gathered by one k_post launch into dst (the mailbox when null)
+int Matcher::post(std::initializer_list<MailRun> runs, unsigned long long* dst, std::string* err) {
+  if (!mail) HIPCHK(hipHostMalloc((void**)&mail, 8 * kMailWords, hipHostMallocMapped | hipHostMallocCoherent));
+  PostArgs a{};
+  int q = 0, words = 0;
+  for (const MailRun& r : runs) {
+    if (q >= kPostRuns || r.words < 0 || (!dst && words + r.words > kMailWords)) {
+      if (err) *err = "mailbox record too large";
+      return OTR_DEVICE_ERROR;
+    }
+    a.src[q] = (const unsigned long long*)r.src;
+    a.n[q] = r.words;
+    words += r.words;
+    ++q;
+  }
+  a.dst = dst;
+  if (!dst) HIPCHK(hipHostGetDevicePointer((void**)&a.dst, mail, 0));
+  k_post<<<1, 64, 0, stream>>>(a);
+  return OTR_OK;
+}
+
+int Matcher::post_wait(std::initializer_list<MailRun> runs, std::string* err) {
+  if (int rc = post(runs, nullptr, err)) return rc;
+  HIPCHK(hipStreamSynchronize(stream));
+  return OTR_OK;
 }
 
 // per-trace output capacity: route/segment/way/report slots
@@ -467,10 +497,51 @@ __global__ void k_collect_tier(int64_t n, int32_t* flag, uint32_t want, int64_t*
 }
 
 // every task the first route tier flagged (overflow or general): the superset of what the
-// later tiers collect, so their collects scan this short list instead of every task
-__global__ void k_collect_flagged(int64_t n, const int32_t* flag, int64_t* list, unsigned long long* count) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  block_append(i < n && flag[i] != 0, i, list, count);
+// later tiers collect, so their collects scan this short list instead of every task.  It reads
+// every flag (55 MB at C2) and keeps few, so it runs at memory speed: four flags per thread in
+// one 16-byte load (flag: 16-byte aligned, a pool buffer), an ordered count inside the block
+// (wave scans of the threads' hit counts, then the 16 wave totals) and one global atomic per
+// block that has a hit.  A block's tasks stay in task order in the list (the retry tiers'
+// locality); the blocks' order is arbitrary, as it always was.
+constexpr int kFlagsPerThread = 4, kFlaggedBlock = 1024;
+__global__ __launch_bounds__(kFlaggedBlock) void k_collect_flagged(int64_t n, const int32_t* flag, int64_t* list,
+                                                                  unsigned long long* count) {
+  __shared__ unsigned int s_wave[kFlaggedBlock / OTR_WAVE];
+  __shared__ unsigned long long s_base;
+  const int64_t i0 = ((int64_t)blockIdx.x * kFlaggedBlock + threadIdx.x) * kFlagsPerThread;
+  int4 f = make_int4(0, 0, 0, 0);
+  if (i0 + 3 < n) {
+    f = *reinterpret_cast<const int4*>(flag + i0);
+  } else if (i0 < n) {  // (the last tasks, fewer than four)
+    f.x = flag[i0];
+    if (i0 + 1 < n) f.y = flag[i0 + 1];
+    if (i0 + 2 < n) f.z = flag[i0 + 2];
+  }
+  const unsigned int c = (f.x != 0) + (f.y != 0) + (f.z != 0) + (f.w != 0);
+  const int lane = (int)(threadIdx.x % OTR_WAVE), w = (int)(threadIdx.x / OTR_WAVE);
+  unsigned int incl = c;
+  for (int o = 1; o < OTR_WAVE; o <<= 1) {
+    const unsigned int v = (unsigned int)__shfl_up((int)incl, o);
+    if (lane >= o) incl += v;
+  }
+  if (lane == OTR_WAVE - 1) s_wave[w] = incl;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned int t = 0;
+    for (int k = 0; k < kFlaggedBlock / OTR_WAVE; ++k) {
+      const unsigned int x = s_wave[k];
+      s_wave[k] = t;
+      t += x;
+    }
+    s_base = t ? atomicAdd(count, (unsigned long long)t) : 0ull;
+  }
+  __syncthreads();
+  if (c == 0) return;
+  int64_t o = (int64_t)s_base + s_wave[w] + (incl - c);
+  if (f.x != 0) list[o++] = i0;
+  if (f.y != 0) list[o++] = i0 + 1;
+  if (f.z != 0) list[o++] = i0 + 2;
+  if (f.w != 0) list[o++] = i0 + 3;
 }
 
 // k_collect_tier over the device-counted task list cand[0..*n_cand): a fixed grid
@@ -559,10 +630,13 @@ __global__ void k_collect_tier_list(const unsigned long long* n_in, int32_t* fla
   block_append(sel, i, list, count);
 }
 
-// states that need a path: a step inside a sub-path
+// states that need a path: a step inside a sub-path.  The step flags ovf[0, n_states] (one per
+// list position, fewer than states) are zeroed here, so the path stage's first attempt fills nothing.
 __global__ void k_step_list(int64_t n_states, const int64_t* prev, const uint8_t* brk, const int32_t* cand_count,
-                            int64_t* list, unsigned long long* count) {
+                            int64_t* list, unsigned long long* count, int32_t* ovf) {
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < n_states) ovf[s] = 0;
+  if (s == 0) ovf[n_states] = 0;
   block_append(s < n_states && cand_count[s] > 0 && prev[s] >= 0 && !brk[s], s, list, count);
 }
 
@@ -571,9 +645,12 @@ __global__ void k_step_list(int64_t n_states, const int64_t* prev, const uint8_t
 // retry collects scan the whole index range, whose gap keeps its zero flags)
 __global__ void k_step_lists(int64_t n_states, const int64_t* prev, const uint8_t* brk, const int32_t* cand_count,
                              PathClass pc, int64_t* list, unsigned long long* count_front,
-                             unsigned long long* count_back, unsigned long long* n_all) {
+                             unsigned long long* count_back, unsigned long long* n_all, int32_t* ovf) {
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (s == 0) *n_all = (unsigned long long)n_states;
+  // (the step flags of every index, the gap between the two lists included: k_step_list)
+  if (s < n_states) ovf[s] = 0;
+  if (s == 0) ovf[n_states] = 0;
   const bool hit = s < n_states && cand_count[s] > 0 && prev[s] >= 0 && !brk[s];
   bool small = false;
   if (hit) {
@@ -636,6 +713,9 @@ static unsigned pgrid(unsigned full, int64_t units) {
 
 constexpr unsigned kCollectGrid = 512;  // blocks of a collect over the flagged tasks (a grid stride)
 
+// words rounded up to whole 256 B lines (the parts of a batch's control block)
+static constexpr size_t line(size_t words) { return (words + 31) / 32 * 32; }
+
 // One batch on its way through the pipeline: what the stages share, and the stages in the
 // order Matcher::run calls them.  A stage returns OTR_OK or the code the batch ends with.
 struct Batch {
@@ -682,7 +762,16 @@ struct Batch {
   // n_ctr values behind them) and list counters (otr_tiers.h CntWord)
   static constexpr size_t bank = (size_t)OTR_COUNTERS * kCShards;
   static constexpr size_t n_ctr = kBanks * (size_t)OTR_COUNTERS;
-  unsigned long long *d_counters = nullptr, *cnt = nullptr;
+  // The batch's control block, one buffer zeroed by ONE fill at batch start (upload()): the work
+  // counter banks, their folded values, the list counters and path cursors (cnt), the route
+  // tiers' work queues and the path tiers' (pq); each part starts on a 256 B line.  Only a
+  // repeated path attempt clears its own words again (paths_attempt).
+  static constexpr int kPQWords = 16 * 8;
+  static constexpr size_t kCntAt = line(kBanks * bank + n_ctr);
+  static constexpr size_t kQueuesAt = kCntAt + line(C_CURSORS + kShards);
+  static constexpr size_t kPQAt = kQueuesAt + line((size_t)kQueues * kQueueWords);
+  static constexpr size_t kControlWords = kPQAt + line(8 * kPQWords);
+  unsigned long long *d_counters = nullptr, *cnt = nullptr, *pq = nullptr;
   int64_t *list = nullptr, *fail_tasks = nullptr, *flagged = nullptr;
   int32_t *task_ovf = nullptr, *d_turn = nullptr;
   uint32_t *trans = nullptr, *trans_tc = nullptr;
@@ -698,14 +787,16 @@ struct Batch {
   const unsigned long long* nscan_d = nullptr;
   int32_t* step_ovf = nullptr;
   bool small_paths = false;
-  // what drain() brought back
-  std::vector<unsigned long long> hc;
+  int64_t* cap = nullptr;  // per-trace output capacity (k_capacity, queued behind every path attempt)
+  int path_attempts = 0;
+  // what drain() brought back (the matcher's pinned drain buffer)
+  const unsigned long long* hc = nullptr;
   unsigned long long h_fail[2] = {0ull, 0ull};  // route tasks / paths beyond every search tier
-  std::vector<int64_t> route_n, seg_n, way_n, rep_n;
+  const int64_t *route_n = nullptr, *seg_n = nullptr, *way_n = nullptr, *rep_n = nullptr;
 
   // the stages, in order
-  int upload(), states(), candidates(), link(), route_first(), route_retry(), route_edge(), route_global(), viterbi();
-  int paths(), paths_attempt(int64_t capacity), segments(), points(), traversals(), drain(), debug_fail(),
+  int upload(), check_probes(), states(), candidates(), link(), route_first(), route_retry(), route_edge(), route_global(), viterbi();
+  int paths(), paths_attempt(int64_t capacity, bool again), segments(), points(), traversals(), drain(), debug_fail(),
       name_failed();
   void fold_counters();
   int copy_out(), points_out(), traversals_out();
@@ -734,6 +825,10 @@ struct Batch {
 
   int scan(const int64_t* src, int64_t* dst_np1, int64_t n);
   int read_i64(const int64_t* p, int64_t* v);
+  template <class... R>
+  int post_wait(R... runs) {
+    return mat.post_wait({runs...}, err);
+  }
   int slabs(int tier, GSlabs* out);
   template <class V>
   int dl(V& vec, const void* src, size_t n) {
@@ -823,7 +918,7 @@ int Batch::upload() {
     b.mode = d_mode;
     b.acc = d_acc;
   } else {
-    if (int rc = read_back(stream, err, fetch(&N, in->trace_offsets + T))) return rc;
+    // (N, the last trace offset, is still on the device: it comes back with S, states())
     b.trace_off = in->trace_offsets;
     b.lat = in->lat;
     b.lon = in->lon;
@@ -831,6 +926,18 @@ int Batch::upload() {
     b.mode = in->mode;
     b.acc = in->accuracy;
   }
+  mat.h_trace_status.assign(T, OTR_OK);
+  d_counters = need<unsigned long long>(S_COUNTERS, kControlWords);
+  cnt = d_counters + kCntAt;
+  queues = d_counters + kQueuesAt;
+  pq = d_counters + kPQAt;
+  HIPCHK(hipMemsetAsync(d_counters, 0, kControlWords * 8, stream));
+  return in->memory == OTR_MEM_HOST ? check_probes() : OTR_OK;
+}
+
+// the batch-size check, once N is known (a device batch: after K0's first pass, which launches
+// by traces and reads no N)
+int Batch::check_probes() {
   out->n_probes = N;
   // one wave per state / trace in the per-state and per-trace kernels: a dispatch counts
   // its work-items in 32 bits, so a batch holds at most kMaxBatchProbes = 2^26 - 64 probes
@@ -842,24 +949,26 @@ int Batch::upload() {
              " per otr_match_batch call";
     return OTR_BAD_REQUEST;
   }
-  mat.h_trace_status.assign(T, OTR_OK);
-  d_counters = need<unsigned long long>(S_COUNTERS, kBanks * bank + n_ctr);
-  HIPCHK(hipMemsetAsync(d_counters, 0, kBanks * bank * 8, stream));
   return OTR_OK;
 }
 
-// dst[0] = 0, dst[1..n] = inclusive prefix sums
+// dst[0] = 0, dst[1..n] = inclusive prefix sums: one inclusive sum over the n + 1 values
+// 0, src[0], .., src[n - 1] (otr_devscan.h shifted_input), so the leading zero needs no fill
 int Batch::scan(const int64_t* src, int64_t* dst_np1, int64_t n) {
-  HIPCHK(hipMemsetAsync(dst_np1, 0, 8, stream));
-  if (n == 0) return OTR_OK;
+  const auto in0 = shifted_input(src);
   Workspace tmp;
-  if (int rc = otr::scan_bytes(src, dst_np1 + 1, (int)n, &tmp.bytes, stream, err)) return rc;
+  if (int rc = otr::scan_bytes(in0, dst_np1, (int)n + 1, &tmp.bytes, stream, err)) return rc;
   scan_bytes = std::max(scan_bytes, tmp.bytes);  // (the slot keeps the batch's largest)
   tmp.p = need<char>(S_SCAN_TMP, scan_bytes);
-  return inclusive_sum(tmp, src, dst_np1 + 1, (int)n, stream, err);
+  return inclusive_sum(tmp, in0, dst_np1, (int)n + 1, stream, err);
 }
 
-int Batch::read_i64(const int64_t* p, int64_t* v) { return read_back(stream, err, fetch(v, p)); }
+// one word through the mailbox
+int Batch::read_i64(const int64_t* p, int64_t* v) {
+  if (int rc = post_wait(Matcher::MailRun{p, 1})) return rc;
+  *v = (int64_t)mat.mail[0];
+  return OTR_OK;
+}
 
 // ---- K0: states
 int Batch::states() {
@@ -870,7 +979,14 @@ int Batch::states() {
   k_select_states<<<grid_ceil(T, 256), 256, 0, stream>>>(b, mp, state_cnt, nullptr, nullptr, nullptr);
   te(OTR_STAGE_STATES);
   if ((rc = scan(state_cnt, trace_state_off, T))) return rc;
-  if ((rc = read_i64(trace_state_off + T, &S))) return rc;
+  if (in->memory == OTR_MEM_HOST) {
+    if ((rc = read_i64(trace_state_off + T, &S))) return rc;
+  } else {  // a device batch: its probe count rides along
+    if ((rc = post_wait(Matcher::MailRun{trace_state_off + T, 1}, Matcher::MailRun{in->trace_offsets + T, 1}))) return rc;
+    S = (int64_t)mat.mail[0];
+    N = (int64_t)mat.mail[1];
+    if ((rc = check_probes())) return rc;
+  }
   out->n_states = S;
   state_probe = need<int64_t>(S_STATE_PROBE, S);
   state_trace = need<int32_t>(S_STATE_TRACE, S);
@@ -1003,14 +1119,26 @@ int Batch::link() {
     sm.small_keys = (float)small_keys;
     k_ntask<<<grid_ceil(S, 256), 256, 0, stream>>>(S, sb.prev, pr.nroot, sb.ntask, sm);
   }
-  if ((rc = scan(sb.ntask, task_off, S))) return rc;
-  if (small_tier && (rc = scan(ntask4, task4_off, S))) return rc;
-  if (tiny_tier && (rc = scan(ntask8, task8_off, S))) return rc;
-  if ((rc = scan(sb.ntrans, trans_off, S))) return rc;
-  HIPCHK(hipMemcpyAsync(&NT, task_off + S, 8, hipMemcpyDeviceToHost, stream));
-  if (small_tier) HIPCHK(hipMemcpyAsync(&NT4, task4_off + S, 8, hipMemcpyDeviceToHost, stream));
-  if (tiny_tier) HIPCHK(hipMemcpyAsync(&NT8, task8_off + S, 8, hipMemcpyDeviceToHost, stream));
-  if ((rc = read_back(stream, err, fetch(&NTR, trans_off + S)))) return rc;
+  // the four offset arrays in one scan over the 4-tuple (otr_devscan.h tuple_sums), each
+  // behind its leading zero: S + 1 tuples, the totals in element S
+  {
+    const ArrayColumns<4, true> cols{{sb.ntask, sb.ntrans, ntask4, ntask8}};
+    int64_t* const offs[4] = {task_off, trans_off, task4_off, task8_off};
+    Workspace tmp;
+    if ((rc = tuple_sums<4>(&tmp, cols, offs, (int)S + 1, stream, err))) return rc;
+    scan_bytes = std::max(scan_bytes, tmp.bytes);
+    tmp.p = need<char>(S_SCAN_TMP, scan_bytes);
+    if ((rc = tuple_sums<4>(&tmp, cols, offs, (int)S + 1, stream, err))) return rc;
+  }
+  // the four totals in one mailbox record (a tier that is off: no word, its count stays 0)
+  if ((rc = post_wait(Matcher::MailRun{task_off + S, 1}, Matcher::MailRun{trans_off + S, 1},
+                      Matcher::MailRun{small_tier ? task4_off + S : nullptr, small_tier ? 1 : 0},
+                      Matcher::MailRun{tiny_tier ? task8_off + S : nullptr, tiny_tier ? 1 : 0})))
+    return rc;
+  NT = (int64_t)mat.mail[0];
+  NTR = (int64_t)mat.mail[1];
+  if (small_tier) NT4 = (int64_t)mat.mail[2];
+  if (tiny_tier) NT8 = (int64_t)mat.mail[3];  // (the tiny tier needs the small one: word 3)
   NT += NT4 + NT8;
   task_ovf = need<int32_t>(S_TASK_OVF, NT);
   trans = need<uint32_t>(S_TRANS, NTR);
@@ -1047,9 +1175,23 @@ int Batch::link() {
     for (int m = 0; m < OTR_MODES; ++m) ta.est_v[m] = est_v[m];
     ta.n_tiers = n_est_tiers;
     for (int t = 0; t < n_est_tiers; ++t) ta.tier_keys[t] = est_tier_keys[t];
-    if (NT > 0) HIPCHK(hipMemsetAsync(task_ovf, 0, 4 * NT, stream));
+    // (no fill of task_ovf: every task's representative stores its flag, 0 or 5, with its
+    // record.  OTR_DEBUG_TASKS checks that on the host: a pattern no flag takes goes in first
+    // and none of it may be left)
+    static const bool debug_tasks = getenv("OTR_DEBUG_TASKS") != nullptr;
+    if (debug_tasks && NT > 0) HIPCHK(hipMemsetAsync(task_ovf, 0x7F, 4 * NT, stream));
     if (k32) k_tasks<2><<<(unsigned)grid_per_state_waves(S, 2).blocks, 256, 0, stream>>>(ta);
     else k_tasks<1><<<(unsigned)grid_per_state_waves(S, 1).blocks, 256, 0, stream>>>(ta);
+    if (debug_tasks && NT > 0) {
+      std::vector<int32_t> h((size_t)NT);
+      HIPCHK(hipMemcpyAsync(h.data(), task_ovf, 4 * NT, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      const int64_t written = NT - std::count(h.begin(), h.end(), 0x7F7F7F7F);
+      if (written != NT) {
+        if (err) *err = "k_tasks wrote " + std::to_string(written) + " of " + std::to_string(NT) + " task flags";
+        return OTR_DEVICE_ERROR;
+      }
+    }
   }
   te(OTR_STAGE_LINK);
   return OTR_OK;
@@ -1168,10 +1310,21 @@ int Batch::retry_tier(int code, const RouteArgs& rb, unsigned long long* ctr_ban
 // ---- K3/K4: routing + transition costs, the first tiers
 int Batch::route_first() {
   // turn cost tables of this batch's parameters (oracle orc_turn_table)
+  // (uploaded only when the parameters or the buffer changed since this matcher's last batch:
+  // the copy is queued from mat.h_turn, which no later batch touches unless it differs)
   d_turn = need<int32_t>(S_TURN, 181 * OTR_MODES);
-  mat.h_turn.resize(181 * OTR_MODES);
-  for (int m = 0; m < OTR_MODES; ++m) turn_table(mp.m[m].turn_penalty_factor, mat.h_turn.data() + 181 * m);
-  HIPCHK(hipMemcpyAsync(d_turn, mat.h_turn.data(), 4 * 181 * OTR_MODES, hipMemcpyHostToDevice, stream));
+  {
+    int32_t tab[181 * OTR_MODES];
+    for (int m = 0; m < OTR_MODES; ++m) turn_table(mp.m[m].turn_penalty_factor, tab + 181 * m);
+    if (mat.turn_dev != d_turn || mat.h_turn.size() != (size_t)(181 * OTR_MODES) ||
+        memcmp(mat.h_turn.data(), tab, sizeof(tab)) != 0) {
+      mat.turn_dev = nullptr;  // (until the copy is queued)
+      HIPCHK(hipStreamSynchronize(stream));  // (an earlier copy may still read h_turn)
+      mat.h_turn.assign(tab, tab + 181 * OTR_MODES);
+      HIPCHK(hipMemcpyAsync(d_turn, mat.h_turn.data(), sizeof(tab), hipMemcpyHostToDevice, stream));
+      mat.turn_dev = d_turn;
+    }
+  }
   ra.task_list = nullptr;
   ra.n_tasks = NT;
   ra.prev = sb.prev;
@@ -1199,9 +1352,8 @@ int Batch::route_first() {
   for (int m = 0; m < OTR_MODES; ++m) ra.est_v[m] = est_v[m];
   ra.n_tiers = n_est_tiers;
   for (int t = 0; t < n_est_tiers; ++t) ra.tier_keys[t] = est_tier_keys[t];
-  // device-side counters of the retry lists (otr_tiers.h CntWord), then the path bump cursors
-  cnt = need<unsigned long long>(S_MISC, C_CURSORS + kShards);
-  HIPCHK(hipMemsetAsync(cnt, 0, 8 * (C_CURSORS + kShards), stream));
+  // (the device-side counters of the retry lists, otr_tiers.h CntWord, and the path bump
+  // cursors behind them: cnt, in the control block, zero since upload())
   list = need<int64_t>(S_LIST, std::max<int64_t>(NT, S));
   fail_tasks = need<int64_t>(S_GFLAG, std::max<int64_t>(NT, 1));
   flagged = need<int64_t>(S_FLAGGED, std::max<int64_t>(NT, 1));
@@ -1243,9 +1395,8 @@ int Batch::route_first() {
     ra.force_edge = fe ? atoi(fe) : 0;
   }
 #endif
-  // the list tiers' work queues (XcdQueue): 8 counters per launch, 128 B apart
-  queues = need<unsigned long long>(S_QUEUE, kQueues * kQueueWords);
-  HIPCHK(hipMemsetAsync(queues, 0, 8 * kQueues * kQueueWords, stream));
+  // (the list tiers' work queues, XcdQueue: 8 counters per launch, 128 B apart, in the control
+  // block, zero since upload())
   // retry-tier dumps (search_run NDump, otr_edge1.h): per task, the dump slot its search
   // left for the next tier; every tier that fails a task writes it (-1: restart), so the
   // first node tier, which flags every task a retry tier will see, initialises it
@@ -1289,7 +1440,8 @@ int Batch::route_retry() {
   const std::vector<int>& tiers = route_tiers();
   const int ntier = (int)tiers.size();
   // the first tier's flagged tasks, once; every later collect scans only them
-  k_collect_flagged<<<grid_ceil(NT, 1024), 1024, 0, stream>>>(NT, task_ovf, flagged, cnt + C_FLAGGED);
+  k_collect_flagged<<<grid_ceil(NT, kFlaggedBlock * kFlagsPerThread), kFlaggedBlock, 0, stream>>>(
+      NT, task_ovf, flagged, cnt + C_FLAGGED);
   // node dump slots: tier t writes buffer t % 2 and tier t + 1 resumes from it; slots for a
   // quarter of the tasks, at most OTR_NDUMP_GB (4) GB per buffer (C4: 4 % of the 1024-slot
   // searches outgrow it, 10 KB each); beyond them, or without the memory, searches restart
@@ -1514,6 +1666,7 @@ int Batch::paths() {
   if (S > 0) k_fill_i32<<<grid_ceil(S, 256), 256, 0, stream>>>(path_len, S, 0);
   {
     steps = need<int64_t>(S_LIST2, std::max<int64_t>(S, 1));
+    step_ovf = need<int32_t>(S_STEP_OVF, S + 1);  // (zeroed by the step-list kernel)
     nsteps_d = cnt + C_STEPS;
     // the small-search path tier (four searches per wave): steps whose winning route
     // bounds a search of at most OTR_SMALL_PATH_KEYS keys (estimate: 4 x the node density
@@ -1528,7 +1681,6 @@ int Batch::paths() {
     small_paths = small_path_keys > 0.0 && est_k > 0.f && (small_path_keys >= 1e8 || 2 * (NT4 + NT8) >= NT);
     nsteps4_d = cnt + C_STEPS_FRONT;                          // (the front list's count)
     unsigned long long* nall_d = cnt + C_STEPS_ALL;           // (S: the collects' index range)
-    static_assert(C_STEPS_ALL == C_STEPS_FRONT + 1, "cleared together below");
     if (S > 0 && small_paths) {
       PathClass pc{};
       pc.winner = va.winner;
@@ -1540,51 +1692,69 @@ int Batch::paths() {
       pc.turn_modes = turn_modes;
       pc.est4 = 8.f * est_k;  // (est_k = half the node density)
       pc.small_keys = (float)small_path_keys;
-      HIPCHK(hipMemsetAsync(nsteps4_d, 0, 16, stream));
+      // (both counts are zero since upload(): the control block)
       k_step_lists<<<grid_ceil(S, 256), 256, 0, stream>>>(S, sb.prev, va.brk, cb.count, pc, steps, nsteps4_d, nsteps_d,
-                                                          nall_d);
-      if ((rc = read_back(stream, err, fetch(&h_nsteps[0], nsteps4_d), fetch(&h_nsteps[1], nsteps_d)))) return rc;
+                                                          nall_d, step_ovf);
+      if ((rc = post_wait(Matcher::MailRun{nsteps4_d, 1}, Matcher::MailRun{nsteps_d, 1}))) return rc;
+      h_nsteps[0] = mat.mail[0];
+      h_nsteps[1] = mat.mail[1];
     } else if (S > 0) {
-      k_step_list<<<grid_ceil(S, 1024), 1024, 0, stream>>>(S, sb.prev, va.brk, cb.count, steps, nsteps_d);
+      k_step_list<<<grid_ceil(S, 1024), 1024, 0, stream>>>(S, sb.prev, va.brk, cb.count, steps, nsteps_d, step_ovf);
     }
     // the retry collects' index range: every step index (front and back lists), or the list
     nscan_d = small_paths ? nall_d : nsteps_d;
-    step_ovf = need<int32_t>(S_STEP_OVF, S + 1);
-    int64_t capacity = kShards * ((int64_t)S * 24 / kShards + 1024);
-    bool paths_fit = S == 0;
-    for (int attempt = 0; attempt < 8 && S > 0; ++attempt) {
-      if ((rc = paths_attempt(capacity))) return rc;
-      unsigned long long capflag = 0;
-      std::vector<unsigned long long> cur(kShards);
-      HIPCHK(hipMemcpyAsync(&capflag, cnt + C_CAP_FLAG, 8, hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipMemcpyAsync(cur.data(), cnt + C_CURSORS, 8 * kShards, hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      if ((capflag & 0xFFFFFFFFu) == 0) {  // every path fitted its region
+    // OTR_PATH_CAP0 (test knob, read once per process): the first attempt's capacity in entries
+    static const int64_t cap0 = getenv("OTR_PATH_CAP0") ? atoll(getenv("OTR_PATH_CAP0")) : 0;
+    int64_t capacity = cap0 > 0 ? kShards * ((cap0 + kShards - 1) / kShards)
+                                : kShards * ((int64_t)S * 24 / kShards + 1024);
+    // The per-trace output capacities (K7's layout) are queued behind every attempt without
+    // waiting for its cap flag, so the flag, the cursors and the layout's total C come back in
+    // ONE mailbox record and one host wait.  A set flag (never seen outside the tests) grows
+    // the buffer and runs the path kernels, k_capacity and its scan again; the capacities of
+    // the failed attempt are simply overwritten.
+    cap = need<int64_t>(S_CAP, T);
+    cap_off = need<int64_t>(S_CAP_OFF, T + 1);
+    bool paths_fit = false;
+    for (int attempt = 0; attempt < 8; ++attempt) {
+      path_attempts = attempt + 1;
+      if (S > 0 && (rc = paths_attempt(capacity, attempt > 0))) return rc;
+      k_capacity<<<grid_ceil(T, 256), 256, 0, stream>>>(T, trace_state_off, cb.count, path_len, cap);
+      if ((rc = scan(cap, cap_off, T))) return rc;
+      if ((rc = post_wait(Matcher::MailRun{cnt + C_CAP_FLAG, 1}, Matcher::MailRun{cap_off + T, 1},
+                          Matcher::MailRun{cnt + C_CURSORS, kShards})))
+        return rc;
+      if ((mat.mail[0] & 0xFFFFFFFFu) == 0) {  // every path fitted its region (no state: no path, no flag)
+        C = (int64_t)mat.mail[1];
         paths_fit = true;
         break;
       }
       unsigned long long mx = 0;
-      for (auto c : cur) mx = c > mx ? c : mx;
+      for (int q = 0; q < kShards; ++q) mx = std::max(mx, mat.mail[2 + q]);
       capacity = kShards * ((int64_t)mx + (int64_t)mx / 2 + 1024);  // grow and redo
     }
     if (!paths_fit) {  // (the capacity grows 1.5x past the largest shard: never seen)
       if (err) *err = "winner paths did not fit the path buffer after 8 attempts";
       return OTR_DEVICE_ERROR;
     }
+    if (path_attempts > 1 && getenv("OTR_DEBUG_FAIL"))
+      fprintf(stderr, "otr: winner paths regrown: %d attempts, %lld entries\n", path_attempts, (long long)capacity);
   }
   return OTR_OK;
 }
 
 // one run of the path kernels into a buffer of `capacity` entries: the first tiers over the
 // step lists, the retry tiers, the edge-state tiers and the global-memory search
-int Batch::paths_attempt(int64_t capacity) {
+int Batch::paths_attempt(int64_t capacity, bool again) {
   int rc;
   uint32_t* path = need<uint32_t>(S_PATH, capacity);
-  HIPCHK(hipMemsetAsync(step_ovf, 0, 4 * (S + 1), stream));
-  // path tier counts .. cap flag (the words between are the path stage's too)
-  HIPCHK(hipMemsetAsync(cnt + C_PATH_TIER, 0, 8 * (C_CAP_FLAG + 1 - C_PATH_TIER), stream));
-  HIPCHK(hipMemsetAsync(cnt + C_EDGE_PATH, 0, 8 * 2, stream));  // edge-state path tier counts
-  HIPCHK(hipMemsetAsync(cnt + C_CURSORS, 0, 8 * kShards, stream));
+  if (again) {  // (the first attempt finds its words zero: the control block, upload(); the step-list kernel)
+    HIPCHK(hipMemsetAsync(step_ovf, 0, 4 * (S + 1), stream));
+    // path tier counts .. cap flag (the words between are the path stage's too)
+    HIPCHK(hipMemsetAsync(cnt + C_PATH_TIER, 0, 8 * (C_CAP_FLAG + 1 - C_PATH_TIER), stream));
+    HIPCHK(hipMemsetAsync(cnt + C_EDGE_PATH, 0, 8 * 2, stream));  // edge-state path tier counts
+    HIPCHK(hipMemsetAsync(cnt + C_CURSORS, 0, 8 * kShards, stream));
+    HIPCHK(hipMemsetAsync(pq, 0, 8 * 8 * kPQWords, stream));  // the path retry tiers' work queues
+  }
   PathArgs pa{};
   pa.steps = steps;
   pa.n_steps = S;
@@ -1612,10 +1782,7 @@ int Batch::paths_attempt(int64_t capacity) {
   pa.trans_off = trans_off;
   pa.trans = trans;
   pa.force_edge = ra.force_edge;
-  // the path retry tiers' work queues (XcdQueue)
-  constexpr int kPQWords = 16 * 8;
-  unsigned long long* pq = need<unsigned long long>(S_PQUEUE, 8 * kPQWords);
-  HIPCHK(hipMemsetAsync(pq, 0, 8 * 8 * kPQWords, stream));
+  // (the path retry tiers' work queues, XcdQueue: pq, in the control block)
   tb(OTR_STAGE_PATHS);
   if (small_paths) {
     // the front list four searches per wave, the back list two, each grid sized by its
@@ -1692,11 +1859,7 @@ int Batch::paths_attempt(int64_t capacity) {
 // ---- K7..K9: stitching, segments, report(); hour buckets -> histogram; tile rows
 int Batch::segments() {
   int rc;
-  int64_t* cap = need<int64_t>(S_CAP, T);
-  cap_off = need<int64_t>(S_CAP_OFF, T + 1);
-  k_capacity<<<grid_ceil(T, 256), 256, 0, stream>>>(T, trace_state_off, cb.count, path_len, cap);
-  if ((rc = scan(cap, cap_off, T))) return rc;
-  if ((rc = read_i64(cap_off + T, &C))) return rc;
+  // (the capacity layout cap_off and its total C: paths(), with the path stage's host wait)
   sa.b = b;
   sa.trace_state_off = trace_state_off;
   sa.state_probe = state_probe;
@@ -1721,7 +1884,10 @@ int Batch::segments() {
   sa.gstart = need<int32_t>(S_GSTART, C);
   sa.cap_off = cap_off;
   sa.route = need<uint32_t>(S_ROUTE, C);
-  sa.route_n = need<int64_t>(S_ROUTE_N, T);
+  // the four per-trace output counts in one slab, the folded counters and the two fail
+  // counts behind them: drain() brings it over with one copy
+  int64_t* counts = need<int64_t>(S_ROUTE_N, 4 * (size_t)T + n_ctr + 2);
+  sa.route_n = counts;
   sa.seg_id = need<unsigned long long>(S_SEG_ID, C);
   sa.seg_start = need<double>(S_SEG_START, C);
   sa.seg_end = need<double>(S_SEG_END, C);
@@ -1731,10 +1897,10 @@ int Batch::segments() {
   sa.seg_bshape = need<int32_t>(S_SEG_BSHAPE, C);
   sa.seg_eshape = need<int32_t>(S_SEG_ESHAPE, C);
   sa.seg_index = need<uint32_t>(S_SEG_INDEX, C);
-  sa.seg_n = need<int64_t>(S_SEG_N, T);
+  sa.seg_n = counts + T;
   sa.seg_way_n = need<int64_t>(S_SEG_WAY_N, C);
   sa.seg_way = need<uint32_t>(S_SEG_WAY, C);
-  sa.way_n = need<int64_t>(S_WAY_N, T);
+  sa.way_n = counts + 3 * (size_t)T;
   sa.rep_id = need<unsigned long long>(S_REP_ID, C);
   sa.rep_next = need<unsigned long long>(S_REP_NEXT, C);
   sa.rep_t0 = need<double>(S_REP_T0, C);
@@ -1742,7 +1908,7 @@ int Batch::segments() {
   sa.rep_length = need<int32_t>(S_REP_LEN, C);
   sa.rep_queue = need<int32_t>(S_REP_QUEUE, C);
   sa.rep_seg = need<uint32_t>(S_REP_SEG, C);
-  sa.rep_n = need<int64_t>(S_REP_N, T);
+  sa.rep_n = counts + 2 * (size_t)T;
   sa.shape_used = need<int32_t>(S_SHAPE_USED, T);
   sa.stats = need<int32_t>(S_STATS, 7 * (size_t)T);
   sa.stats_len = need<double>(S_STATS_LEN, 2 * (size_t)T);
@@ -2059,17 +2225,28 @@ int Matcher::edge_observations(int quantisation, otr_hist_entry** d_entries, int
 // the work counters folded, the counts of what no tier could search and the per-trace
 // output counts: one host wait per batch for all of them
 int Batch::drain() {
-  hc.resize(n_ctr);
-  k_ctr_fold<<<(unsigned)n_ctr, kCShards, 0, stream>>>(d_counters, d_counters + kBanks * bank);
-  HIPCHK(hipMemcpyAsync(hc.data(), d_counters + kBanks * bank, n_ctr * 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(&h_fail[0], cnt + C_TASKS_LEFT, 8, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(&h_fail[1], cnt + C_PATHS_LEFT, 8, hipMemcpyDeviceToHost, stream));
-  route_n.resize(T), seg_n.resize(T), way_n.resize(T), rep_n.resize(T);
-  HIPCHK(hipMemcpyAsync(route_n.data(), sa.route_n, 8 * T, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(seg_n.data(), sa.seg_n, 8 * T, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(rep_n.data(), sa.rep_n, 8 * T, hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(way_n.data(), sa.way_n, 8 * T, hipMemcpyDeviceToHost, stream));
+  // the slab of segments(): {route_n, seg_n, rep_n, way_n}[T], then the folded counters (k_ctr_fold
+  // stores them there) and the two fail counts (k_post): one copy into the matcher's pinned buffer
+  const size_t words = 4 * (size_t)T + n_ctr + 2;
+  unsigned long long* slab = (unsigned long long*)sa.route_n;
+  k_ctr_fold<<<(unsigned)n_ctr, kCShards, 0, stream>>>(d_counters, slab + 4 * (size_t)T);
+  if (int rc = mat.post({Matcher::MailRun{cnt + C_TASKS_LEFT, 1}, Matcher::MailRun{cnt + C_PATHS_LEFT, 1}},
+                        slab + 4 * (size_t)T + n_ctr, err))
+    return rc;
+  if (mat.h_drain_words < words) {
+    if (mat.h_drain) (void)hipHostFree(mat.h_drain);
+    mat.h_drain = nullptr;
+    mat.h_drain_words = 0;
+    HIPCHK(hipHostMalloc((void**)&mat.h_drain, 8 * (words + words / 4), hipHostMallocDefault));
+    mat.h_drain_words = words + words / 4;
+  }
+  HIPCHK(hipMemcpyAsync(mat.h_drain, slab, 8 * words, hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
+  const int64_t* h = (const int64_t*)mat.h_drain;
+  route_n = h, seg_n = h + T, rep_n = h + 2 * (size_t)T, way_n = h + 3 * (size_t)T;
+  hc = mat.h_drain + 4 * (size_t)T;
+  h_fail[0] = hc[n_ctr];
+  h_fail[1] = hc[n_ctr + 1];
   return OTR_OK;
 }
 
@@ -2231,8 +2408,18 @@ int Batch::copy_out() {
   ca.seg_off = seg_off;
   ca.way_off = way_off;
   ca.rep_off = rep_off;
+  // K7's arguments for k_compact: uploaded from pinned memory (the mailbox: the stream is idle
+  // since drain()), and only when they or their buffer changed since this matcher's last upload
   SegArgs* d_sa = need<SegArgs>(S_C_ARGS, 1);
-  HIPCHK(hipMemcpyAsync(d_sa, &sa, sizeof(SegArgs), hipMemcpyHostToDevice, stream));
+  static_assert(sizeof(SegArgs) <= 8 * Matcher::kMailWords, "SegArgs goes through the mailbox");
+  if (mat.seg_args_dev != d_sa || mat.seg_args.size() != sizeof(SegArgs) ||
+      memcmp(mat.seg_args.data(), &sa, sizeof(SegArgs)) != 0) {
+    mat.seg_args_dev = nullptr;
+    mat.seg_args.assign((const char*)&sa, (const char*)&sa + sizeof(SegArgs));
+    memcpy(mat.mail, &sa, sizeof(SegArgs));
+    HIPCHK(hipMemcpyAsync(d_sa, mat.mail, sizeof(SegArgs), hipMemcpyHostToDevice, stream));
+    mat.seg_args_dev = d_sa;
+  }
   ca.s = d_sa;
   auto n1 = [](int64_t n) { return (size_t)(n > 0 ? n : 1); };
   ca.route = need<uint32_t>(S_C_ROUTE, n1(nroute));

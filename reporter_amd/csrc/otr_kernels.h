@@ -1560,7 +1560,7 @@ struct TaskArgs {
   const int64_t* ntask8;      // tiny-tier steps' task counts, or null
   const int64_t* task8_off;   // their exclusive offsets: tiny-tier tasks are [0, nt8)
   int64_t nt8;
-  int32_t* flag_turn;         // per task: 5 for a turn-mode task (the first edge-state tier's list), or null
+  int32_t* flag_turn;         // per task: 5 for a turn-mode task (the first edge-state tier's list), else 0; or null
   // the two-search first tier's size estimate (RouteArgs est_*): a node-mode step whose
   // estimated keys exceed est_first_keys (0: no estimate) starts in a retry tier
   int est_first_keys;
@@ -1646,7 +1646,8 @@ __global__ __launch_bounds__(256) void k_tasks(TaskArgs a) {
   const uint32_t meta = (uint32_t)a.cand_count[s] | ((uint32_t)md << 8) | ((a.forced[s] ? 1u : 0u) << 10) |
                         (sh << 11) | ((general ? 1u : 0u) << 16) | (turn << 17) | (pre << 18);
   const int64_t to = a.trans_off[s];
-  if (turn && a.flag_turn) a.flag_turn[o] = 5;  // the edge-state tiers (otr_edge1.h)
+  // 5: the edge-state tiers (otr_edge1.h); 0 otherwise, so the flags need no fill beforehand
+  if (a.flag_turn) a.flag_turn[o] = turn ? 5 : 0;
   a.rec[3 * o] = make_uint4((uint32_t)s, (uint32_t)sp, root, bmm);
   a.rec[3 * o + 1] = make_uint4(d0min, meta, (uint32_t)same, (uint32_t)(same >> 32));
   a.rec[3 * o + 2] = make_uint4(0u, (uint32_t)bt, (uint32_t)to, (uint32_t)((uint64_t)to >> 32));

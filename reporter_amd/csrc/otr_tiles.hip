@@ -114,8 +114,12 @@ int Matcher::cull_device(const otr_tile_row* d_in, int64_t n, int privacy, int r
 }
 
 // ---- keyed speed histogram (include/otr.h otr_hist_reduce) -----------------
-__global__ void k_rows_to_entries(const otr_tile_row* r, int64_t n, otr_hist_entry* e) {
+struct EntryRange;
+__device__ inline void entry_range_init(EntryRange* rng);
+// (the first thread also starts the key ranges k_entry_range folds into, the next launch)
+__global__ void k_rows_to_entries(const otr_tile_row* r, int64_t n, otr_hist_entry* e, EntryRange* rng) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) entry_range_init(rng);
   if (i >= n) return;
   otr_hist_entry x;
   x.file = r[i].file;
@@ -132,6 +136,9 @@ __global__ void k_rows_to_entries(const otr_tile_row* r, int64_t n, otr_hist_ent
 struct EntryRange {
   unsigned long long id_or, next_or, file_or, bmin, bmax, foreign;
 };
+__device__ inline void entry_range_init(EntryRange* rng) { *rng = EntryRange{0ull, 0ull, 0ull, ~0ull, 0ull, 0ull}; }
+// entries given as such: no conversion kernel to start the ranges in
+__global__ void k_entry_range_init(EntryRange* rng) { entry_range_init(rng); }
 // a fixed grid (kRangeBlocks x 1024) strides over the entries; one set of atomics per
 // block (one per wave queued ~23K atomics on a single line: 263 us for 244K entries)
 constexpr int kRangeBlocks = 128;
@@ -174,11 +181,14 @@ __global__ __launch_bounds__(1024) void k_entry_range(const otr_hist_entry* e, i
 static int bit_width(unsigned long long v) { return v ? 64 - __builtin_clzll(v) : 0; }
 // sort key of one LSD pass: 0 file, 1 id, 2 next id, 3 speed bin, 4 next id << 3 | bin,
 // 5 (bucket - bmin) << 46 | level << 43 | tile << 21 | index (K9 files, 46-bit ids)
+// (iota non-null: the first pass, over the entries as they came; it also writes that identity
+// permutation, the values of the first sort)
 __global__ void k_entry_key(const otr_hist_entry* e, const int32_t* perm, int64_t n, int field,
-                            unsigned long long bmin, unsigned long long* key) {
+                            unsigned long long bmin, unsigned long long* key, int32_t* iota) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const otr_hist_entry& x = e[perm[i]];
+  if (iota) iota[i] = (int32_t)i;
+  const otr_hist_entry& x = e[iota ? i : perm[i]];
   unsigned long long k;
   switch (field) {
     case 0: k = x.file; break;
@@ -192,9 +202,19 @@ __global__ void k_entry_key(const otr_hist_entry* e, const int32_t* perm, int64_
   }
   key[i] = k;
 }
-__global__ void k_gather_entries(const otr_hist_entry* in, const int32_t* idx, int64_t n, otr_hist_entry* out) {
+// the entries in sorted order, and their run heads by the full key (k_entry_heads' pair = 0)
+__global__ void k_gather_entries(const otr_hist_entry* in, const int32_t* idx, int64_t n, otr_hist_entry* out,
+                                 int64_t* head) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = in[idx[i]];
+  if (i >= n) return;
+  const otr_hist_entry b = in[idx[i]];
+  out[i] = b;
+  bool h = i == 0;
+  if (!h) {
+    const otr_hist_entry& a = in[idx[i - 1]];
+    h = a.file != b.file || a.id != b.id || a.next_id != b.next_id || a.speed_bin != b.speed_bin;
+  }
+  head[i] = h ? 1 : 0;
 }
 // run heads over sorted entries: pair = 0 the full key, 1 the (file, id, next_id) pair
 __global__ void k_entry_heads(const otr_hist_entry* e, int64_t n, int pair, int64_t* head) {
@@ -207,10 +227,13 @@ __global__ void k_entry_heads(const otr_hist_entry* e, int64_t n, int pair, int6
   }
   head[i] = h ? 1 : 0;
 }
-__global__ void k_entry_counts(const otr_hist_entry* e, int64_t n, int64_t* c) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) c[i] = e[i].count;
-}
+// the two columns scanned together over sorted entries (otr_devscan.h tuple_sums): the run head
+// flags and the entries' counts, read from the entries themselves
+struct HeadCountColumns {
+  const int64_t* head;
+  const otr_hist_entry* e;
+  __host__ __device__ int64_t operator()(int q, int64_t i) const { return q == 0 ? head[i] : (int64_t)e[i].count; }
+};
 // the last entry of every run carries its run's count sum: csum = inclusive scan of counts,
 // run r spans [start_r, next start); out[r] = entry at start_r with count = the sum
 __global__ void k_entry_reduce(const otr_hist_entry* e, int64_t n, const int64_t* run_start, int64_t n_runs,
@@ -253,9 +276,14 @@ __device__ inline void pf_add(PairFile& T, unsigned long long s, unsigned long l
     T.t2 = t;
   }
 }
-__global__ void k_pair_file_heads(const otr_hist_entry* e, const int64_t* pair_start, int64_t n_pairs, int64_t* head) {
+// (the number of pairs is still on the device, *n_pairs <= n_max: the launch covers n_max and
+// writes zeros behind the pairs, so the scan over n_max ends at the number of files and both
+// counts reach the host with one wait)
+__global__ void k_pair_file_heads(const otr_hist_entry* e, const int64_t* pair_start, const int64_t* n_pairs,
+                                  int64_t n_max, int64_t* head) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p < n_pairs) head[p] = p == 0 || e[pair_start[p]].file != e[pair_start[p - 1]].file ? 1 : 0;
+  if (p >= n_max) return;
+  head[p] = p < *n_pairs && (p == 0 || e[pair_start[p]].file != e[pair_start[p - 1]].file) ? 1 : 0;
 }
 // every pair's string-order keys (dec_key of id and next id) and total, one thread per
 // pair: the per-file reduction below then only compares
@@ -348,43 +376,64 @@ int Matcher::hist_reduce(const void* in, int64_t n, int memory, int rows_in, int
     int rc;
     Workspace tmp;
     if ((rc = scan_sort_bytes(head, pos, key_a, key_b, perm_a, perm_b, ni, &tmp.bytes, stream, err))) return rc;
+    {
+      Workspace q;
+      int64_t* const two[2] = {pos, csum};
+      if ((rc = tuple_sums<2>(&q, HeadCountColumns{head, e_sorted}, two, ni, stream, err))) return rc;
+      tmp.bytes = std::max(tmp.bytes, q.bytes);
+    }
     tmp.p = need<char>(S_SORT_TMP, tmp.bytes);
     const hipMemcpyKind kind = memory == OTR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (rows_in) {
-      otr_tile_row* rows = need<otr_tile_row>(S_ROWS_IN, n);
-      HIPCHK(hipMemcpyAsync(rows, in, sizeof(otr_tile_row) * n, kind, stream));
-      k_rows_to_entries<<<grid_ceil(n, 256), 256, 0, stream>>>(rows, n, e_in);
+      // rows already in device memory are read where they are (once, and only read)
+      const otr_tile_row* rows = (const otr_tile_row*)in;
+      if (memory != OTR_MEM_DEVICE) {
+        otr_tile_row* staged = need<otr_tile_row>(S_ROWS_IN, n);
+        HIPCHK(hipMemcpyAsync(staged, in, sizeof(otr_tile_row) * n, kind, stream));
+        rows = staged;
+      }
+      k_rows_to_entries<<<grid_ceil(n, 256), 256, 0, stream>>>(rows, n, e_in, rng);
     } else {
       HIPCHK(hipMemcpyAsync(e_in, in, sizeof(otr_hist_entry) * n, kind, stream));
+      k_entry_range_init<<<1, 1, 0, stream>>>(rng);
     }
     // LSD over (file, id, next_id, speed_bin), stable passes over a permutation, each only
     // as wide as the keys' range: typically two passes of ~49 bits (next id and bin) and
-    // ~47 bits (hour offset and the id in file order), instead of 3 + 3 x 64 bits
-    EntryRange hr{0ull, 0ull, 0ull, ~0ull, 0ull, 0ull};
-    HIPCHK(hipMemcpyAsync(rng, &hr, sizeof(hr), hipMemcpyHostToDevice, stream));
+    // ~47 bits (hour offset and the id in file order), instead of 3 + 3 x 64 bits.  (At ~250K
+    // pairs hipcub sorts each pass with a block sort and merge levels, 17 launches; rocprim's
+    // one-sweep radix passes, 9 launches, and one merge sort of the 32-byte entries under their
+    // full key were both measured slower: DESIGN.md §6u2.)
+    // (the host reads of this call, the ranges and the four counts, come through the matcher's
+    // pinned mailbox: otr_engine.h)
+    static_assert(sizeof(EntryRange) == 6 * 8, "six mailbox words");
     k_entry_range<<<(unsigned)std::min<int64_t>(kRangeBlocks, (n + 1023) / 1024), 1024, 0, stream>>>(e_in, n, rng);
-    if ((rc = read_back(stream, err, fetch(&hr, rng)))) return rc;
+    if ((rc = post_wait({MailRun{rng, 6}}, err))) return rc;
+    EntryRange hr;
+    memcpy(&hr, mail, sizeof(hr));
     std::vector<std::pair<int, int>> passes;  // (field, end bit), least significant first
     const int wn = bit_width(hr.next_or), wi = bit_width(hr.id_or), ws = bit_width(hr.bmax - hr.bmin);
     if (wn + 3 <= 64) passes.push_back({4, wn + 3});
     else passes.insert(passes.end(), {{3, 3}, {2, wn}});
     if (!hr.foreign && wi <= 46 && ws + 46 <= 64) passes.push_back({5, std::max(46 + ws, 1)});
     else passes.insert(passes.end(), {{1, std::max(wi, 1)}, {0, std::max(bit_width(hr.file_or), 1)}});
-    k_iota<int32_t><<<grid_ceil(n, 256), 256, 0, stream>>>(perm_a, n);
+    bool first = true;
     for (const auto& ps : passes) {
-      k_entry_key<<<grid_ceil(n, 256), 256, 0, stream>>>(e_in, perm_a, n, ps.first, hr.bmin, key_a);
+      k_entry_key<<<grid_ceil(n, 256), 256, 0, stream>>>(e_in, perm_a, n, ps.first, hr.bmin, key_a,
+                                                         first ? perm_a : nullptr);
+      first = false;
       if ((rc = sort_pairs(tmp, key_a, key_b, perm_a, perm_b, ni, 0, ps.second, stream, err))) return rc;
       std::swap(perm_a, perm_b);
     }
-    k_gather_entries<<<grid_ceil(n, 256), 256, 0, stream>>>(e_in, perm_a, n, e_sorted);
-    // runs of equal keys -> one entry each, counts summed
-    k_entry_heads<<<grid_ceil(n, 256), 256, 0, stream>>>(e_sorted, n, 0, head);
-    if ((rc = inclusive_sum(tmp, head, pos, ni, stream, err))) return rc;
+    // runs of equal keys -> one entry each, counts summed: the sorted entries with their run
+    // heads, then the head positions and the count sums in one scan
+    k_gather_entries<<<grid_ceil(n, 256), 256, 0, stream>>>(e_in, perm_a, n, e_sorted, head);
+    {
+      int64_t* const two[2] = {pos, csum};
+      if ((rc = tuple_sums<2>(&tmp, HeadCountColumns{head, e_sorted}, two, ni, stream, err))) return rc;
+    }
     k_scatter_index<int64_t><<<grid_ceil(n, 256), 256, 0, stream>>>(head, pos, n, rstart);
-    k_entry_counts<<<grid_ceil(n, 256), 256, 0, stream>>>(e_sorted, n, head);  // head reused: counts
-    if ((rc = inclusive_sum(tmp, head, csum, ni, stream, err))) return rc;
-    int64_t nr = 0;
-    if ((rc = read_back(stream, err, fetch(&nr, pos + (n - 1))))) return rc;
+    if ((rc = post_wait({MailRun{pos + (n - 1), 1}}, err))) return rc;
+    const int64_t nr = (int64_t)mail[0];
     if (nr < 1 || nr > n) {
       if (err) *err = "histogram run split failed";
       return OTR_DEVICE_ERROR;
@@ -396,32 +445,37 @@ int Matcher::hist_reduce(const void* in, int64_t n, int memory, int rows_in, int
       // pairs over the reduced entries: heads, totals, keep flags, compaction
       const int nri = (int)nr;
       k_entry_heads<<<grid_ceil(nr, 256), 256, 0, stream>>>(e_red, nr, 1, head);
-      if ((rc = inclusive_sum(tmp, head, pos, nri, stream, err))) return rc;
+      {
+        int64_t* const two[2] = {pos, csum};
+        if ((rc = tuple_sums<2>(&tmp, HeadCountColumns{head, e_red}, two, nri, stream, err))) return rc;
+      }
       k_scatter_index<int64_t><<<grid_ceil(nr, 256), 256, 0, stream>>>(head, pos, nr, rstart);
-      int64_t np = 0;
-      HIPCHK(hipMemcpyAsync(&np, pos + (nr - 1), 8, hipMemcpyDeviceToHost, stream));
-      k_entry_counts<<<grid_ceil(nr, 256), 256, 0, stream>>>(e_red, nr, head);
-      if ((rc = inclusive_sum(tmp, head, csum, nri, stream, err))) return rc;
-      HIPCHK(hipStreamSynchronize(stream));
-      // per file: the string-last and string-second pairs (the reference loop's trailing run)
-      int64_t* fidx = need<int64_t>(S_HE_FIDX, std::max<int64_t>(np, 1));
-      int64_t* fhead = need<int64_t>(S_HE_FHEAD, std::max<int64_t>(np, 1));
-      k_pair_file_heads<<<grid_ceil(np, 256), 256, 0, stream>>>(e_red, rstart, np, fhead);
-      if ((rc = inclusive_sum(tmp, fhead, fidx, (int)np, stream, err))) return rc;
-      int64_t nf = 0;
-      if ((rc = read_back(stream, err, fetch(&nf, fidx + (np - 1))))) return rc;
+      // per file: the string-last and string-second pairs (the reference loop's trailing run).
+      // The file heads and their scan run over nr >= np slots, so np needs no wait of its own:
+      // it comes back with nf.
+      int64_t* fidx = need<int64_t>(S_HE_FIDX, nr);
+      int64_t* fhead = need<int64_t>(S_HE_FHEAD, nr);
+      k_pair_file_heads<<<grid_ceil(nr, 256), 256, 0, stream>>>(e_red, rstart, pos + (nr - 1), nr, fhead);
+      if ((rc = inclusive_sum(tmp, fhead, fidx, nri, stream, err))) return rc;
+      if ((rc = post_wait({MailRun{pos + (nr - 1), 1}, MailRun{fidx + (nr - 1), 1}}, err))) return rc;
+      const int64_t np = (int64_t)mail[0], nf = (int64_t)mail[1];
+      if (np < 1 || np > nr || nf < 1 || nf > np) {
+        if (err) *err = "histogram pair split failed";
+        return OTR_DEVICE_ERROR;
+      }
       PairFile* pf = need<PairFile>(S_HE_PFILE, std::max<int64_t>(nf, 1));
       int64_t* ffirst = need<int64_t>(S_HE_FFIRST, std::max<int64_t>(nf, 1));
       PairKey* pkey = need<PairKey>(S_HE_PKEY, std::max<int64_t>(np, 1));
       k_scatter_index<int64_t><<<grid_ceil(np, 256), 256, 0, stream>>>(fhead, fidx, np, ffirst);
       k_pair_keys<<<grid_ceil(np, 256), 256, 0, stream>>>(e_red, rstart, np, nr, csum, pkey);
       k_pair_file_top2<<<(unsigned)nf, 1024, 0, stream>>>(pkey, np, ffirst, nf, pf);
-      int64_t* keep = head;  // counts no longer needed
+      int64_t* keep = head;  // the pair heads are no longer needed
       k_entry_keep<<<grid_ceil(nr, 256), 256, 0, stream>>>(pos, nr, pkey, fidx, pf, privacy, keep);
       int64_t* kpos = rstart;  // pair starts no longer needed after k_entry_keep
       if ((rc = inclusive_sum(tmp, keep, kpos, nri, stream, err))) return rc;
       k_scatter_flagged<otr_hist_entry><<<grid_ceil(nr, 256), 256, 0, stream>>>(e_red, keep, kpos, nr, e_out);
-      if ((rc = read_back(stream, err, fetch(&nres, kpos + (nr - 1))))) return rc;
+      if ((rc = post_wait({MailRun{kpos + (nr - 1), 1}}, err))) return rc;
+      nres = (int64_t)mail[0];
       result = e_out;
     }
     HIPCHK(hipGetLastError());

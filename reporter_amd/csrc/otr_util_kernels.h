@@ -34,4 +34,23 @@ __global__ void k_scatter_index(const int64_t* flag, const int64_t* pos, int64_t
   if (i < n && flag[i]) out[pos[i] - 1] = (Out)i;
 }
 
+// The scalars the host reads after a stage, gathered into one record of 8-byte words: up to
+// eight runs src[q][0, n[q]) stored back to back at dst.  dst is the matcher's pinned mailbox
+// (mapped host memory: the host reads it after the stream wait, no copy operation at all) or a
+// device slab that one copy brings over.  One block.
+constexpr int kPostRuns = 8;
+struct PostArgs {
+  const unsigned long long* src[kPostRuns];
+  int n[kPostRuns];
+  unsigned long long* dst;
+};
+template <int RUNS = kPostRuns>
+__global__ void k_post(PostArgs a) {
+  int o = 0;
+  for (int q = 0; q < RUNS; ++q) {
+    for (int i = threadIdx.x; i < a.n[q]; i += blockDim.x) a.dst[o + i] = a.src[q][i];
+    o += a.n[q];
+  }
+}
+
 }  // namespace otr
