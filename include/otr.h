@@ -148,7 +148,11 @@ typedef struct otr_tile_row {
   int32_t duration;    /* int(round(t1 - t0)), Python 2 rounding (:179) */
   int32_t length;
   int32_t queue_length;
-  int32_t speed_bin;   /* min(int(length / (t1 - t0) * 3.6 / 20), 7): the report's 20 km/h speed bin */
+  int32_t speed_bin;   /* min(int(length / (t1 - t0) * 3.6 / 20), 7): the report's 20 km/h speed bin;
+                          -1 in a row read back from a tile file's text (otr_tiles_parse below): the
+                          text holds floor(t0), ceil(t1) and the rounded duration, not t0 and t1, so
+                          the bin cannot be recovered.  The cull's two orders and the file texts
+                          never read it. */
 } otr_tile_row;
 #define OTR_INVALID_SEGMENT_ID 0x3fffffffffffull
 
@@ -346,7 +350,9 @@ typedef struct otr_hist_entry {
  * summing counts; with privacy > 1 also drop the (file, id, next_id) pairs whose total
  * count is below privacy.  The reduced entries, in key order, are copied to `out`
  * (out_memory: host or device; room for out_cap entries, n suffices) and *n_out is
- * their number.  rows_in != 0: the input is n tile rows, count 1 each. */
+ * their number.  rows_in != 0: the input is n tile rows, count 1 each; rows read back from
+ * tile file texts (otr_tiles_parse) carry speed_bin -1 and have no place in a speed histogram:
+ * they would all land in the one bin 0xFFFFFFFF. */
 int otr_hist_reduce(otr_matcher* m, const void* in, int64_t n, int32_t memory, int32_t rows_in, int32_t privacy,
                     otr_hist_entry* out, int64_t out_cap, int32_t out_memory, int64_t* n_out);
 
@@ -912,6 +918,96 @@ int otr_tiles_text(otr_matcher* m, const otr_tile_row* rows, int64_t n, int32_t 
  * store returns zero files and no text. */
 int otr_tile_store_flush_text(otr_matcher* m, const char* source, const char* mode, int32_t flags,
                               otr_tile_flush_result* flush, otr_tile_text_result* out);
+
+/* ---- tile file texts read back: payload bytes to rows in HBM -------
+ * The inverse of otr_tiles_text, for simple_reporter.py --match-dir (report(), :211-254, reads the
+ * tile files match() appended to a directory earlier, :199-206): the byte buffer of many tile
+ * files with their names and offsets, in the shape otr_tile_text_result has, to otr_tile_row
+ * records in HBM grouped by file, every line that is not a row named with its reason.
+ *
+ * THE RULE: a line becomes a row if and only if writing that row back (otr_tiles_format, the
+ * same rules, source and mode) reproduces the line's bytes; a file name is accepted if and only
+ * if it is the name otr_tiles_text gives the resulting `file` value at the caller's quantisation
+ * without wrapping modulo 2^64.  Nothing is approximated: a numeral that is not the canonical
+ * decimal ("01", "+1", "-0", " 1", "1.0") would sort elsewhere in the reference than its row does
+ * here, and a line the reference would carry through as opaque text but a row cannot express is
+ * counted and reported, never turned into a row.  (A source or mode that holds a ',' gives lines
+ * of more than 10 fields: they are OTR_TILE_LINE_U_FIELDS.)
+ *
+ * Lines.  File f is T = text[text_off[f] .. text_off[f+1]), split at every '\n' into pieces
+ * p0..pk; an empty T has no line.  With H the column line of otr_tiles_text:
+ *   OTR_TILE_RULES_SIMPLE (line = piece "\n"): p0..p(k-1) are lines, pk only if it is not empty,
+ *     and then it is an unterminated final line (U_END: ''.join(segments), :253, would glue it to
+ *     its successor after the sort).  H is optional: write_tiles and the uploaded bodies have it,
+ *     the reference's match-dir files do not.
+ *   OTR_TILE_RULES_STREAM (row = "\n" piece): p0..pk are all lines, p0 must be H, and an empty
+ *     piece (one left by a trailing "\n" included) is a line and is bad.
+ * A p0 that equals H is OTR_TILE_LINE_HEADER; H anywhere else is U_HEADER.  Line indices are
+ * global over the files in order, headers included.  The first status that applies, in the order
+ * of the values below, is a line's status, except that every line of a file whose name was
+ * refused is U_NAME (its lines are not parsed).  Values >= OTR_TILE_LINE_UNSUPPORTED mean "the
+ * reference would carry this line; rows cannot". */
+#define OTR_TILE_LINE_ROW 0        /* became a row */
+#define OTR_TILE_LINE_HEADER 1     /* the column line, first of its file: skipped */
+#define OTR_TILE_LINE_E_FIELDS 2   /* fewer than 2 comma-separated fields (the empty line included):
+                                      report() raises IndexError (:224-227) and the file is lost */
+#define OTR_TILE_LINE_UNSUPPORTED 32
+#define OTR_TILE_LINE_U_NAME 32    /* the file's name was refused */
+#define OTR_TILE_LINE_U_END 33     /* SIMPLE: the final line has no "\n" */
+#define OTR_TILE_LINE_U_HEADER 34  /* the column line misplaced, or missing under STREAM */
+#define OTR_TILE_LINE_U_FIELDS 35  /* not exactly 10 fields */
+#define OTR_TILE_LINE_U_NUMBER 36  /* a numeric field is not the canonical decimal ("-"? then digits,
+                                      no leading zero, no "-0") of a value its row member holds: id and
+                                      next_id uint64 without sign, duration, length and queue_length
+                                      int32, start and end int64 (an empty next_id is U_NEXT's) */
+#define OTR_TILE_LINE_U_NEXT 37    /* next_id empty under SIMPLE, or spelled 70368744177663 under STREAM
+                                      (otr_tiles_text leaves it out there; empty under STREAM is
+                                      OTR_INVALID_SEGMENT_ID) */
+#define OTR_TILE_LINE_U_COUNT 38   /* the fourth field is not "1" */
+#define OTR_TILE_LINE_U_TAG 39     /* source or vehicle_type is not byte-equal to the caller's source and
+                                      upper-cased mode (a "\r" before the newline lands here) */
+
+/* The input: otr_tiles_text's output shape.  A name is "{a}_{b}/{level}/{tile}", four canonical
+ * unsigned decimals with a % q == 0, b == a + q - 1, a / q < 2^39, level <= 7, tile < 2^22 (q the
+ * quantisation); no directory prefix. */
+typedef struct otr_tile_texts {
+  const uint8_t* text;  const int64_t* text_off;   /* n_files + 1, ascending from 0 */
+  const uint8_t* names; const int64_t* name_off;   /* n_files + 1, ascending from 0 */
+  int32_t n_files, memory;                         /* OTR_MEM_*: one memory for all four */
+} otr_tile_texts;
+
+/* Rows are grouped by file in line order: file f's are rows[row_off[f] .. row_off[f+1]), each with
+ * `file` = file[f] (from the name alone: the reference never compares the ids with the path
+ * either) and speed_bin -1.  A file whose name was refused has file[f] = OTR_NO_ID,
+ * file_status[f] = 1 and no rows.  Lines file_line_off[f] .. file_line_off[f+1]-1 are file f's.
+ * first_bad: the lowest line with a status >= OTR_TILE_LINE_E_FIELDS (-1, -1, 0: none).  Host copies
+ * unless OTR_TILE_PARSE_NO_HOST, device copies always; all owned by the matcher until its next
+ * otr_tiles_parse: they survive otr_tiles_cull, otr_tiles_text and the tile store calls, so
+ * d_rows can go to any of them with OTR_MEM_DEVICE. */
+typedef struct otr_tile_parse_result {
+  int64_t n_lines, n_rows, n_headers, n_bad, n_bad_names;
+  int64_t first_bad;  int32_t first_bad_file, first_bad_reason;
+  float device_ms;  int32_t n_files;
+  const otr_tile_row* rows;    const int64_t* row_off;       /* n_rows, n_files + 1 */
+  const uint64_t* file;        const uint8_t* file_status;   /* n_files */
+  const int64_t* file_line_off;                              /* n_files + 1 */
+  const uint8_t* line_status;                                /* n_lines: OTR_TILE_LINE_* */
+  const otr_tile_row* d_rows;  const int64_t* d_row_off;
+  const uint64_t* d_file;      const uint8_t* d_file_status;
+  const int64_t* d_file_line_off;
+  const uint8_t* d_line_status;
+} otr_tile_parse_result;
+
+#define OTR_TILE_PARSE_NO_HOST 1   /* leave the host pointers null: device copies only */
+
+/* Device text is read where the caller's pointers say (one device-to-device copy pads it to whole
+ * 16-byte chunks, as otr_ingest does), never through the host.  OTR_BAD_REQUEST, with the previous
+ * result left as it was, for quantisation < 1, unknown rules, a source or mode longer than 255
+ * bytes, n_files < 0, offsets that do not ascend from 0, and sizes beyond otr_ingest's: text of
+ * 2^40 bytes or of 2^31 - 1 sixteen-byte chunks, or 2^31 - 1 lines.  Everything else is decided per
+ * line and per file; n_files == 0 gives zero lines. */
+int otr_tiles_parse(otr_matcher* m, const otr_tile_texts* in, int32_t quantisation, int32_t rules,
+                    const char* source, const char* mode, int32_t flags, otr_tile_parse_result* out);
 
 /* ---- tile store: snapshot, restore, Segment.ListSerder records ----
  * The reference keeps the anonymiser's state in two Kafka state stores with changelogs

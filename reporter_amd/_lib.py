@@ -76,7 +76,7 @@ EXPORTS = ['otr_configure', 'otr_configure_json', 'otr_matcher_new', 'otr_matche
            'otr_sessions_restore_records_named', 'otr_tiles_text', 'otr_tile_store_flush_text',
            'otr_tile_store_open_ex', 'otr_tile_store_snapshot', 'otr_tile_store_restore',
            'otr_tile_store_export_records', 'otr_tile_store_restore_records', 'otr_tile_slice_key',
-           'otr_tile_slice_key_parse']
+           'otr_tile_slice_key_parse', 'otr_tiles_parse']
 
 
 class ServiceSplit(ctypes.Structure):
@@ -332,6 +332,52 @@ class TileTextResult(ctypes.Structure):
                  ('reserved2', ctypes.c_int32)] +
                 [(k, ctypes.c_void_p) for k in TILE_TEXT_FIELDS] +
                 [('d_' + k, ctypes.c_void_p) for k in TILE_TEXT_FIELDS])
+
+
+class TileTexts(ctypes.Structure):
+    """otr_tile_texts (include/otr.h): the texts and names of many tile files, K19's output shape."""
+    _fields_ = [('text', ctypes.c_void_p), ('text_off', ctypes.c_void_p), ('names', ctypes.c_void_p),
+                ('name_off', ctypes.c_void_p), ('n_files', ctypes.c_int32), ('memory', ctypes.c_int32)]
+
+
+# the arrays of otr_tile_parse_result, in the struct's order (rows: TILE_ROW records)
+TILE_PARSE_FIELDS = ['rows', 'row_off', 'file', 'file_status', 'file_line_off', 'line_status']
+TILE_PARSE_COUNTS = ['n_lines', 'n_rows', 'n_headers', 'n_bad', 'n_bad_names', 'first_bad', 'first_bad_file',
+                     'first_bad_reason', 'n_files']
+# OTR_TILE_LINE_*
+TILE_LINE = {'ROW': 0, 'HEADER': 1, 'E_FIELDS': 2, 'U_NAME': 32, 'U_END': 33, 'U_HEADER': 34, 'U_FIELDS': 35,
+             'U_NUMBER': 36, 'U_NEXT': 37, 'U_COUNT': 38, 'U_TAG': 39}
+TILE_LINE_NAME = {v: k for k, v in TILE_LINE.items()}
+OTR_TILE_LINE_UNSUPPORTED = 32
+OTR_TILE_PARSE_NO_HOST = 1
+
+
+class TileParseResult(ctypes.Structure):
+    """otr_tile_parse_result (include/otr.h): the rows read back from tile file texts."""
+    _fields_ = ([(k, ctypes.c_int64) for k in TILE_PARSE_COUNTS[:6]] +
+                [('first_bad_file', ctypes.c_int32), ('first_bad_reason', ctypes.c_int32),
+                 ('device_ms', ctypes.c_float), ('n_files', ctypes.c_int32)] +
+                [(k, ctypes.c_void_p) for k in TILE_PARSE_FIELDS] +
+                [('d_' + k, ctypes.c_void_p) for k in TILE_PARSE_FIELDS])
+
+
+def tile_parse_to_numpy(r, host=True):
+    """An otr_tile_parse_result: its counts, device_ms and device pointers d_*, and with host=True
+    copies of rows (TILE_ROW), row_off and file_line_off (int64), file (uint64), file_status and
+    line_status (uint8)."""
+    nf = int(r.n_files)
+    out = {k: int(getattr(r, k)) for k in TILE_PARSE_COUNTS}
+    out['device_ms'] = float(r.device_ms)
+    if host:
+        out['rows'] = _copy(r.rows, int(r.n_rows), TILE_ROW)
+        out['row_off'] = _copy(r.row_off, nf + 1, np.int64)
+        out['file'] = _copy(r.file, nf, np.uint64)
+        out['file_status'] = _copy(r.file_status, nf, np.uint8)
+        out['file_line_off'] = _copy(r.file_line_off, nf + 1, np.int64)
+        out['line_status'] = _copy(r.line_status, int(r.n_lines), np.uint8)
+    for k in TILE_PARSE_FIELDS:
+        out['d_' + k] = int(getattr(r, 'd_' + k) or 0)
+    return out
 
 
 class TileSnapshot(ctypes.Structure):
@@ -634,6 +680,9 @@ def lib():
                                      P(TileTextResult)]
         L.otr_tile_store_flush_text.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32,
                                                 P(TileFlushResult), P(TileTextResult)]
+    if hasattr(L, 'otr_tiles_parse'):
+        L.otr_tiles_parse.argtypes = [ctypes.c_void_p, P(TileTexts), ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p,
+                                      ctypes.c_char_p, ctypes.c_int32, P(TileParseResult)]
     if hasattr(L, 'otr_tile_store_open_ex'):
         L.otr_tile_store_open_ex.argtypes = [ctypes.c_void_p, P(TileStoreConfig), ctypes.c_int32]
         L.otr_tile_store_snapshot.argtypes = [ctypes.c_void_p, ctypes.c_int32, P(TileSnapshot)]

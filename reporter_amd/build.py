@@ -204,6 +204,21 @@ def build_tiletextcheck(force=False, sanitize=False, out=None):
     return exe
 
 
+def build_tileparsecheck(force=False, sanitize=False, out=None):
+    """tools/tileparsecheck: the tile file parser's per-line and per-name rules and its line table
+    as a stand-alone host program (CPU tests only).  sanitize=True: built with AddressSanitizer and
+    UndefinedBehaviorSanitizer (any report is fatal), to `out` or tools/tileparsecheck_san."""
+    src = os.path.join(PKG, 'tools', 'tileparsecheck.cpp')
+    exe = out or os.path.join(PKG, 'tools', 'tileparsecheck_san' if sanitize else 'tileparsecheck')
+    deps = [src, os.path.join(ROOT, 'include', 'otr.h')]
+    deps += [os.path.join(CSRC, f) for f in ('otr_tileparse.h', 'otr_tiletext.h')]
+    if force or not _newer(exe, deps):
+        flags = ['-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
+                 '-fno-omit-frame-pointer'] if sanitize else ['-O2']
+        _run(['g++', '-std=c++17', '-Wall'] + flags + ['-o', exe, src])
+    return exe
+
+
 def build_tilerecordcheck(force=False, sanitize=False, out=None):
     """tools/tilerecordcheck: the tile records' per-record rules as a stand-alone host program
     (CPU tests only).  sanitize=True: built with AddressSanitizer and UndefinedBehaviorSanitizer
@@ -240,6 +255,7 @@ def build_all(force=False):
     build_recordcheck(force)
     build_namecheck(force)
     build_tiletextcheck(force)
+    build_tileparsecheck(force)
     build_tilerecordcheck(force)
     build_oracle(force)
     build_calib(force)

@@ -643,6 +643,12 @@ int otr_tile_store_flush_text(otr_matcher* m, const char* source, const char* mo
   OTR_SESSIONS_CALL(!m || !flush || !out, tile_store_flush_text(source, mode, flags, flush, out, &err));
 }
 
+// tile file texts read back (K21): what report() reads from a match directory (simple_reporter.py:211-218)
+int otr_tiles_parse(otr_matcher* m, const otr_tile_texts* in, int32_t quantisation, int32_t rules, const char* source,
+                    const char* mode, int32_t flags, otr_tile_parse_result* out) {
+  OTR_SESSIONS_CALL(!m || !in || !out, tiles_parse(in, quantisation, rules, source, mode, flags, out, &err));
+}
+
 // simple_reporter.py:188-195: ','.join([id, next, duration, '1', length, queue, start, end,
 // source, mode.upper()]) + os.linesep
 // Segment.appendToStringBuffer (Segment.java:59-74) for OTR_TILE_RULES_STREAM

@@ -104,6 +104,9 @@ void tile_store_destroy(TileStore* s);  // frees the store's device memory
 struct TileText;                      // otr_tilestore.hip (K19): the buffers of the file texts
 void tile_text_destroy(TileText* t);  // frees them
 
+struct TileParse;                       // otr_tilestore.hip (K21): the rows read back from file texts
+void tile_parse_destroy(TileParse* t);  // frees them
+
 // what cull_device leaves in the matcher's cull slots
 struct CulledRows {
   const otr_tile_row* sorted;  // all n rows in file, then rule order
@@ -117,6 +120,7 @@ struct Matcher {
   SessionStore* ses = nullptr;  // the session store (otr_sessions_open), owned
   TileStore* tst = nullptr;     // the tile store (otr_tile_store_open), owned
   TileText* ttx = nullptr;      // the file texts of the last otr_tiles_text / flush_text, owned
+  TileParse* tpx = nullptr;     // the rows of the last otr_tiles_parse, owned
   DevPool pool{PoolOwner::matcher, nullptr, 0};  // the workspace slots (otr_slots.h), sized at first use
   GSlab gslab[2];
   // the turn cost tables last uploaded and the device buffer that holds them: a batch with the
@@ -251,6 +255,9 @@ struct Matcher {
                  const char* mode, int flags, otr_tile_text_result* out, std::string* err);
   int tile_store_flush_text(const char* source, const char* mode, int flags, otr_tile_flush_result* flush,
                             otr_tile_text_result* out, std::string* err);
+  // tile file texts read back (K21, otr_tileparse.h; otr_tilestore.hip)
+  int tiles_parse(const otr_tile_texts* in, int quantisation, int rules, const char* source, const char* mode,
+                  int flags, otr_tile_parse_result* out, std::string* err);
   ~Matcher();
 };
 

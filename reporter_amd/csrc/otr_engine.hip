@@ -408,6 +408,7 @@ Matcher::~Matcher() {
   if (ses) sessions_destroy(ses);
   if (tst) tile_store_destroy(tst);
   if (ttx) tile_text_destroy(ttx);
+  if (tpx) tile_parse_destroy(tpx);
   pool.release();
   if (mail) (void)hipHostFree(mail);
   if (h_drain) (void)hipHostFree(h_drain);

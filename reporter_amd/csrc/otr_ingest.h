@@ -370,8 +370,10 @@ struct IngestLines {
   unsigned long long* bad;  // min over rejected lines of (line << 8 | reason)
 };
 
+// The two newline kernels are static: the tile file parser's unit (otr_tilestore.hip, K21) builds
+// its own copy of them, with OTR_INGEST_NEWLINES_ONLY leaving the rest of the kernels out.
 // newline counts per 16-byte chunk (text padded to a multiple of 16 with zeros)
-__global__ void k_nl_count(const uint4* text, int64_t n_chunks, int64_t* cnt) {
+static __global__ void k_nl_count(const uint4* text, int64_t n_chunks, int64_t* cnt) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n_chunks) return;
   const uint4 v = text[c];
@@ -384,7 +386,7 @@ __global__ void k_nl_count(const uint4* text, int64_t n_chunks, int64_t* cnt) {
   cnt[c] = n;
 }
 
-__global__ void k_nl_write(const uint4* text, int64_t n_chunks, const int64_t* scan, int64_t* nl) {
+static __global__ void k_nl_write(const uint4* text, int64_t n_chunks, const int64_t* scan, int64_t* nl) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n_chunks) return;
   int64_t o = c ? scan[c - 1] : 0;
@@ -394,6 +396,8 @@ __global__ void k_nl_write(const uint4* text, int64_t n_chunks, const int64_t* s
   for (int k = 0; k < 16; ++k)
     if (((w[k >> 2] >> (8 * (k & 3))) & 0xFF) == 0x0A) nl[o++] = 16 * c + k;
 }
+
+#ifndef OTR_INGEST_NEWLINES_ONLY
 
 __device__ inline void ingest_reject(const IngestLines& L, int64_t line, int reason) {
   atomicMin(L.bad, ((unsigned long long)line << 8) | (unsigned)reason);
@@ -619,5 +623,6 @@ __global__ void k_win_emit(const int32_t* perm, int64_t m, const int64_t* wid, c
   }
 }
 
+#endif  // OTR_INGEST_NEWLINES_ONLY
 #endif  // OTR_INGEST_PARSE_ONLY
 }  // namespace otr

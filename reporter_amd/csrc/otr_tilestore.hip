@@ -1,9 +1,10 @@
 // otr_tilestore.hip — host side of the tile store (K15, otr_tilestore.h): the store's row
 // buffer, the two passes of an add (count, scan, capacity check, write) and the flush (the
 // matcher's device cull, then the per-file table), and of the tile file texts (K19,
-// otr_tiletext.h): lengths, scans, one emit pass, and of the store's snapshot, restore and
-// changelog records (K20, otr_tile_records.h).  include/otr.h otr_tile_store_* and
-// otr_tiles_text for the rules.
+// otr_tiletext.h): lengths, scans, one emit pass, of the store's snapshot, restore and
+// changelog records (K20, otr_tile_records.h), and of the file texts read back into rows (K21,
+// otr_tileparse.h): newline list, line table, one parse pass, compaction.  include/otr.h
+// otr_tile_store_*, otr_tiles_text and otr_tiles_parse for the rules.
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -15,6 +16,9 @@
 #include "otr_tilestore.h"
 #include "otr_tiletext.h"
 #include "otr_tile_records.h"
+// (K21 launches K11's two newline kernels; the rest of otr_ingest.h's kernels stay in otr_text.hip)
+#define OTR_INGEST_NEWLINES_ONLY
+#include "otr_tileparse.h"
 
 namespace otr {
 
@@ -37,6 +41,10 @@ enum TstBuf {
   T_I_START, T_I_TILE, T_I_SLICE, T_I_OFF, T_I_BYTES, T_I_MAP, T_I_COUNT, T_I_KEY_OK, T_I_FILE, T_I_FILE_A, T_I_FILE_B,
   T_I_SLICE_KEY, T_I_SLICE_B, T_I_IDX_A, T_I_IDX_B, T_I_IDX_C, T_I_WORDS, T_I_REF, T_I_ROW_OFF,
   T_M_FILE_A, T_M_FILE_B, T_M_IDX_A, T_M_IDX_B, T_M_VALUE, T_M_OK,
+  // K21: a parse's inputs and work, then its six results
+  T_P_TEXT, T_P_TEXT_OFF, T_P_NAMES, T_P_NAME_OFF, T_P_TAG, T_P_CNT, T_P_CSCAN, T_P_NL, T_P_NL_LO, T_P_LINE_CNT,
+  T_P_LINE_INCL, T_P_SLOT, T_P_ROW_INCL, T_P_HEAD_INCL, T_P_BAD_INCL, T_P_BAD,
+  T_P_ROWS, T_P_ROW_OFF, T_P_FILE, T_P_FILE_STATUS, T_P_FILE_LINE_OFF, T_P_LINE_STATUS,
   T_NUM
 };
 const char* const kTstName[T_NUM] = {
@@ -54,7 +62,12 @@ const char* const kTstName[T_NUM] = {
     "input counts", "input key flags", "input file keys", "input file keys in slice order", "sorted input file keys",
     "input slice keys", "sorted input slice keys", "input index", "input slice order", "input order",
     "restore verdict and counters", "referenced counts", "restored row offsets",
-    "map file keys", "sorted map file keys", "map index", "map order", "map values", "map key flags"};
+    "map file keys", "sorted map file keys", "map index", "map order", "map values", "map key flags",
+    "parse text", "parse text offsets", "parse names", "parse name offsets", "parse tag", "newline counts",
+    "newline ranks", "newline positions", "file newline ranks", "file line counts", "file line ranks",
+    "line row slots", "line row ranks", "line header ranks", "line refusal ranks", "first refused line",
+    "parsed rows", "parsed row offsets", "parsed files", "parsed file status", "parsed file line offsets",
+    "parsed line status"};
 
 }  // namespace
 
@@ -100,6 +113,21 @@ struct TileText : TstBufs {
 };
 
 void tile_text_destroy(TileText* t) {
+  if (!t) return;
+  t->release();
+  delete t;
+}
+
+// The rows of the last otr_tiles_parse (K21): a pool of its own, so that its results survive the
+// cull, the texts and the tile store calls, and the host copies the result points to.
+struct TileParse : TstBufs {
+  std::vector<otr_tile_row> h_rows;
+  std::vector<int64_t> h_row_off, h_file_line_off;
+  std::vector<unsigned long long> h_file;
+  std::vector<uint8_t> h_file_status, h_line_status;
+};
+
+void tile_parse_destroy(TileParse* t) {
   if (!t) return;
   t->release();
   delete t;
@@ -699,6 +727,209 @@ int Matcher::tile_store_flush_text(const char* source, const char* mode, int fla
     if ((rc = text_state(*this, err))) return rc;
     ttx->h_tag = tag;
     return tst->flush(*this, ttx, flags, flush, out, err);
+  });
+}
+
+// ---- tile file texts read back (K21) ------------------------------------------------------
+
+// The sizes refused are those of Matcher::ingest (otr_text.hip): text of 2^40 bytes or of
+// INT32_MAX 16-byte chunks (the chunk scan counts in int), INT32_MAX lines (the line scans do).
+// Order of work: the inputs, the newline list and the line counts go to work slots; only once the
+// line count has passed are the six result slots touched, so a refusal leaves the last result,
+// host and device, as it was.
+int Matcher::tiles_parse(const otr_tile_texts* in, int quantisation, int rules, const char* source, const char* mode,
+                         int flags, otr_tile_parse_result* out, std::string* err) {
+  std::vector<uint8_t> tag;
+  if (quantisation < 1) return bad(err, "tile parse: quantisation below 1");
+  if (!tile_text_rules_ok(rules)) return bad(err, "tile parse: unknown rules " + std::to_string(rules));
+  if (!text_tag(&tag, source, mode, rules)) return bad(err, "tile parse: source and mode take at most 255 bytes each");
+  const int64_t nf = in->n_files;
+  if (nf < 0) return bad(err, "tile parse: n_files below 0");
+  if (nf > 0 && (!in->text_off || !in->name_off)) return bad(err, "null argument");
+  return guarded(*this, err, false, [&]() -> int {
+    int rc;
+    HIPCHK(hipSetDevice(graph_state().device));
+    if (!stream) HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    if (!tpx) tpx = new TileParse();
+    TileParse& t = *tpx;
+    t.stream = stream;
+    if ((rc = t.events(err))) return rc;
+    const bool dev = in->memory == OTR_MEM_DEVICE;
+    // the two offset arrays on the host: checked here, whichever memory they came from
+    std::vector<int64_t> toff((size_t)nf + 1, 0), noff((size_t)nf + 1, 0);
+    if (nf > 0) {
+      const hipMemcpyKind k = dev ? hipMemcpyDeviceToHost : hipMemcpyHostToHost;
+      HIPCHK(hipMemcpy(toff.data(), in->text_off, 8 * ((size_t)nf + 1), k));
+      HIPCHK(hipMemcpy(noff.data(), in->name_off, 8 * ((size_t)nf + 1), k));
+    }
+    for (const auto* o : {&toff, &noff}) {
+      if ((*o)[0] != 0) return bad(err, "tile parse: offsets do not ascend from 0");
+      for (int64_t f = 0; f < nf; ++f)
+        if ((*o)[(size_t)f + 1] < (*o)[(size_t)f]) return bad(err, "tile parse: offsets do not ascend from 0");
+    }
+    const int64_t len = toff[(size_t)nf], name_len = noff[(size_t)nf];
+    const int64_t n_chunks = (len + 15) / 16;
+    if (len >= ((int64_t)1 << 40) || n_chunks >= (int64_t)INT32_MAX) return bad(err, "tile parse: text too large");
+    if ((len > 0 && !in->text) || (name_len > 0 && !in->names)) return bad(err, "null argument");
+    HIPCHK(hipEventRecord(t.ev[0], stream));
+    // inputs in HBM: the text padded to whole chunks, the rest as it is or uploaded
+    const hipMemcpyKind up = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    TileParseIn a{};
+    a.n_files = nf;
+    a.rules = rules;
+    a.quantisation = quantisation;
+    uint8_t* d_text = t.get<uint8_t>(T_P_TEXT, 16 * (size_t)n_chunks);
+    a.text = d_text;
+    if (n_chunks > 0) {
+      HIPCHK(hipMemsetAsync(d_text + 16 * (n_chunks - 1), 0, 16, stream));
+      HIPCHK(hipMemcpyAsync(d_text, in->text, (size_t)len, up, stream));
+    }
+    if (dev && nf > 0) {
+      a.text_off = in->text_off;
+      a.names = in->names;
+      a.name_off = in->name_off;
+    } else {
+      int64_t* d_toff = t.get<int64_t>(T_P_TEXT_OFF, (size_t)nf + 1);
+      int64_t* d_noff = t.get<int64_t>(T_P_NAME_OFF, (size_t)nf + 1);
+      uint8_t* d_names = t.get<uint8_t>(T_P_NAMES, (size_t)name_len);
+      HIPCHK(hipMemcpyAsync(d_toff, toff.data(), 8 * ((size_t)nf + 1), hipMemcpyHostToDevice, stream));
+      HIPCHK(hipMemcpyAsync(d_noff, noff.data(), 8 * ((size_t)nf + 1), hipMemcpyHostToDevice, stream));
+      if (name_len > 0) HIPCHK(hipMemcpyAsync(d_names, in->names, (size_t)name_len, hipMemcpyHostToDevice, stream));
+      a.text_off = d_toff;
+      a.names = d_names;
+      a.name_off = d_noff;
+    }
+    uint8_t* d_tag = t.get<uint8_t>(T_P_TAG, kTileTextTagMax);
+    HIPCHK(hipMemcpyAsync(d_tag, tag.data(), tag.size(), hipMemcpyHostToDevice, stream));
+    // the newline positions (K11's kernels)
+    int64_t n_nl = 0;
+    if (n_chunks > 0) {
+      int64_t* cnt = t.get<int64_t>(T_P_CNT, (size_t)n_chunks);
+      int64_t* cscan = t.get<int64_t>(T_P_CSCAN, (size_t)n_chunks);
+      k_nl_count<<<grid_ceil(n_chunks, 256), 256, 0, stream>>>(reinterpret_cast<const uint4*>(d_text), n_chunks, cnt);
+      HIPCHK(hipGetLastError());
+      if ((rc = t.scan64(cnt, cscan, n_chunks, err))) return rc;
+      if ((rc = read_back(stream, err, fetch(&n_nl, cscan + (n_chunks - 1))))) return rc;
+      if (n_nl < 0 || n_nl > len) {
+        if (err) *err = "tile parse newline count failed";
+        return OTR_DEVICE_ERROR;
+      }
+      int64_t* nl = t.get<int64_t>(T_P_NL, (size_t)n_nl);
+      if (n_nl > 0) {
+        k_nl_write<<<grid_ceil(n_chunks, 256), 256, 0, stream>>>(reinterpret_cast<const uint4*>(d_text), n_chunks, cscan,
+                                                                nl);
+        HIPCHK(hipGetLastError());
+      }
+      a.nl = nl;
+    } else {
+      a.nl = t.get<int64_t>(T_P_NL, 1);
+    }
+    a.n_nl = n_nl;
+    // the line table: per file its newlines and its line count, then the counts' scan
+    int64_t n_lines = 0;
+    int64_t* nl_lo = t.get<int64_t>(T_P_NL_LO, (size_t)nf + 1);
+    int64_t* line_cnt = t.get<int64_t>(T_P_LINE_CNT, (size_t)nf);
+    int64_t* line_incl = t.get<int64_t>(T_P_LINE_INCL, (size_t)nf);
+    const unsigned gf = grid_ceil1(nf + 1, 256);
+    if (nf > 0) {
+      k_tile_parse_files<<<gf, 256, 0, stream>>>(a, nl_lo, line_cnt);
+      HIPCHK(hipGetLastError());
+      if ((rc = t.scan64(line_cnt, line_incl, nf, err))) return rc;
+      if ((rc = read_back(stream, err, fetch(&n_lines, line_incl + (nf - 1))))) return rc;
+      if (n_lines < 0 || n_lines > n_nl + nf) {
+        if (err) *err = "tile parse line table failed";
+        return OTR_DEVICE_ERROR;
+      }
+    }
+    if (n_lines >= (int64_t)INT32_MAX) return bad(err, "tile parse: too many lines for one call");
+    // ---- from here on the result slots are written
+    int64_t* file_line_off = t.get<int64_t>(T_P_FILE_LINE_OFF, (size_t)nf + 1);
+    unsigned long long* file = t.get<unsigned long long>(T_P_FILE, (size_t)nf);
+    uint8_t* file_status = t.get<uint8_t>(T_P_FILE_STATUS, (size_t)nf);
+    uint8_t* line_status = t.get<uint8_t>(T_P_LINE_STATUS, (size_t)n_lines);
+    int64_t* row_off = t.get<int64_t>(T_P_ROW_OFF, (size_t)nf + 1);
+    otr_tile_row* slot = t.get<otr_tile_row>(T_P_SLOT, (size_t)n_lines);
+    int64_t* row_incl = t.get<int64_t>(T_P_ROW_INCL, (size_t)n_lines);
+    int64_t* head_incl = t.get<int64_t>(T_P_HEAD_INCL, (size_t)n_lines);
+    int64_t* bad_incl = t.get<int64_t>(T_P_BAD_INCL, (size_t)n_lines);
+    unsigned long long* d_bad = t.get<unsigned long long>(T_P_BAD, 1);
+    k_tile_parse_names<<<gf, 256, 0, stream>>>(a, line_incl, file_line_off, file, file_status);
+    HIPCHK(hipGetLastError());
+    int64_t n_rows = 0, n_headers = 0, n_bad = 0;
+    unsigned long long h_bad = ~0ull;
+    if (n_lines > 0) {
+      HIPCHK(hipMemsetAsync(d_bad, 0xFF, 8, stream));
+      k_tile_parse<<<grid_ceil(n_lines, 256), 256, 0, stream>>>(a, nl_lo, file_line_off, file, file_status, d_tag,
+                                                                (int32_t)tag.size(), n_lines, line_status, slot, d_bad);
+      HIPCHK(hipGetLastError());
+      Workspace ws;
+      int64_t* const three[3] = {row_incl, head_incl, bad_incl};
+      if ((rc = tuple_sums<3>(&ws, TileParseColumns{line_status}, three, (int)n_lines, stream, err))) return rc;
+      ws.p = t.get<char>(T_TMP, ws.bytes);
+      if ((rc = tuple_sums<3>(&ws, TileParseColumns{line_status}, three, (int)n_lines, stream, err))) return rc;
+      if ((rc = read_back(stream, err, fetch(&n_rows, row_incl + (n_lines - 1)), fetch(&n_headers, head_incl + (n_lines - 1)),
+                          fetch(&n_bad, bad_incl + (n_lines - 1)), fetch(&h_bad, d_bad))))
+        return rc;
+      if (n_rows < 0 || n_headers < 0 || n_bad < 0 || n_rows + n_headers + n_bad != n_lines ||
+          (n_bad == 0) != (h_bad == ~0ull) || (h_bad != ~0ull && (int64_t)(h_bad >> 8) >= n_lines)) {
+        if (err) *err = "tile parse line counts failed";
+        return OTR_DEVICE_ERROR;
+      }
+    }
+    otr_tile_row* rows = t.get<otr_tile_row>(T_P_ROWS, (size_t)n_rows);
+    k_tile_parse_compact<<<grid_ceil1(std::max<int64_t>(n_lines, nf + 1), 256), 256, 0, stream>>>(
+        line_status, slot, row_incl, n_lines, file_line_off, nf, rows, row_off);
+    HIPCHK(hipGetLastError());
+    // the file table always comes to the host: the first refused line's file and the refused names
+    t.h_file_line_off.resize((size_t)nf + 1);
+    t.h_file_status.resize((size_t)nf + 1);
+    HIPCHK(hipMemcpyAsync(t.h_file_line_off.data(), file_line_off, 8 * ((size_t)nf + 1), hipMemcpyDeviceToHost, stream));
+    if (nf > 0) HIPCHK(hipMemcpyAsync(t.h_file_status.data(), file_status, (size_t)nf, hipMemcpyDeviceToHost, stream));
+    const bool host = !(flags & OTR_TILE_PARSE_NO_HOST);
+    if (host) {
+      t.h_rows.resize((size_t)n_rows + 1);
+      t.h_row_off.resize((size_t)nf + 1);
+      t.h_file.resize((size_t)nf + 1);
+      t.h_line_status.resize((size_t)n_lines + 1);
+      if (n_rows > 0)
+        HIPCHK(hipMemcpyAsync(t.h_rows.data(), rows, sizeof(otr_tile_row) * (size_t)n_rows, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipMemcpyAsync(t.h_row_off.data(), row_off, 8 * ((size_t)nf + 1), hipMemcpyDeviceToHost, stream));
+      if (nf > 0) HIPCHK(hipMemcpyAsync(t.h_file.data(), file, 8 * (size_t)nf, hipMemcpyDeviceToHost, stream));
+      if (n_lines > 0)
+        HIPCHK(hipMemcpyAsync(t.h_line_status.data(), line_status, (size_t)n_lines, hipMemcpyDeviceToHost, stream));
+    }
+    float ms = 0.f;
+    if ((rc = t.finish(&ms, err))) return rc;
+    memset(out, 0, sizeof(*out));
+    out->n_lines = n_lines;
+    out->n_rows = n_rows;
+    out->n_headers = n_headers;
+    out->n_bad = n_bad;
+    for (int64_t f = 0; f < nf; ++f) out->n_bad_names += t.h_file_status[(size_t)f];
+    out->first_bad = -1;
+    out->first_bad_file = -1;
+    if (h_bad != ~0ull) {
+      out->first_bad = (int64_t)(h_bad >> 8);
+      out->first_bad_reason = (int32_t)(h_bad & 0xFF);
+      out->first_bad_file = (int32_t)tile_parse_file_of(t.h_file_line_off.data(), nf, out->first_bad);
+    }
+    out->device_ms = ms;
+    out->n_files = (int32_t)nf;
+    if (host) {
+      out->rows = t.h_rows.data();
+      out->row_off = t.h_row_off.data();
+      out->file = (const uint64_t*)t.h_file.data();
+      out->file_status = t.h_file_status.data();
+      out->file_line_off = t.h_file_line_off.data();
+      out->line_status = t.h_line_status.data();
+    }
+    out->d_rows = rows;
+    out->d_row_off = row_off;
+    out->d_file = (const uint64_t*)file;
+    out->d_file_status = file_status;
+    out->d_file_line_off = file_line_off;
+    out->d_line_status = line_status;
+    return OTR_OK;
   });
 }
 

@@ -888,6 +888,40 @@ class Matcher:
                 out[k] = text[k]
         return out
 
+    # --- tile file texts read back (include/otr.h otr_tiles_parse) -----
+    def tiles_parse(self, text=None, text_off=None, names=None, name_off=None, device=False, n_files=None,
+                    quantisation=3600, rules=0, source='smpl_rprt', mode='auto', host=True):
+        """otr_tiles_parse: the texts of many tile files (text and names: bytes or numpy uint8,
+        text_off and name_off: int64 of n_files + 1, the shape tiles_text returns; or with
+        device=True four device pointers and n_files) to rows in HBM grouped by file.  Returns
+        _lib.tile_parse_to_numpy's dict: the counts, first_bad*, the device pointers d_* (owned by
+        the matcher until its next tiles_parse) and, with host=True, numpy copies of rows, row_off,
+        file, file_status, file_line_off and line_status.  Lines and names that are not rows are
+        reported there, not raised; ValueError only for arguments the call refuses as a whole."""
+        c, r = _lib.TileTexts(), _lib.TileParseResult()
+        if device:
+            c.n_files, c.memory = int(n_files), _lib.OTR_MEM_DEVICE
+            c.text, c.text_off, c.names, c.name_off = (int(x) or None for x in (text, text_off, names, name_off))
+        else:
+            def u8(x):
+                return np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, np.uint8)
+            t, nm = u8(text if text is not None else b''), u8(names if names is not None else b'')
+            to = np.ascontiguousarray(text_off if text_off is not None else [0], np.int64)
+            no = np.ascontiguousarray(name_off if name_off is not None else [0], np.int64)
+            if len(to) != len(no) or len(to) < 1:
+                raise ValueError('tiles_parse: text_off and name_off hold n_files + 1 offsets each')
+            if int(to[-1]) > len(t) or int(no[-1]) > len(nm):
+                raise ValueError('tiles_parse: the offsets run past the text or the names')
+            self._keep = [t, nm, to, no]
+            c.n_files, c.memory = len(to) - 1, _lib.OTR_MEM_HOST
+            c.text, c.names = (t.ctypes.data if len(t) else None), (nm.ctypes.data if len(nm) else None)
+            c.text_off, c.name_off = to.ctypes.data, no.ctypes.data
+        rc = self._L.otr_tiles_parse(self._h, ctypes.byref(c), int(quantisation), int(rules), self._tag_bytes(source),
+                                     self._tag_bytes(mode), 0 if host else _lib.OTR_TILE_PARSE_NO_HOST,
+                                     ctypes.byref(r))
+        self._check(rc, 'otr_tiles_parse')
+        return _lib.tile_parse_to_numpy(r, host)
+
     def match_batch_numpy(self, traces, **kw):
         r = self.match_batch(traces, copy_out=True, **kw)
         return _lib.result_to_numpy(r)

@@ -274,6 +274,74 @@ def tiles_text_device(matcher, device_ptr, n, quantisation=3600, mode='auto', so
                                             source=source, mode=mode))
 
 
+def read_tile_files(match_dir):
+    """The tile files under match_dir ("{start}_{end}/{level}/{tile}", what write_tiles and the
+    reference's match() leave there) as the four arrays Matcher.tiles_parse takes: text (uint8),
+    text_off, names (uint8), name_off (int64).  The directory is walked in sorted order and
+    stripped from the names; the names use '/' whatever the platform's separator is."""
+    texts, names = [], []
+    for root, dirs, files in os.walk(match_dir):
+        dirs.sort()
+        for f in sorted(files):
+            path = os.path.join(root, f)
+            with open(path, 'rb') as fh:
+                texts.append(fh.read())
+            names.append(os.path.relpath(path, match_dir).replace(os.sep, '/').encode())
+
+    def pack(parts):
+        off = np.zeros(len(parts) + 1, np.int64)
+        off[1:] = np.cumsum([len(p) for p in parts])
+        return np.frombuffer(b''.join(parts), np.uint8), off
+    text, text_off = pack(texts)
+    name, name_off = pack(names)
+    return text, text_off, name, name_off
+
+
+def report_match_dir(matcher, match_dirs, privacy, quantisation=3600, mode='auto', source='smpl_rprt', rules=0):
+    """simple_reporter.py --match-dir: report() (:211-254) over tile files written earlier, by this
+    run, another process, host or day, or at another privacy.  match_dirs: one directory or
+    several, concatenated (the same name may occur more than once: the cull's sort by file merges
+    them).  read_tile_files -> Matcher.tiles_parse (rows in HBM) -> cull_rows on the device rows
+    -> Matcher.tiles_text.  Returns {name: text} as tiles_text_device does.  The parsed rows go
+    into the cull where they lie in HBM; the kept rows come back through the host on their way
+    to the text stage, because otr_tiles_cull hands out its kept rows as a host array only (its
+    device copy is reachable from the tile store's flush, not through the C interface), so there
+    is no device pointer to give tiles_text_device.  Files with the column line (write_tiles)
+    and without it (the reference's match-dir form) are both read under rules=0.  ValueError naming the file, line and reason when any line or name was refused: a
+    file the rows cannot express is not reported half."""
+    from . import _lib
+    if isinstance(match_dirs, (str, bytes, os.PathLike)):
+        match_dirs = [match_dirs]
+    parts = [read_tile_files(d) for d in match_dirs]
+    text = np.concatenate([p[0] for p in parts]) if parts else np.zeros(0, np.uint8)
+    names = np.concatenate([p[2] for p in parts]) if parts else np.zeros(0, np.uint8)
+    text_off, name_off = [np.zeros(1, np.int64)], [np.zeros(1, np.int64)]
+    for p in parts:
+        text_off.append(p[1][1:] + text_off[-1][-1])
+        name_off.append(p[3][1:] + name_off[-1][-1])
+    text_off, name_off = np.concatenate(text_off), np.concatenate(name_off)
+    r = matcher.tiles_parse(text=text, text_off=text_off, names=names, name_off=name_off, quantisation=quantisation,
+                            rules=rules, source=source, mode=mode)
+
+    def name_of(f):
+        return names[name_off[f]:name_off[f + 1]].tobytes().decode('utf-8', 'replace')
+    if r['n_bad_names']:
+        f = int(np.flatnonzero(r['file_status'])[0])
+        raise ValueError('report_match_dir: file %d: %r is not a tile file name at quantisation %d (%d such names)'
+                         % (f, name_of(f), quantisation, r['n_bad_names']))
+    if r['n_bad']:
+        f, line = r['first_bad_file'], r['first_bad']
+        raise ValueError('report_match_dir: file %r, line %d (line %d of the file): %s (%d such lines)' % (
+            name_of(f), line, line - int(r['file_line_off'][f]),
+            _lib.TILE_LINE_NAME.get(r['first_bad_reason'], r['first_bad_reason']), r['n_bad']))
+    if r['n_rows'] == 0:
+        return {}
+    kept = cull_rows(matcher, None, privacy, device_ptr=r['d_rows'], n=r['n_rows'], rules=rules)
+    if len(kept) == 0:
+        return {}
+    return text_payloads(matcher.tiles_text(kept, quantisation=quantisation, rules=rules, source=source, mode=mode))
+
+
 def _window_batch(traces, inactivity):
     from .tools.gen import Traces
     idx_lat, idx_lon, idx_time, offs, modes = [], [], [], [0], []

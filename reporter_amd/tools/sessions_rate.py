@@ -56,6 +56,13 @@ path's device_ms (flush + text stage) beside it; median [min, max].
 
     python -m reporter_amd.tools.sessions_rate --traces 2000 --tile-store --text --out profiles/tile_text_c2dep.json
 
+`--tile-store --text --parse` measures the way back (K21) on the same two fills: one flush with texts,
+then otr_tiles_parse of those texts from the device pointers (device_ms) and from the host arrays to
+host arrays (wall time), beside otr_tiles_text of the same rows in HBM (K19's device_ms); one warm-up,
+`--repeats` timed runs, median [min, max].
+
+    python -m reporter_amd.tools.sessions_rate --traces 2000 --tile-store --text --parse --out profiles/tile_parse_c2dep.json
+
 `--tile-store --records` times the tile store's state leaving and coming back (K20) on a store with
 the times: export_records, restore_records from device and from host arrays, and snapshot +
 restore, on the replay's held rows at the stream's midpoint and on `--tile-rows` synthetic rows,
@@ -300,6 +307,53 @@ def tile_text_rates(m, fill, close, repeats):
                             'text_ms_median_min_max': med(runs_b, 'text_ms')}}
 
 
+def tile_parse_rates(m, fill, close, repeats):
+    """K21 on the texts K19 wrote for the store `fill` leaves open (`close` closes it): one flush
+    with texts, then otr_tiles_parse of those texts, one warm-up and `repeats` timed runs each way:
+    from the device pointers with device copies only (device_ms), and from the host arrays to the
+    host arrays (wall time); beside them otr_tiles_text of the parsed rows in HBM, the same rows
+    K19 wrote the texts from (device_ms)."""
+    fill()
+    fl = m.tile_store_flush_text('reporter', 'auto')
+    kw = dict(quantisation=fl['quantisation'], rules=1, source='reporter', mode='auto')
+    host_args = {k: fl[k] for k in ('text', 'text_off', 'names', 'name_off')}
+
+    def device():
+        return m.tiles_parse(text=fl['d_text'], text_off=fl['d_text_off'], names=fl['d_names'], name_off=fl['d_name_off'],
+                             device=True, n_files=fl['n_files'], host=False, **kw)
+
+    def host():
+        t0 = time.perf_counter()
+        r = m.tiles_parse(**host_args, **kw)
+        return r, 1e3 * (time.perf_counter() - t0)
+
+    r = device()
+    if r['n_bad'] or r['n_bad_names'] or r['n_rows'] != fl['n_rows'] or host()[0]['n_rows'] != fl['n_rows']:
+        raise RuntimeError('the texts of the flush do not parse back into its rows')
+    dev_ms, wall_ms, host_dev_ms, text_ms = [], [], [], []
+    for _ in range(repeats):
+        dev_ms.append(device()['device_ms'])
+        h, w = host()
+        wall_ms.append(w)
+        host_dev_ms.append(h['device_ms'])
+    p = device()
+    m.tiles_text(device_ptr=p['d_rows'], n=p['n_rows'], host=False, **kw)
+    for _ in range(repeats):
+        text_ms.append(m.tiles_text(device_ptr=p['d_rows'], n=p['n_rows'], host=False, **kw)['device_ms'])
+    close()
+
+    def med(v):
+        v = sorted(v)
+        return [round(float(np.median(v)), 3), round(float(v[0]), 3), round(float(v[-1]), 3)]
+
+    return {'rows': fl['n_rows'], 'files': fl['n_files'], 'text_bytes': fl['n_text_bytes'], 'lines': r['n_lines'],
+            'k19_flush_text_ms': round(fl['text_ms'], 3),
+            'k19_tiles_text_device_ms_median_min_max': med(text_ms),
+            'k21_device_text_device_ms_median_min_max': med(dev_ms),
+            'k21_host_to_host_wall_ms_median_min_max': med(wall_ms),
+            'k21_host_to_host_device_ms_median_min_max': med(host_dev_ms)}
+
+
 def restore_rates(m, pts, max_points, repeats):
     """The store at the stream's midpoint (10 s chunks): snapshot, export, take-all, restore from
     the SoA and from records, each timed `repeats` times after a warm-up."""
@@ -485,6 +539,8 @@ def main():
     ap.add_argument('--text', choices=['sv', 'json', 'tiles'], nargs='?', const='tiles', default=None,
                     help='sv, json: render the stream as messages and push them through otr_sessions_push_text; '
                          'no value, with --tile-store: time the flush to file payloads on the host and on the device')
+    ap.add_argument('--parse', action='store_true',
+                    help='with --tile-store --text: time otr_tiles_parse (K21) on the texts of the flush instead')
     ap.add_argument('--restore', action='store_true',
                     help='time snapshot, export, take-all and the two restores on the store at the midpoint')
     ap.add_argument('--records', action='store_true',
@@ -573,6 +629,23 @@ def main():
             m.tile_store_open(args.tile_rows, 3600, 1)
             m.tile_store_add_rows(rows)
 
+        if args.parse:
+            res = {'workload': 'c2dep: %s graph, %d traces x 100 probes @15 s, sigma 10 m, deployed configuration; and '
+                               '%d seeded rows over 300 files' % (args.graph, args.traces, args.tile_rows),
+                   'method': 'one process; one flush with texts per leg, then 1 warm-up and %d timed runs of each call '
+                             'on those texts; device_ms: the call\'s HIP events (its copies included); wall: host '
+                             'arrays in to host arrays out; median [min, max]' % args.repeats,
+                   'tile_parse': {
+                       'replay_10_s_privacy_2': tile_parse_rates(
+                           m, lambda: replay(m, pts, cuts, args.max_points, batch_ms, args.tile_rows, hold=True),
+                           m.tile_store_close, args.repeats),
+                       'add_rows_privacy_1': tile_parse_rates(m, fill_rows, m.tile_store_close, args.repeats)}}
+            line = json.dumps(res, indent=1)
+            print(line)
+            if args.out:
+                with open(args.out, 'w') as f:
+                    f.write(line + '\n')
+            return
         res = {'workload': 'c2dep: %s graph, %d traces x 100 probes @15 s, sigma 10 m, deployed configuration; and '
                            '%d seeded rows over 300 files' % (args.graph, args.traces, args.tile_rows),
                'method': 'one process; 1 warm-up of each path, then %d timed runs alternating; host wall time from '
