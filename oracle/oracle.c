@@ -685,6 +685,34 @@ int orc_route(const orc_graph* g, const orc_params* p, int mode, uint32_t src_ed
   return ok;
 }
 
+void orc_route_step(const orc_graph* g, const orc_params* p, int mode, int32_t n_src, const uint32_t* src_edge,
+                    const double* src_p, int32_t n_dst, const uint32_t* dst_edge, const double* dst_p, double bound,
+                    int64_t dt_sec, double* out_dist, int64_t* out_time_ds, int64_t* out_turn_mm) {
+  mode_data md;
+  mode_data_init(g, p, mode, &md);
+  rctx X;
+  orc_params q = *p; /* bound given directly, as orc_route */
+  q.max_route_distance_factor = 1.0;
+  q.interpolation_distance = 0.0;
+  q.breakage_distance = bound;
+  step_ctx(&X, g, &md, &q, bound, dt_sec);
+  nodemap_t m;
+  nm_init(&m, 1024);
+  for (int32_t i = 0; i < n_src; ++i) {
+    search(&X, src_edge[i], src_p[i], &m);
+    for (int32_t j = 0; j < n_dst; ++j) {
+      rkey r;
+      const int ok = route_of(&X, &m, src_edge[i], src_p[i], dst_edge[j], dst_p[j], &r);
+      const size_t o = (size_t)i * (size_t)n_dst + (size_t)j;
+      out_dist[o] = ok ? (double)r.d / 1000.0 : INFINITY;
+      out_time_ds[o] = ok ? r.t : -1;
+      out_turn_mm[o] = ok ? r.k - r.d : -1;
+    }
+  }
+  nm_free(&m);
+  free(md.time_ds);
+}
+
 /* ---------------------------------------------------------------------------- */
 /* report() — reporter_service.py:79-179                                          */
 /* ---------------------------------------------------------------------------- */

@@ -146,6 +146,14 @@ int orc_route(const orc_graph* g, const orc_params* p, int mode, uint32_t src_ed
               double dst_p, double bound, int64_t dt_sec, double* out_dist, int64_t* out_time_ds,
               int64_t* out_turn_mm);
 
+/* orc_route for every pair of one step: sources (src_edge, src_p)[n_src], targets
+ * (dst_edge, dst_p)[n_dst], one search per source.  Row-major [n_src][n_dst] outputs as
+ * orc_route's: length (m, INFINITY without a valid route), time (0.1 s, -1) and turn cost
+ * (mm, -1). */
+void orc_route_step(const orc_graph* g, const orc_params* p, int mode, int32_t n_src, const uint32_t* src_edge,
+                    const double* src_p, int32_t n_dst, const uint32_t* dst_edge, const double* dst_p, double bound,
+                    int64_t dt_sec, double* out_dist, int64_t* out_time_ds, int64_t* out_turn_mm);
+
 /* graph-derived per-edge data the routing semantics use (for tests): heading of the
  * first / last shape segment (integer degrees clockwise from north), route time
  * (0.1 s) under the mode's speed, and the mode's turn cost table (mm, 181 entries). */

@@ -109,6 +109,11 @@ def lib():
                                 ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_int64,
                                 P(ctypes.c_double), P(ctypes.c_int64), P(ctypes.c_int64)]
         L.orc_route.restype = ctypes.c_int
+        L.orc_route_step.argtypes = [ctypes.c_void_p, P(Params), ctypes.c_int, ctypes.c_int32, P(ctypes.c_uint32),
+                                     P(ctypes.c_double), ctypes.c_int32, P(ctypes.c_uint32), P(ctypes.c_double),
+                                     ctypes.c_double, ctypes.c_int64, P(ctypes.c_double), P(ctypes.c_int64),
+                                     P(ctypes.c_int64)]
+        L.orc_route_step.restype = None
         L.orc_edge_info.argtypes = [ctypes.c_void_p, P(Params), ctypes.c_uint32, P(ctypes.c_int32),
                                     P(ctypes.c_int32), P(ctypes.c_int64)]
         L.orc_turn_table.argtypes = [P(Params), P(ctypes.c_int32)]
@@ -144,6 +149,21 @@ class Graph:
         ok = lib().orc_route(self.h, ctypes.byref(prm[mode]), mode, se, sp, de, dp, bound, int(dt_sec),
                              ctypes.byref(d), ctypes.byref(t), ctypes.byref(c))
         return (d.value, t.value, c.value) if ok else None
+
+    def route_step(self, se, sp, de, dp, bound, dt_sec=0, prm=None, mode=0):
+        """route() for every pair of one step (sources se, sp; targets de, dp): arrays
+        [len(se)][len(de)] of length (m, inf without a route), time (0.1 s, -1) and turn cost
+        (mm, -1)."""
+        prm = prm if prm is not None else params()
+        se, de = np.ascontiguousarray(se, np.uint32), np.ascontiguousarray(de, np.uint32)
+        sp, dp = np.ascontiguousarray(sp, np.float64), np.ascontiguousarray(dp, np.float64)
+        n, m = len(se), len(de)
+        d, t, c = np.zeros((n, m)), np.zeros((n, m), np.int64), np.zeros((n, m), np.int64)
+        lib().orc_route_step(self.h, ctypes.byref(prm[mode]), mode, n, _ptr(se, ctypes.c_uint32),
+                             _ptr(sp, ctypes.c_double), m, _ptr(de, ctypes.c_uint32), _ptr(dp, ctypes.c_double),
+                             float(bound), int(dt_sec), _ptr(d, ctypes.c_double), _ptr(t, ctypes.c_int64),
+                             _ptr(c, ctypes.c_int64))
+        return d, t, c
 
     def edge_info(self, e, prm=None, mode=0):
         """(begin heading, end heading, route time 0.1 s) of edge e."""
