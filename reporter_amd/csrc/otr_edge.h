@@ -375,7 +375,7 @@ __device__ bool edge_search(EdgeLds<CAP, TG>& L, const DevGraph& g, int md, bool
 // first hop from the target takes the smallest a whose offer is the target's label.  The
 // lanes test the in-edges of one node in parallel.
 // ------------------------------------------------------------------------------
-// overflow_flag: the step's flag when the table overflows (the next tier)
+// overflow_flag: the step's flag when the table overflows (the next tier: kPathTiers' overflow column)
 template <int CAP>
 __global__ __launch_bounds__(64) void k_paths_edge(DevGraph gr, PathArgs a, const int32_t* turn_tab,
                                                    const int64_t* step_list, const unsigned long long* list_count,
@@ -405,8 +405,8 @@ __global__ __launch_bounds__(64) void k_paths_edge(DevGraph gr, PathArgs a, cons
     e_turn_table(L, turn_tab, md);
     bool ok = edge_search<CAP, 32>(L, gr, md, true, ei, gr.edge_dst[ei], pd, pt, bt >= 0, 1, ct.y, ct.x,
                                    tpt, thb, nullptr, nullptr);
-#ifdef OTR_FORCE_RETRY  // test build: OTR_FORCE_EDGE bit 3 / 4 fails every 384 / 2048-state winner path
-    if (a.force_edge & (CAP < 2048 ? 8 : 16)) ok = false;
+#ifdef OTR_FORCE_RETRY  // test build: fail every 384 / 2048-state winner path
+    if (a.force_edge & (CAP < 2048 ? FE_FAIL_PATH_384 : FE_FAIL_PATH_2048)) ok = false;
 #endif
     const unsigned long long tl = L.tlab[0];
     int n = -1;

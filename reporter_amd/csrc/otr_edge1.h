@@ -367,9 +367,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OTR_E1WAVES,
     const int64_t s = r0.x, sp = r0.y;
     const unsigned long long mask = ((unsigned long long)r1.w << 32) | r1.z;
     const int i = __ffsll((long long)mask) - 1;  // the task's one source
-    const int Kb = (int)(r1.y & 0xFFu);
-    const int md = (int)((r1.y >> 8) & 3u);
-    const bool forced = (r1.y >> 10) & 1u;
+    const int Kb = (int)tw_Kb(r1.y);
+    const int md = (int)tw_mode(r1.y);
+    const bool forced = tw_forced(r1.y);
     const uint32_t bmm = r0.w;
     const int32_t bt = (int32_t)r2.y;
     const bool timed = bt >= 0;
@@ -588,11 +588,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OTR_E1WAVES,
           dump = !L.overflow && !pover;  // (a full table lost a relaxation: that search restarts)
           break;
         }
-#ifdef OTR_FORCE_RETRY  // test build: OTR_FORCE_EDGE bit 5 / 6 stops every OTR_E1CAP / 512-state search
+#ifdef OTR_FORCE_RETRY  // test build: FE_STOP_E1 / FE_STOP_E512 stops every OTR_E1CAP / 512-state search
                         // after 2 / 4 rounds, to be resumed in the next table
         ++rounds;
-        if (((a.force_edge & 32) && CAP == OTR_E1CAP && rounds == 2) ||
-            ((a.force_edge & 64) && CAP == 512 && rounds == 4)) {
+        if (((a.force_edge & FE_STOP_E1) && CAP == OTR_E1CAP && rounds == 2) ||
+            ((a.force_edge & FE_STOP_E512) && CAP == 512 && rounds == 4)) {
           ok = false;
           dump = true;
           break;
@@ -600,8 +600,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OTR_E1WAVES,
 #endif
       }
     }
-#ifdef OTR_FORCE_RETRY  // test build: OTR_FORCE_EDGE bit 0 / 1 / 2 fails every OTR_E1CAP (360) / 512 / 1024-state search
-    if (a.force_edge & (CAP < 512 ? 1 : (CAP < 1024 ? 2 : 4))) {
+#ifdef OTR_FORCE_RETRY  // test build: fail every OTR_E1CAP (360) / 512 / 1024-state search
+    if (a.force_edge & (CAP < 512 ? FE_FAIL_E1 : (CAP < 1024 ? FE_FAIL_E512 : FE_FAIL_E1024))) {
       ok = false;
       dump = false;
     }
@@ -658,7 +658,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OTR_E1WAVES,
       if (slot >= 0) e1_dump(L, a.dump_out + (size_t)slot * a.dump_out_words, npend, kmin, dmin, tmn, 0u, 0u);
       if (counters && slot >= 0 && lane == 0) atomicAdd(&counters[23 * kCShards + cshard()], 1ull);
       if (lane == 0) {
-        a.overflow_flag[task] = CAP < 512 ? 6 : (CAP < 1024 ? 7 : 3);
+        a.overflow_flag[task] = edge_overflow_flag(CAP);
         if (a.task_dump != nullptr) a.task_dump[task] = slot;
       }
     }

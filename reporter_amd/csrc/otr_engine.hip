@@ -481,22 +481,6 @@ __device__ inline void block_append(bool hit, int64_t value, int64_t* list, unsi
   if (hit) list[s_base + my] = value;
 }
 
-__global__ void k_collect(int64_t n, const int32_t* flag, int64_t* list, unsigned long long* count) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  block_append(i < n && flag[i], i, list, count);
-}
-
-// retry tiers: take the tasks whose flag is in the bit set `want` (bit f = flag value f)
-// and clear their flags; tasks flagged for a later tier keep theirs.  The list length
-// stays on the device: the next kernel reads it there.
-__global__ void k_collect_tier(int64_t n, int32_t* flag, uint32_t want, int64_t* list, unsigned long long* count) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int f = i < n ? flag[i] : 0;
-  const bool sel = f != 0 && ((want >> f) & 1u);
-  if (sel) flag[i] = 0;
-  block_append(sel, i, list, count);
-}
-
 // every task the first route tier flagged (overflow or general): the superset of what the
 // later tiers collect, so their collects scan this short list instead of every task.  It reads
 // every flag (55 MB at C2) and keeps few, so it runs at memory speed: four flags per thread in
@@ -545,8 +529,11 @@ __global__ __launch_bounds__(kFlaggedBlock) void k_collect_flagged(int64_t n, co
   if (f.w != 0) list[o++] = i0 + 3;
 }
 
-// k_collect_tier over the device-counted task list cand[0..*n_cand): a fixed grid
-// strides over it (block-uniform trip count: block_append synchronises the block)
+// A retry tier's collect over the device-counted list of flagged tasks cand[0..*n_cand): it
+// takes the tasks whose flag is in the bit set `want` (bit f = flag value f: otr_tiers.h
+// flag_bit) and clears their flags; tasks flagged for a later tier keep theirs.  The list
+// length stays on the device: the next kernel reads it there.  A fixed grid strides over
+// the list (block-uniform trip count: block_append synchronises the block)
 __global__ void k_collect_tier_from(const int64_t* cand, const unsigned long long* n_cand, int32_t* flag,
                                     uint32_t want, int64_t* list, unsigned long long* count) {
   const int64_t n = (int64_t)*n_cand;
@@ -771,7 +758,7 @@ struct Batch {
   static constexpr size_t kCntAt = line(kBanks * bank + n_ctr);
   static constexpr size_t kQueuesAt = kCntAt + line(C_CURSORS + kShards);
   static constexpr size_t kPQAt = kQueuesAt + line((size_t)kQueues * kQueueWords);
-  static constexpr size_t kControlWords = kPQAt + line(8 * kPQWords);
+  static constexpr size_t kControlWords = kPQAt + line(kPathQueues * kPQWords);
   unsigned long long *d_counters = nullptr, *cnt = nullptr, *pq = nullptr;
   int64_t *list = nullptr, *fail_tasks = nullptr, *flagged = nullptr;
   int32_t *task_ovf = nullptr, *d_turn = nullptr;
@@ -831,6 +818,25 @@ struct Batch {
     return mat.post_wait({runs...}, err);
   }
   int slabs(int tier, GSlabs* out);
+  // A retry tier's collect: the items whose flag is in `take` (otr_tiers.h: a tier's take
+  // column) go to `dst`, their number to list counter `word`, and their flags are cleared.
+  // Route tasks are looked for among the flagged ones, path steps among all of them.
+  enum class Chain { Route, Path };
+  void collect(Chain chain, uint32_t take, int word, int64_t* dst) {
+    if (chain == Chain::Route)
+      k_collect_tier_from<<<kCollectGrid, 1024, 0, stream>>>(flagged, cnt + C_FLAGGED, task_ovf, take, dst, cnt + word);
+    else
+      k_collect_tier_list<<<grid_ceil(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, take, dst, cnt + word);
+  }
+  // a route list tier's turn: its collect, and the arguments of its launch
+  RouteArgs take_list(int slot) {
+    collect(Chain::Route, kRouteTiers[slot].take, kRouteTiers[slot].list, list);
+    RouteArgs rb = ra;
+    rb.task_list = list;
+    rb.list_count = tier_list(slot);
+    rb.queue = tier_queue(slot);
+    return rb;
+  }
   template <class V>
   int dl(V& vec, const void* src, size_t n) {
     vec.resize(n ? n : 1);
@@ -1169,7 +1175,7 @@ int Batch::link() {
     ta.ntask8 = ntask8;
     ta.task8_off = task8_off;
     ta.nt8 = NT8;
-    ta.flag_turn = task_ovf;  // turn-mode tasks start in the first edge-state tier (flag 5)
+    ta.flag_turn = task_ovf;  // turn-mode tasks start in the first edge-state tier (RF_EDGE_FIRST)
     // the two-search first tier's table: a step expected beyond it is flagged here
     ta.est_first_keys = route_g == 2 ? (OTR_CAP1 * OTR_LOAD1) / 8 : 0;
     ta.est_k = est_k;
@@ -1278,23 +1284,27 @@ void Batch::first_tier(int slot, int cap, int g_, int64_t n_tasks, int64_t task_
   out->route_tier_code[slot] = route_tier_code(slot, cap, g_);
 }
 
-// a node retry tier's kernel by its code (otr_tiers.h kRetryShapes: every code OTR_TIERS
-// accepts has its kernel here)
-template <int I = 0, class F>
-static bool with_retry_shape(int code, F&& f) {
-  if constexpr (I < kRetryShapeN) {
-    if (code == kRetryShapes[I].code()) {
+// f(std::integral_constant<int, i>) for the row i of a table of N rows: how a tier picks the
+// kernel instance of its row (a table size is a template argument); false: no such row
+template <int N, int I = 0, class F>
+static bool with_row(int i, F&& f) {
+  if constexpr (I < N) {
+    if (i == I) {
       f(std::integral_constant<int, I>{});
       return true;
     }
-    return with_retry_shape<I + 1>(code, f);
+    return with_row<N, I + 1>(i, f);
   } else {
     return false;
   }
 }
 
+// a node retry tier's kernel by its code (otr_tiers.h kRetryShapes: every code OTR_TIERS
+// accepts has its kernel here)
 int Batch::retry_tier(int code, const RouteArgs& rb, unsigned long long* ctr_bank) {
-  const bool known = with_retry_shape(code, [&](auto i) {
+  int row = 0;
+  while (row < kRetryShapeN && kRetryShapes[row].code() != code) ++row;
+  const bool known = with_row<kRetryShapeN>(row, [&](auto i) {
     constexpr int cap = kRetryShapes[decltype(i)::value].cap, gw = kRetryShapes[decltype(i)::value].g;
     // persistent grids over per-XCD queues: about twice a tier's resident waves (256 CUs x
     // 4 SIMDs x 8 waves for the small tables, fewer for the big ones, whose LDS admits
@@ -1434,9 +1444,9 @@ int Batch::route_retry() {
   int rc;
   // overflow retries with larger LDS tables (same results, fewer resident waves): each
   // tier takes its list on the device and runs a fixed grid over it — no host round
-  // trip between tiers.  Tier t takes the previous tier's overflows (flag 1) and the
-  // first-tier tasks whose size estimate starts them in a tier <= t (flags 16 + u, u <= t);
-  // OTR_TIERS (A/B knob) lists the retry kernels.
+  // trip between tiers.  Tier t takes the previous tier's overflows and the first-tier tasks
+  // whose size estimate starts them in a tier <= t (otr_tiers.h node_tier_mask); OTR_TIERS
+  // (A/B knob) lists the retry kernels.
   tb(OTR_STAGE_ROUTE_BIG);
   const std::vector<int>& tiers = route_tiers();
   const int ntier = (int)tiers.size();
@@ -1467,13 +1477,7 @@ int Batch::route_retry() {
   }
   for (int tier = 0; tier < (node_tasks ? ntier : 0); ++tier) {  // (no node task: no node tier)
     const int slot = SLOT_NODE + tier;
-    unsigned long long* c = tier_list(slot);
-    k_collect_tier_from<<<kCollectGrid, 1024, 0, stream>>>(flagged, cnt + C_FLAGGED, task_ovf,
-                                                          0x2u | (((2u << tier) - 1u) << 16), list + 0, c);
-    RouteArgs rb = ra;
-    rb.task_list = list;
-    rb.list_count = c;
-    rb.queue = tier_queue(slot);
+    RouteArgs rb = take_list(slot);
     const bool din = nd_in(tier) && nd_out(tier - 1) && ndump[(tier + 1) & 1] != nullptr;
     const bool dout = nd_out(tier) && ndump[tier & 1] != nullptr;
     rb.dump_in = din ? ndump[(tier + 1) & 1] : nullptr;
@@ -1489,29 +1493,28 @@ int Batch::route_retry() {
   }
 #ifndef OTR_FORCE_GENERAL  // (test build: every search in k_general)
   // the node-mode tasks whose (length << sh | time) words need more than 32 bits
-  // (flag 3: long gaps between states) run in an LDS table of 64-bit words (same labels,
-  // DESIGN.md §3.5); what outgrows it is flagged 3 again
+  // (RF_GENERAL: long gaps between states) run in an LDS table of 64-bit words (same labels,
+  // DESIGN.md §3.5); what outgrows it is flagged RF_GENERAL again.  It runs ahead of the
+  // edge-state tiers for a reason: otr_tiers.h kRouteOrder
   {
-    constexpr int cap = kRouteTiers[SLOT_WIDE64].cap;
-    unsigned long long* c = tier_list(SLOT_WIDE64);
-    k_collect_tier_from<<<kCollectGrid, 1024, 0, stream>>>(flagged, cnt + C_FLAGGED, task_ovf, 0x8u, list, c);
-    RouteArgs rb = ra;
-    rb.task_list = list;
-    rb.list_count = c;
-    rb.queue = tier_queue(SLOT_WIDE64);
-    out->route_tier_code[SLOT_WIDE64] = route_tier_code(SLOT_WIDE64, cap, 1);
+    constexpr RouteTier w = kRouteTiers[SLOT_WIDE64];
+    const RouteArgs rb = take_list(SLOT_WIDE64);
+    out->route_tier_code[SLOT_WIDE64] = route_tier_code(SLOT_WIDE64, w.cap, 1);
     tier_begin(SLOT_WIDE64);
-    if (rwork) k_route<cap, 1, true, true, true><<<pgrid(4096, NT), 64, 0, stream>>>(g, rb, tier_bank(SLOT_WIDE64));
-    else k_route<cap, 1, true, true, false><<<pgrid(4096, NT), 64, 0, stream>>>(g, rb, nullptr);
+    if (rwork) k_route<w.cap, 1, true, true, true><<<pgrid(w.grid, NT), 64, 0, stream>>>(g, rb, tier_bank(SLOT_WIDE64));
+    else k_route<w.cap, 1, true, true, false><<<pgrid(w.grid, NT), 64, 0, stream>>>(g, rb, nullptr);
     tier_end(SLOT_WIDE64);
   }
 #endif
   return OTR_OK;
 }
 
+// the table of edge-state tier et (kEdgeSlots): the first one's is a build knob
+static constexpr int edge_cap(int et) { return kRouteTiers[kEdgeSlots[et]].cap ? kRouteTiers[kEdgeSlots[et]].cap : OTR_E1CAP; }
+
 // edge-state tiers (turn-cost modes, otr_edge1.h), in the order of kEdgeSlots: OTR_E1CAP (360)
-// states (flag 5), 512 (flag 6), 1024 (flag 7); what outgrows those (flag 3) goes on to the
-// global-memory tiers
+// states, 512, 1024, each taking what the one before outgrew; what outgrows those goes on to
+// the global-memory tiers (otr_tiers.h edge_overflow_flag)
 int Batch::route_edge() {
   if (NT == 0) return OTR_OK;
   if (turns) {
@@ -1522,9 +1525,7 @@ int Batch::route_edge() {
     // restart in the next table (same results)
     unsigned long long* dump[2] = {nullptr, nullptr};
     uint32_t dslots[2] = {0u, 0u};
-    constexpr int cap512 = kRouteTiers[SLOT_EDGE_512].cap, cap1024 = kRouteTiers[SLOT_EDGE_1024].cap;
-    const int caps[3] = {OTR_E1CAP, cap512, cap1024};
-    const uint32_t dwords[2] = {e1_dump_words(OTR_E1CAP), e1_dump_words(cap512)};
+    const uint32_t dwords[2] = {e1_dump_words(edge_cap(0)), e1_dump_words(edge_cap(1))};
     if (eresume && task_dump) {
       const int64_t cap_bytes[2] = {4ll << 30, 1ll << 30};
       const int64_t wanted[2] = {std::max<int64_t>(NT / 16, 4096), std::max<int64_t>(NT / 64, 1024)};
@@ -1537,11 +1538,9 @@ int Batch::route_edge() {
     }
     for (int et = 0; et < 3; ++et) {
       const int slot = kEdgeSlots[et];
-      out->route_tier_code[slot] = route_tier_code(slot, caps[et], 1);
-      unsigned long long* c = tier_list(slot);
-      k_collect_tier_from<<<kCollectGrid, 1024, 0, stream>>>(flagged, cnt + C_FLAGGED, task_ovf, 0x20u << et, list, c);
-      RouteArgs rb = ra;
-      rb.task_list = list;
+      out->route_tier_code[slot] = route_tier_code(slot, edge_cap(et), 1);
+      RouteArgs rb = take_list(slot);
+      const unsigned long long* c = rb.list_count;
       // the first edge tier's list in spatial order (k_sort_*: one band of the map per XCD)
       static const bool esort = !getenv("OTR_SORT") || atoi(getenv("OTR_SORT")) != 0;  // A/B knob
       int64_t* list2 = nullptr;
@@ -1560,11 +1559,9 @@ int Batch::route_edge() {
         k_sort_place<<<grid_ceil(NT, 1024), 1024, 0, stream>>>(list, c, task_rec, shift, hist, list2);
         rb.task_list = list2;
       }
-      rb.list_count = c;
-      rb.queue = tier_queue(slot);
       rb.dump_in = et > 0 ? dump[et - 1] : nullptr;
       rb.dump_in_words = et > 0 ? dwords[et - 1] : 0u;
-      rb.dump_in_cap = et == 1 ? OTR_E1CAP : cap512;
+      rb.dump_in_cap = et == 1 ? edge_cap(0) : edge_cap(1);
       rb.dump_out = et < 2 ? dump[et] : nullptr;  // (the last tier never dumps: otr_tiers.h)
       rb.dump_ctr = queues + dump_ctr_word(slot);
       rb.dump_out_words = et < 2 ? dwords[et] : 0u;
@@ -1576,9 +1573,9 @@ int Batch::route_edge() {
       // 512, 6 at 1024) claiming tasks from per-XCD queues; steps with more than 32
       // targets (modes keeping > 32 candidates) pass the lean tiers (their TG = 32) on to
       // k_general
-      if (et == 0) k_route_e1<OTR_E1CAP><<<pgrid(8192, NT), 64, 0, stream>>>(g, rb, rcn);
-      else if (et == 1) k_route_e1<cap512><<<pgrid(4096, NT), 64, 0, stream>>>(g, rb, rcn);
-      else k_route_e1<cap1024><<<pgrid(2048, NT), 64, 0, stream>>>(g, rb, rcn);
+      with_row<3>(et, [&](auto i) {
+        k_route_e1<edge_cap(decltype(i)::value)><<<pgrid(kRouteTiers[slot].grid, NT), 64, 0, stream>>>(g, rb, rcn);
+      });
       tier_end(slot);
     }
   }
@@ -1594,14 +1591,12 @@ int Batch::route_global() {
   int rc;
   for (int gt = 0; gt < 2; ++gt) {
     const int slot = SLOT_GLOBAL + gt;
-    unsigned long long* c = tier_list(slot);
-    k_collect_tier_from<<<kCollectGrid, 1024, 0, stream>>>(flagged, cnt + C_FLAGGED, task_ovf,
-                                                          gt == 0 ? 0x1Eu : 0x2u, list, c);
+    collect(Chain::Route, kRouteTiers[slot].take, kRouteTiers[slot].list, list);
     GSlabs gs2;
     if ((rc = slabs(gt, &gs2))) return rc;
     ga.mode = 0;
     ga.list = list;
-    ga.list_count = c;
+    ga.list_count = tier_list(slot);
     ga.flag = task_ovf;
     ga.counters = tier_bank(slot);
     out->route_tier_code[slot] = route_tier_code(slot, (int)gs2.cap, 0);
@@ -1610,8 +1605,7 @@ int Batch::route_global() {
     tier_end(slot);
   }
   // tasks still flagged (beyond a 1M-state slab): their traces get OTR_MATCH_ERROR
-  k_collect_tier_from<<<kCollectGrid, 1024, 0, stream>>>(flagged, cnt + C_FLAGGED, task_ovf, 0x1Eu, fail_tasks,
-                                                        cnt + C_TASKS_LEFT);
+  collect(Chain::Route, kTasksLeft.take, kTasksLeft.list, fail_tasks);
   te(OTR_STAGE_ROUTE_BIG);
   return OTR_OK;
 }
@@ -1754,7 +1748,7 @@ int Batch::paths_attempt(int64_t capacity, bool again) {
     HIPCHK(hipMemsetAsync(cnt + C_PATH_TIER, 0, 8 * (C_CAP_FLAG + 1 - C_PATH_TIER), stream));
     HIPCHK(hipMemsetAsync(cnt + C_EDGE_PATH, 0, 8 * 2, stream));  // edge-state path tier counts
     HIPCHK(hipMemsetAsync(cnt + C_CURSORS, 0, 8 * kShards, stream));
-    HIPCHK(hipMemsetAsync(pq, 0, 8 * 8 * kPQWords, stream));  // the path retry tiers' work queues
+    HIPCHK(hipMemsetAsync(pq, 0, 8 * kPathQueues * kPQWords, stream));  // the path retry tiers' work queues
   }
   PathArgs pa{};
   pa.steps = steps;
@@ -1806,30 +1800,10 @@ int Batch::paths_attempt(int64_t capacity, bool again) {
   }
   te(OTR_STAGE_PATHS);
   tb(OTR_STAGE_PATHS_BIG);
-  // large-table retries for table overflows (flag 1), on device-side lists; each
-  // launch's waves claim steps from its own per-XCD queue (XcdQueue)
-  for (int tier = 0; tier < 3; ++tier) {
-    unsigned long long* c = cnt + C_PATH_TIER + tier;
-    k_collect_tier_list<<<grid_ceil(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, 0x2u, list, c);
-    PathArgs pb = pa;
-    pb.queue = pq + tier * kPQWords;
-    if (tier == 0) k_paths<512, 1><<<pgrid(16384, S), 64, 0, stream>>>(g, pb, list, c);
-    else if (tier == 1) k_paths<1024, 1><<<pgrid(8192, S), 64, 0, stream>>>(g, pb, list, c);
-    else k_paths<4096, 1><<<pgrid(4096, S), 64, 0, stream>>>(g, pb, list, c);
-  }
-  // turn-cost winners (flag 5): the edge-state LDS search, 384 then 2048 states
-  if (turn_modes != 0u) {
-    for (int et = 0; et < 2; ++et) {
-      unsigned long long* c = cnt + C_EDGE_PATH + et;
-      k_collect_tier_list<<<grid_ceil(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, et == 0 ? 0x20u : 0x40u,
-                                                                   list, c);
-      PathArgs pb = pa;
-      pb.queue = pq + (3 + et) * kPQWords;
-      if (et == 0) k_paths_edge<384><<<pgrid(4096, S), 64, 0, stream>>>(g, pb, d_turn, list, c, 6);
-      else k_paths_edge<2048><<<pgrid(512, S), 64, 0, stream>>>(g, pb, d_turn, list, c, 3);
-    }
-  }
-  // 64-bit labels, the largest-table overflows and what the edge tiers left: k_general
+  // The retry tiers in the order of kPathTiers (otr_tiers.h), on device-side lists: larger
+  // node tables for table overflows, the edge-state LDS search for turn-cost winners, then
+  // k_general for 64-bit labels, the largest-table overflows and what the edge tiers left.
+  // Each LDS launch's waves claim steps from its own per-XCD queue (XcdQueue).
   ga.steps = steps;
   ga.winner = va.winner;
   ga.path_off = path_off;
@@ -1838,21 +1812,35 @@ int Batch::paths_attempt(int64_t capacity, bool again) {
   ga.cursor = cnt + C_CURSORS;
   ga.capacity = capacity;
   ga.cap_flag = (int32_t*)(cnt + C_CAP_FLAG);
-  for (int gt = 0; gt < 2; ++gt) {
-    unsigned long long* c = cnt + C_PATH_GLOBAL + gt;
-    k_collect_tier_list<<<grid_ceil(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, gt == 0 ? 0xAu : 0x2u, list,
-                                                                 c);
-    GSlabs gs2;
-    if ((rc = slabs(gt, &gs2))) return rc;
-    ga.mode = 1;
-    ga.list = list;
-    ga.list_count = c;
-    ga.flag = step_ovf;
-    ga.counters = nullptr;
-    k_general<<<pgrid(gs2.n, S), kGenThreads, 0, stream>>>(g, ga, gs2);
+  int gt = 0;  // the next global-memory tier's slabs
+  for (int t = 0; t < kPathTierN; ++t) {
+    const PathTier& pt = kPathTiers[t];
+    if (pt.kind == PathKind::EdgeState && turn_modes == 0u) continue;
+    unsigned long long* c = cnt + pt.list;
+    collect(Chain::Path, pt.take, pt.list, list);
+    if (pt.kind == PathKind::Global) {
+      GSlabs gs2;
+      if ((rc = slabs(gt++, &gs2))) return rc;
+      ga.mode = 1;
+      ga.list = list;
+      ga.list_count = c;
+      ga.flag = step_ovf;
+      ga.counters = nullptr;
+      k_general<<<pgrid(gs2.n, S), kGenThreads, 0, stream>>>(g, ga, gs2);
+      continue;
+    }
+    PathArgs pb = pa;
+    pb.queue = pq + pt.queue * kPQWords;
+    with_row<kPathTierN>(t, [&](auto i) {
+      constexpr PathTier row = kPathTiers[decltype(i)::value];
+      if constexpr (row.kind == PathKind::Node)
+        k_paths<row.cap, 1><<<pgrid(row.grid, S), 64, 0, stream>>>(g, pb, list, c);
+      else if constexpr (row.kind == PathKind::EdgeState)
+        k_paths_edge<row.cap><<<pgrid(row.grid, S), 64, 0, stream>>>(g, pb, d_turn, list, c, row.overflow);
+    });
   }
   // steps still flagged (beyond a 1M-state slab): named after the final sync
-  k_collect_tier_list<<<grid_ceil(S, 1024), 1024, 0, stream>>>(nscan_d, step_ovf, 0xAu, list, cnt + C_PATHS_LEFT);
+  collect(Chain::Path, kPathsLeft.take, kPathsLeft.list, list);
   te(OTR_STAGE_PATHS_BIG);
   return OTR_OK;
 }

@@ -478,9 +478,9 @@ __global__ __launch_bounds__(kGenThreads) void k_general(DevGraph G, GenArgs a, 
         g_reset(key, lab, qmark, touched, &sh, cap);
       }
       if (ok) {
-        if (tid == 0) a.flag[item] = 0;
+        if (tid == 0) a.flag[item] = RF_NONE;
       } else if (tid == 0) {
-        a.flag[item] = 1;
+        a.flag[item] = kSlabOverflow;  // (the larger slabs, then the left-over collect: otr_tiers.h)
         atomicAdd(a.n_overflow, 1ull);
       }
     } else {
@@ -495,7 +495,7 @@ __global__ __launch_bounds__(kGenThreads) void k_general(DevGraph G, GenArgs a, 
       const bool ok = run(T, nullptr);
       if (!ok) {
         if (tid == 0) {
-          a.flag[item] = 1;
+          a.flag[item] = kSlabOverflow;
           atomicAdd(a.n_overflow, 1ull);
         }
       } else {
@@ -569,7 +569,7 @@ __global__ __launch_bounds__(kGenThreads) void k_general(DevGraph G, GenArgs a, 
         const uint32_t n = s_path[0];
         if (n == 0xFFFFFFFFu) {
           if (tid == 0) {
-            a.flag[item] = 1;  // cannot happen for a valid winner; reported as an overflow
+            a.flag[item] = kSlabOverflow;  // cannot happen for a valid winner; reported as an overflow
             atomicAdd(a.n_overflow, 1ull);
           }
         } else {
@@ -587,7 +587,7 @@ __global__ __launch_bounds__(kGenThreads) void k_general(DevGraph G, GenArgs a, 
             if (tid == 0) {
               a.path_off[s] = base;
               a.path_len[s] = (int32_t)n;
-              a.flag[item] = 0;
+              a.flag[item] = PF_NONE;
             }
           }
         }

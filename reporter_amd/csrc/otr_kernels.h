@@ -24,6 +24,7 @@
 #include "otr_pred.h"     // the round's 32-bit predicates (in_final32, target_final32)
 #include "otr_report.h"
 #include "otr_tilerow.h"  // the stream rules' rows and the wave scan, shared with K15
+#include "otr_tiers.h"    // the retry flags (RouteFlag, PathFlag), the task record word, the force_edge bits
 
 // the first tier's table (slots per search, two searches per wave) and its load limit in
 // eighths (A/B knobs)
@@ -1505,10 +1506,9 @@ struct RouteArgs {
   const int32_t* turn;        // [OTR_MODES][181] turn cost tables (mm), turn modes only
   uint32_t* trans_tc;         // turn cost (mm) per transition, turn modes only
   double inv_beta[OTR_MODES];
-  int32_t* overflow_flag;     // per task: 1/2 retry in a larger LDS table, 3 the global-memory search,
-                              // 5 / 6 the edge-state tiers
+  int32_t* overflow_flag;     // per task: the tier it goes on to (otr_tiers.h RouteFlag), RF_NONE: done
   // first tier: a search whose expected size (keys) exceeds its table starts in the first
-  // retry tier that holds it (flag 16 + tier): expected keys = est_k * r^2 with r = the
+  // retry tier that holds it (route_start_flag): expected keys = est_k * r^2 with r = the
   // step's reach, min(length bound, time bound x est_v[mode])
   float est_k;                // keys per m^2 of reach (calibrated on the graph's node density)
   float est_v[OTR_MODES];     // m/s: the mode's typical speed (50 km/h, capped by the mode's)
@@ -1518,13 +1518,7 @@ struct RouteArgs {
   int64_t task_base;          // first tier: its first task (the small tier's tasks come first)
   unsigned long long* queue;  // list tiers: this launch's 8 per-XCD unit counters (XcdQueue), zeroed
   unsigned long long* stamps;  // diagnostic build (OTR_STAMPS): bank 0 of the work counters (phase cycles)
-  int force_edge;             // test build only (OTR_FORCE_RETRY, env OTR_FORCE_EDGE): bits 0 / 1 / 2 fail
-                              // every OTR_E1CAP (360) / 512 / 1024-state edge-state route search (the
-                              // next tier takes it), bits 3 / 4 every 384 / 2048-state winner path;
-                              // bits 5 / 6 stop every OTR_E1CAP / 512-state search after 2 / 4 rounds
-                              // and resume it in the next table (otr_edge1.h e1_dump / e1_restore);
-                              // bit 7 stops every node retry-tier search that has dump slots after 2
-                              // rounds (search_run, NDump): resumed tier after tier to the last
+  int force_edge;             // test build only (OTR_FORCE_RETRY, env OTR_FORCE_EDGE): otr_tiers.h ForceEdge bits
   // retry tiers (node and edge-state): a search that outgrows its table is dumped between
   // two rounds and resumed in the next table (search_run NDump, otr_edge1.h e1_dump)
   const unsigned long long* dump_in;  // the previous tier's dumps (null: every search starts afresh)
@@ -1560,7 +1554,8 @@ struct TaskArgs {
   const int64_t* ntask8;      // tiny-tier steps' task counts, or null
   const int64_t* task8_off;   // their exclusive offsets: tiny-tier tasks are [0, nt8)
   int64_t nt8;
-  int32_t* flag_turn;         // per task: 5 for a turn-mode task (the first edge-state tier's list), else 0; or null
+  int32_t* flag_turn;         // per task (the route stage's overflow_flag): RF_EDGE_FIRST for a turn-mode
+                              // task, else RF_NONE; or null
   // the two-search first tier's size estimate (RouteArgs est_*): a node-mode step whose
   // estimated keys exceed est_first_keys (0: no estimate) starts in a retry tier
   int est_first_keys;
@@ -1579,13 +1574,14 @@ struct TaskArgs {
 // source edge is its own task (the edge-state search).  The task's representative (its lowest source) writes the task
 // record every route kernel reads (its state and source mask included):
 //   rec[3t]   = {s, sp, root, bound_mm}
-//   rec[3t+1] = {d0min, Kb | mode << 8 | forced << 10 | sh << 11 | general << 16 | turn << 17 | pre << 18,
-//                mask lo, mask hi}
+//   rec[3t+1] = {d0min, Kb | mode << 8 | forced << 10 | sh << 11 | general << 16 | turn << 17 | pre << 18 |
+//                start tier << 19 (otr_tiers.h task_word packs it, tw_* read it), mask lo, mask hi}
 //   rec[3t+2] = {0, time bound bt, trans_off[s] lo, hi}
 // general: the task runs in the global-memory search (a bound whose packed labels would
-// not fit 32 bits, or a turn mode: edge-based labels).  pre (4 bits): 1 | the retry tier
-// << 1 of a step whose size estimate exceeds the first tier's table (the first tier flags
-// it 16 + tier without loading its step); the estimate is per step (bound, time bound, mode).
+// not fit 32 bits, or a turn mode: edge-based labels).  pre: a step whose size estimate
+// exceeds the first tier's table, with the retry tier (3 bits) it starts in (the first tier
+// flags it route_start_flag(tier) without loading its step); the estimate is per step
+// (bound, time bound, mode).
 template <int G>
 __global__ __launch_bounds__(256) void k_tasks(TaskArgs a) {
   constexpr int GL = OTR_WAVE / G;
@@ -1640,14 +1636,13 @@ __global__ __launch_bounds__(256) void k_tasks(TaskArgs a) {
     if (est > (float)a.est_first_keys) {
       uint32_t st = 0;
       while ((int)st + 1 < a.n_tiers && (float)a.tier_keys[st] < est) ++st;
-      pre = 1u | (st << 1);
+      pre = task_start(st);
     }
   }
-  const uint32_t meta = (uint32_t)a.cand_count[s] | ((uint32_t)md << 8) | ((a.forced[s] ? 1u : 0u) << 10) |
-                        (sh << 11) | ((general ? 1u : 0u) << 16) | (turn << 17) | (pre << 18);
+  const uint32_t meta = task_word((uint32_t)a.cand_count[s], (uint32_t)md, a.forced[s] ? 1u : 0u, sh, general ? 1u : 0u, turn, pre);
   const int64_t to = a.trans_off[s];
-  // 5: the edge-state tiers (otr_edge1.h); 0 otherwise, so the flags need no fill beforehand
-  if (a.flag_turn) a.flag_turn[o] = turn ? 5 : 0;
+  // the edge-state tiers (otr_edge1.h), or none: every task's flag is written, so the flags need no fill beforehand
+  if (a.flag_turn) a.flag_turn[o] = turn ? RF_EDGE_FIRST : RF_NONE;
   a.rec[3 * o] = make_uint4((uint32_t)s, (uint32_t)sp, root, bmm);
   a.rec[3 * o + 1] = make_uint4(d0min, meta, (uint32_t)same, (uint32_t)(same >> 32));
   a.rec[3 * o + 2] = make_uint4(0u, (uint32_t)bt, (uint32_t)to, (uint32_t)((uint64_t)to >> 32));
@@ -1672,7 +1667,7 @@ __device__ inline int nth_set_bit(unsigned long long m, int q) {
 // per-XCD queues (its length never crosses to the host).  WIDE: the table keeps 64-bit
 // packed words and takes the tasks whose (length << sh | time) words do not fit 32 bits
 // (`general` in the record).  The LDS tiers run node-mode tasks; turn-mode (edge-state)
-// tasks carry flag 5 from k_tasks and run in the edge-state tiers (otr_edge1.h), then
+// tasks carry RF_EDGE_FIRST from k_tasks and run in the edge-state tiers (otr_edge1.h), then
 // k_general.
 template <int CAP, int G, bool LIST, bool WIDE = false, bool CNT = true>
 __device__ __forceinline__ void route_unit(const DevGraph& gr, const RouteArgs& a, unsigned long long* counters,
@@ -1722,19 +1717,21 @@ __device__ __forceinline__ void route_unit(const DevGraph& gr, const RouteArgs& 
     const int64_t s = r0.x;
     const unsigned long long mask = ((unsigned long long)r1.w << 32) | r1.z;
     const int64_t sp = r0.y;
-    Kb = (int)(r1.y & 0xFFu);
-    K.sh = (r1.y >> 11) & 31u;
-    const bool general = (r1.y >> 16) & 1u;  // re-read after the search
+    Kb = (int)tw_Kb(r1.y);
+    K.sh = tw_sh(r1.y);
+    const bool general = tw_general(r1.y);  // re-read after the search
     // targets are lanes of the group (wider steps go to a G = 1 tier); 32-bit tables leave
     // the tasks whose packed words need 64 bits to the WIDE tier
-    fits = Kb <= Gr::GL && (WIDE || !general) && !((r1.y >> 17) & 1u);
+    // (tw_turn and, below, tw_forced written out: a call on the right of && is compiled by
+    // another route, and the route kernels would no longer be the code that was measured)
+    fits = Kb <= Gr::GL && (WIDE || !general) && !((r1.y >> TW_TURN) & 1u);
     // a step too big for this table starts in a retry tier (k_tasks' estimate): no load of it
-    const bool pre = G >= 2 && !LIST && have && ((r1.y >> 18) & 1u);
+    const bool pre = G >= 2 && !LIST && have && tw_pre(r1.y);
     if (pre) {
-      start_tier = (int)((r1.y >> 19) & 7u);
+      start_tier = (int)tw_start_tier(r1.y);
       fits = false;
     }
-    mode_bit = 1u << ((r1.y >> 8) & 3u);
+    mode_bit = 1u << tw_mode(r1.y);
     bmm = r0.w;
     root = r0.z;
     d0min = r1.x;
@@ -1781,7 +1778,7 @@ __device__ __forceinline__ void route_unit(const DevGraph& gr, const RouteArgs& 
       feasible_root = feasible_root && t0 <= (uint32_t)bt;
       pt = t0 <= (uint32_t)bt ? (uint32_t)bt - t0 : 0u;
     }
-    forced = have && ((r1.y >> 10) & 1u);
+    forced = have && ((r1.y >> TW_FORCED) & 1u);
     const unsigned long long need_mask = __ballot(needed);
     search = have && fits && !forced && feasible_root && Gr::mine(need_mask) != 0ull;
     if (needed) {
@@ -1807,7 +1804,7 @@ __device__ __forceinline__ void route_unit(const DevGraph& gr, const RouteArgs& 
     nd.words = a.dump_out_words;
     nd.slots = a.dump_out_slots;
 #ifdef OTR_FORCE_RETRY
-    nd.stop_rounds = (a.force_edge >> 7) & 1 ? 2 + Gr::g() : 0;  // (G = 2: the groups stop in different rounds)
+    nd.stop_rounds = (a.force_edge & FE_STOP_NODE) ? 2 + Gr::g() : 0;  // (G = 2: the groups stop in different rounds)
 #endif
   }
   search_init<CAP, LM, G>(Ls);
@@ -1918,17 +1915,17 @@ __device__ __forceinline__ void route_unit(const DevGraph& gr, const RouteArgs& 
       }
     }
   }
-  // general (flag 3): the global-memory search; overflow: retry with a bigger table (1); a
-  // first-tier search expected beyond its table starts in retry tier t (16 + t); turn modes:
-  // none here (k_tasks flagged them 5, for the edge-state tiers otr_edge1.h / otr_edge.h)
+  // general: the 64-bit table and the global-memory search; overflow: retry with a bigger
+  // table; a first-tier search expected beyond its table starts in retry tier t; turn modes:
+  // none here (k_tasks flagged them for the edge-state tiers otr_edge1.h / otr_edge.h)
   if (have && !ok && !forced && lane == 0) {
     const uint32_t meta = a.rec[3 * task + 1].y;
-    const bool general = ((meta >> 16) & 1u) != 0u, turn = ((meta >> 17) & 1u) != 0u;
+    const bool general = tw_general(meta) != 0u, turn = tw_turn(meta) != 0u;
 #ifdef OTR_FORCE_GENERAL
-    a.overflow_flag[task] = 3;  // test build: every search (edge-state ones too) in k_general
+    a.overflow_flag[task] = RF_GENERAL;  // test build: every search (edge-state ones too) in k_general
 #else
-    // (turn-mode tasks carry flag 5 from k_tasks: the edge-state tiers take them)
-    if (!turn) a.overflow_flag[task] = general ? 3 : (start_tier >= 0 ? 16 + start_tier : 1);
+    // (turn-mode tasks carry RF_EDGE_FIRST from k_tasks: the edge-state tiers take them)
+    if (!turn) a.overflow_flag[task] = general ? RF_GENERAL : (start_tier >= 0 ? route_start_flag(start_tier) : RF_OVERFLOW);
 #endif
     if (!WIDE && !turn && a.task_dump != nullptr) a.task_dump[task] = dslot;  // (-1: the next tier restarts it)
   }
@@ -2354,12 +2351,12 @@ struct PathArgs {
   uint32_t* path;              // bump-allocated edge list
   unsigned long long* cursor;
   int64_t capacity;
-  int32_t* overflow_flag;      // per step index: 1 table overflow, 3 global-memory search
+  int32_t* overflow_flag;      // per step index: the tier it goes on to (otr_tiers.h PathFlag), PF_NONE: done
   int32_t* cap_flag;           // global: path buffer too small
   const int32_t* cand_count;
   const int64_t* trans_off;    // the route lengths k_route found (u32 mm per transition)
   const uint32_t* trans;
-  int force_edge;              // test build only (OTR_FORCE_RETRY): RouteArgs::force_edge bits 3-4
+  int force_edge;              // test build only (OTR_FORCE_RETRY): RouteArgs::force_edge, FE_FAIL_PATH_*
   unsigned long long* queue;   // list tiers: this launch's per-XCD step counters (XcdQueue), zeroed
   bool from_back;              // first tier: its steps are the last *n_steps_dev of steps[0, n_steps)
                                // (k_step_lists: the small-search tier's at the front)
@@ -2432,13 +2429,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(G >= 2 ? 6 :
                && false  // test build: every winner path in k_general
 #endif
     ) {
-      if (gl == 0) a.overflow_flag[k] = 5;  // turn costs: the edge-state search (otr_edge.h)
+      if (gl == 0) a.overflow_flag[k] = PF_EDGE_FIRST;  // turn costs: the edge-state search (otr_edge.h)
     } else if (!pack_fits(bmm, K.sh)
 #ifdef OTR_FORCE_GENERAL
                || true
 #endif
     ) {
-      if (gl == 0) a.overflow_flag[k] = 3;  // 64-bit labels: k_general
+      if (gl == 0) a.overflow_flag[k] = PF_GENERAL;  // 64-bit labels: k_general
     } else {
       active = true;
       mode_bit = 1u << mode;
@@ -2463,7 +2460,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(G >= 2 ? 6 :
                                            1, nullptr, nullptr, nullptr);
   SearchLds<CAP, true>& L = Ls[Gr::g()];
   if (active && !ok) {
-    if (gl == 0) a.overflow_flag[k] = 1;  // the next (larger) table
+    if (gl == 0) a.overflow_flag[k] = PF_OVERFLOW;  // the next (larger) table
     active = false;
   }
   // walk predecessor edges T → S (the group's lane 0).  The predecessor node of every
@@ -2509,7 +2506,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(G >= 2 ? 6 :
   }
   n = __shfl(n, Gr::g() * Gr::GL);
   if (active && n < 0) {
-    if (gl == 0) a.overflow_flag[k] = 1;
+    if (gl == 0) a.overflow_flag[k] = PF_OVERFLOW;
     active = false;
   }
   // bump allocation in one of 64 regions (a single cursor serialises ~1M returning
